@@ -93,6 +93,27 @@ BOX_BYTES_PER_SAMPLE = 16
 BOX_TIME_BYTES_PER_SAMPLE = 13
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: the .npy files of one run stay below 64 MB in all
+
+
+def dump_outputs(torch, outdir, outputs):
+    """--dump-outputs: writes the flags the timed path returned in its last step, so that two builds can be compared
+    output for output on the same seeded inputs.  Per output `name` (bool, (..., time, chan)), as float32:
+      <name>_per_chan.npy  flags counted over the time axis, (..., chan): every flag of the output enters a count;
+      <name>.npy           the 0/1 flags themselves.
+    Each file gets an equal share of DUMP_BYTES; an array larger than its share is written as a fixed sample instead:
+    the elements at the sorted, de-duplicated flat indices RandomState(0).randint(0, size, share / 4)."""
+    os.makedirs(outdir, exist_ok=True)
+    cap = DUMP_BYTES // (2 * len(outputs)) // 4
+    for name, flags in outputs:
+        for fname, arr in ((name + "_per_chan", flags.sum(dim=-2)), (name, flags)):
+            n = arr.numel()
+            if n > cap:
+                idx = np.unique(np.random.RandomState(0).randint(0, n, size=cap, dtype=np.int64))
+                arr = arr.reshape(-1)[torch.from_numpy(idx).to(arr.device)]
+            np.save(os.path.join(outdir, fname + ".npy"), arr.float().cpu().numpy())
+
+
 def box_radius(sigma):
     """int(0.5 * sqrt(12 sigma^2 / passes + 1)), flagging.py:451 (passes = 4)"""
     return int(0.5 * np.sqrt(12.0 * sigma * sigma / 4.0 + 1.0))
@@ -440,7 +461,7 @@ def ska_stream(torch, tricolour_amd, device, kw, nbl, ncorr, T, F, slabs, warmup
     1-D spectrum path of these windows is 65536 sequential steps on two workgroups -- 10 % of a slab's time with 254 CUs
     idle -- so consecutive slabs run as two concurrent calls (each its own workspace) and one slab's spectrum kernels
     run under the other's 2-D kernels, the way two dask threads would issue them.  Returns (seconds for `slabs` slabs
-    with transfers, seconds for the same slabs device-resident, flagged fraction)."""
+    with transfers, seconds for the same slabs device-resident, flagged fraction, flags of the last device-resident slab)."""
     from tricolour_amd import flagging
     shape = (nbl, ncorr, T, F)
     NB = kstreams + 1
@@ -507,7 +528,7 @@ def ska_stream(torch, tricolour_amd, device, kw, nbl, ncorr, T, F, slabs, warmup
     flagged = float(outs[0].float().mean().item())
     if kstreams > 1:
         flagging.set_num_threads(1)
-    return t_stream, t_res, flagged
+    return t_stream, t_res, flagged, outs[(slabs - 1) % kstreams]
 
 
 def scatter_leg(torch, dist, tricolour_amd, device, rank, world, kw, ncorr, T, F, bl_per_rank, backend, root_budget_gb=2.0):
@@ -616,7 +637,7 @@ def other_workload_legs(torch, tricolour_amd, flagging, device, kw, pname):
     legs["chain"] = leg
     # ---- ska
     nbl, ncorr, T, F, slabs = 32, 2, 512, 65536, 4
-    t_stream, t_res, flagged = ska_stream(torch, tricolour_amd, device, kw, nbl, ncorr, T, F, slabs, 1)
+    t_stream, t_res, flagged, _ = ska_stream(torch, tricolour_amd, device, kw, nbl, ncorr, T, F, slabs, 1)
     nvis = nbl * ncorr * T * F * slabs
     leg = dict(value=round(nvis / t_res / 1e6, 2), unit="Mvis/s", ms_per_step=round(t_res / slabs * 1e3, 3), steps=slabs, warmup=1,
                workload="SKA-Mid window geometry (BASELINE configs[4], the 1-GPU half): slabs of %d bl x %d corr x %d x %d, "
@@ -690,12 +711,17 @@ def main():
                     help="skip the short chain / ska legs of the default (slab, N = 1) run")
     ap.add_argument("--roofline-only", action="store_true",
                     help="run only the per-kernel roofline legs (what the rocprofv3 --pmc passes of profiles/ wrap)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the flags of the last timed step as DIR/<name>.npy (rank 0; "
+                         "float32, under 64 MB in all: larger outputs as a fixed seeded sample, see dump_outputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal without a GPU: every rank joins a gloo group, rank 0 prints the rank count")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1,
                     help="launcher rehearsal: this rank leaves with exit code 3 the way a failed scatter leg does, while its "
                          "peers wait in a collective -- the launcher must tear the group down and report a non-zero code")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -789,11 +815,15 @@ def main():
         scans = [synth_slab(torch, nbl, ncorr, T, F, device, 1234 + 17 * s + rank) for s in range(args.scans)]
         setup = chain_setup(nbl, F)
         strategies = chain_strategies(kw)
+        scan_outs = []          # --dump-outputs: the flags of every scan of the step, not only the last one
 
         def step():
             out = None
+            scan_outs.clear()
             for v, f in scans:
                 out = apply_strategies(strategies, f, v, **setup)
+                if args.dump_outputs is not None:
+                    scan_outs.append(out)
             return out
         nvis_step *= args.scans
         workload = ("multi-scan chain (BASELINE configs[3]): %d scans x (%d bl x %d corr x %d time x %d chan) per GPU, "
@@ -808,7 +838,7 @@ def main():
     out = None
     if wl == "ska":
         barrier()
-        t_stream, dt, flagged = ska_stream(torch, tricolour_amd, device, kw, nbl, ncorr, T, F, steps, warmup, args.ska_streams)
+        t_stream, dt, flagged, out = ska_stream(torch, tricolour_amd, device, kw, nbl, ncorr, T, F, steps, warmup, args.ska_streams)
         barrier()
         extra["pcie_inclusive"] = dict(value=round(nvis_step * steps * world / t_stream / 1e6, 2), unit="Mvis/s",
                                        what="same slabs streamed host->device->host through two pinned buffers, "
@@ -829,6 +859,9 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         flagged = float(out.float().mean().item()) if out is not None else float("nan")
+    if args.dump_outputs is not None and rank == 0:
+        outputs = [("flags_scan%d" % s, o) for s, o in enumerate(scan_outs)] if wl == "chain" else [("flags", out)]
+        dump_outputs(torch, args.dump_outputs, outputs)
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -879,7 +912,7 @@ def main():
     if wl == "slab":
         del vis, flags
     elif wl == "chain":
-        del scans
+        del scans, scan_outs
     out = None
     flagging.release_workspace()
     torch.cuda.empty_cache()
