@@ -162,6 +162,45 @@ int tri_unpack_data(const uint8_t *flag_windows,
                     uint8_t *out_flags, int any_corr, void *stream);
 
 /*
+ * The per-scan input steps of apps/tricolour/app.py:389-457 fused into one
+ * pass over the MS rows (row, chan, ncorr), complex64:
+ *   vis = data - model            (:389-395; model == NULL: vis = data)
+ *   flags = 0 if flag == NULL     (--ignore-flags, :403-410)
+ *   mode 0 (standard):    windows of wcorr = ncorr correlations, vis and flags
+ *                         per correlation
+ *   mode 1 (polarisation), 2 (total_power): windows of wcorr = 1 correlation,
+ *                         vis = polarised_intensity(vis, terms) as in
+ *                         tri_stokes_intensity mode 0 (same device arithmetic,
+ *                         same bits), flags = any over corr (:415-439)
+ * then the scatter of tri_pack_data (packing.py:243-278) into windows
+ * (bl, wcorr, time, chan): row_bl / row_time as there, rows with row_bl < 0
+ * skipped.  Term tables are HOST arrays as in tri_stokes_intensity (idx =
+ * (c1, c2, s1, s2), alpha = (re, im) per term): the non-I terms of
+ * stokes_corr_map for mode 1, all of them for mode 2; ignored in mode 0.
+ * Cells no row maps to keep their prior contents: initialise the windows
+ * with tri_fill_windows.
+ */
+int tri_pack_scan(const void *data_c64, const void *model_c64, const uint8_t *flag,
+                  const int32_t *row_bl, const int32_t *row_time,
+                  int64_t rows, int64_t nchan, int64_t ncorr,
+                  int64_t nbl, int64_t ntime, int mode,
+                  const int32_t *pol_idx, const double *pol_alpha, int64_t n_pol,
+                  void *vis_windows_c64, uint8_t *flag_windows, void *stream);
+
+/*
+ * Flags of the MS after a scan (apps/tricolour/app.py:475-480): gathers the
+ * (bl, wcorr, time, chan) flag windows back to MS row order as
+ *   out_flags[row, chan, :] = any(flag_windows[bl, :, time, chan])
+ * broadcast to all out_ncorr correlations (unpack_data, then
+ * sum(axis=corr) > 0 and broadcast_to(..., ncorr)).  wcorr is 1 (Stokes
+ * modes) or out_ncorr (standard); rows with row_bl < 0 are set to 0.
+ */
+int tri_unpack_scan(const uint8_t *flag_windows,
+                    const int32_t *row_bl, const int32_t *row_time,
+                    int64_t rows, int64_t nchan, int64_t wcorr, int64_t out_ncorr,
+                    int64_t nbl, int64_t ntime, uint8_t *out_flags, void *stream);
+
+/*
  * Replaces tricolour.stokes.polarised_intensity (stokes.py:157-209, mode 0)
  * and unpolarised_intensity (stokes.py:79-153, mode 1) on (row, chan, corr)
  * visibilities, n = row * chan samples:

@@ -1414,34 +1414,44 @@ struct StokesTerms {
     StokesTerm unpol[TRI_MAX_STOKES_TERMS];
 };
 
+// One sample's intensity.  load(c) returns correlation c as (re, im) in double; shared with the fused scan
+// pack (kernels_scan.hpp) so both produce the same bits.
+__device__ __forceinline__ double stokes_term_magnitude(const StokesTerm& t, double2 x1, double2 x2) {
+    // s * (re + i im) with s = (double)s + 0i, then the sum, then a * (...): numba's complex products
+    const double s1 = (double)t.s1, s2 = (double)t.s2;
+    const double p1r = s1 * x1.x - 0.0 * x1.y, p1i = s1 * x1.y + 0.0 * x1.x;
+    const double p2r = s2 * x2.x - 0.0 * x2.y, p2i = s2 * x2.y + 0.0 * x2.x;
+    const double sr = p1r + p2r, si = p1i + p2i;
+    const double vr = t.ar * sr - t.ai * si, vi = t.ar * si + t.ai * sr;
+    return hypot(vr, vi);
+}
+
+template <typename Load>
+__device__ __forceinline__ double stokes_intensity_sample(const StokesTerms& terms, int mode, Load load) {
+    double pol = 0.0;
+    for (int k = 0; k < terms.n_pol; k++) {
+        const double m = stokes_term_magnitude(terms.pol[k], load(terms.pol[k].c1), load(terms.pol[k].c2));
+        pol += m * m;
+    }
+    double res = sqrt(pol);
+    if (mode == 1) {
+        double unpol = 0.0;
+        for (int k = 0; k < terms.n_unpol; k++)
+            unpol += stokes_term_magnitude(terms.unpol[k], load(terms.unpol[k].c1), load(terms.unpol[k].c2));
+        res = unpol - res;
+    }
+    return res;
+}
+
 template <typename T>   // float (complex64) or double (complex128)
 __global__ void k_stokes_intensity(const T* __restrict__ vis, T* __restrict__ out, size_t n, int ncorr,
                                    StokesTerms terms, int mode) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const T* v = vis + i * (size_t)ncorr * 2;
-    auto magnitude = [&](const StokesTerm& t) {
-        // s * (re + i im) with s = (double)s + 0i, then the sum, then a * (...): numba's complex products
-        const double x1r = (double)v[2 * t.c1], x1i = (double)v[2 * t.c1 + 1];
-        const double x2r = (double)v[2 * t.c2], x2i = (double)v[2 * t.c2 + 1];
-        const double s1 = (double)t.s1, s2 = (double)t.s2;
-        const double p1r = s1 * x1r - 0.0 * x1i, p1i = s1 * x1i + 0.0 * x1r;
-        const double p2r = s2 * x2r - 0.0 * x2i, p2i = s2 * x2i + 0.0 * x2r;
-        const double sr = p1r + p2r, si = p1i + p2i;
-        const double vr = t.ar * sr - t.ai * si, vi = t.ar * si + t.ai * sr;
-        return hypot(vr, vi);
-    };
-    double pol = 0.0;
-    for (int k = 0; k < terms.n_pol; k++) {
-        const double m = magnitude(terms.pol[k]);
-        pol += m * m;
-    }
-    double res = sqrt(pol);
-    if (mode == 1) {
-        double unpol = 0.0;
-        for (int k = 0; k < terms.n_unpol; k++) unpol += magnitude(terms.unpol[k]);
-        res = unpol - res;
-    }
+    const double res = stokes_intensity_sample(terms, mode, [&](int c) {
+        return make_double2((double)v[2 * c], (double)v[2 * c + 1]);
+    });
     out[2 * i] = (T)res;
     out[2 * i + 1] = (T)0;
 }

@@ -10,6 +10,7 @@
 //   kernels_boxweight.hpp     K4w integer weight image of the time-axis stage (bit / byte / halfword-packed delay lines)
 //   kernels_boxexact.hpp      K4x exact row filter for any radius (LDS-resident line, checked exactness)
 //   kernels_sumthreshold.hpp  K7  fused SumThreshold
+//   kernels_scan.hpp          fused scan pack (residual, Stokes, scatter) and broadcast unpack
 #include <unordered_set>
 #include "tri_common.hpp"
 #include "kernels_elementwise.hpp"
@@ -22,6 +23,7 @@
 #include "kernels_boxweight.hpp"
 #include "kernels_boxexact.hpp"
 #include "kernels_sumthreshold.hpp"
+#include "kernels_scan.hpp"
 
 // ===========================================================================
 // host side
@@ -2142,6 +2144,112 @@ extern "C" int tri_unpack_data(const uint8_t* flag_windows, const int32_t* row_b
     return TRI_OK;
 }
 
+// host term tables (idx = (c1, c2, s1, s2), alpha = (re, im) per term) -> StokesTerm; false if a
+// correlation index is outside [0, ncorr)
+static bool fill_stokes_terms(StokesTerm* dst, const int32_t* idx, const double* alpha, int64_t cnt, int64_t ncorr) {
+    for (int64_t k = 0; k < cnt; k++) {
+        dst[k].c1 = idx[4 * k];
+        dst[k].c2 = idx[4 * k + 1];
+        dst[k].s1 = idx[4 * k + 2];
+        dst[k].s2 = idx[4 * k + 3];
+        dst[k].ar = alpha[2 * k];
+        dst[k].ai = alpha[2 * k + 1];
+        if (dst[k].c1 < 0 || dst[k].c1 >= ncorr || dst[k].c2 < 0 || dst[k].c2 >= ncorr) return false;
+    }
+    return true;
+}
+
+extern "C" int tri_pack_scan(const void* data_c64, const void* model_c64, const uint8_t* flag,
+                             const int32_t* row_bl, const int32_t* row_time, int64_t rows, int64_t nchan,
+                             int64_t ncorr, int64_t nbl, int64_t ntime, int mode, const int32_t* pol_idx,
+                             const double* pol_alpha, int64_t n_pol, void* vis_windows_c64,
+                             uint8_t* flag_windows, void* stream) {
+    if (!data_c64 || !row_bl || !row_time || !vis_windows_c64 || !flag_windows)
+        return set_err(TRI_EINVAL, "NULL pointer argument");
+    if (rows < 0 || nchan <= 0 || ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
+    if (mode < 0 || mode > 2) return set_err(TRI_EINVAL, "mode must be 0 (standard), 1 (polarisation) or 2 (total_power)");
+    StokesTerms terms;
+    terms.n_pol = 0;
+    terms.n_unpol = 0;
+    if (mode != 0) {
+        if (n_pol <= 0) return set_err(TRI_EINVAL, "modes 1 and 2 need at least one stokes term");
+        if (n_pol > TRI_MAX_STOKES_TERMS) return set_err(TRI_EUNSUPPORTED, "at most 4 stokes terms");
+        if (!pol_idx || !pol_alpha) return set_err(TRI_EINVAL, "NULL pointer argument");
+        terms.n_pol = (int)n_pol;
+        if (!fill_stokes_terms(terms.pol, pol_idx, pol_alpha, n_pol, ncorr))
+            return set_err(TRI_EINVAL, "correlation index out of range");
+    }
+    if (rows == 0) return TRI_OK;
+    if (rows > 0x7FFFFFFF || nchan > 0x7FFFFFFF || ncorr > 0x7FFFFFFF || nbl > 0x7FFFFFFF || ntime > 0x7FFFFFFF)
+        return set_err(TRI_EUNSUPPORTED, "dimension too large for one call");
+    const bool stokes = mode != 0;
+    // 1 / 2 / 4 correlations with 16-byte aligned rows: vector loads of a thread's (chan, corr) piece
+    const bool al = (uintptr_t)data_c64 % 16 == 0 && (uintptr_t)model_c64 % 16 == 0 && (uintptr_t)flag % 4 == 0;
+    const bool vec = al && (ncorr == 4 || ncorr == 2 || ncorr == 1);
+    dim3 grid((unsigned)cdiv(nchan, 256), 1, 1);
+    // gridDim.y is limited to 65535: walk the rows in slabs
+    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
+        const int64_t nr = std::min<int64_t>(65535, rows - r0);
+        grid.y = (unsigned)nr;
+        const size_t off = (size_t)r0 * nchan * ncorr;
+        const float2* d = (const float2*)data_c64 + off;
+        const float2* m = model_c64 ? (const float2*)model_c64 + off : nullptr;
+        const uint8_t* fl = flag ? flag + off : nullptr;
+        const int32_t* rb = row_bl + r0;
+        const int32_t* rt = row_time + r0;
+        hipStream_t st = (hipStream_t)stream;
+        float2* vw = (float2*)vis_windows_c64;
+#define TRI_PACK_SCAN_V(NC, S)                                                                                      \
+        do {                                                                                                         \
+            if (m && fl)  hipLaunchKernelGGL((k_pack_scan_v<NC, S, true, true>), grid, dim3(256), 0, st, d, m, fl,   \
+                                             rb, rt, (int)nchan, (int)nbl, (int)ntime, terms, vw, flag_windows);     \
+            else if (m)   hipLaunchKernelGGL((k_pack_scan_v<NC, S, true, false>), grid, dim3(256), 0, st, d, m, fl,  \
+                                             rb, rt, (int)nchan, (int)nbl, (int)ntime, terms, vw, flag_windows);     \
+            else if (fl)  hipLaunchKernelGGL((k_pack_scan_v<NC, S, false, true>), grid, dim3(256), 0, st, d, m, fl,  \
+                                             rb, rt, (int)nchan, (int)nbl, (int)ntime, terms, vw, flag_windows);     \
+            else          hipLaunchKernelGGL((k_pack_scan_v<NC, S, false, false>), grid, dim3(256), 0, st, d, m, fl, \
+                                             rb, rt, (int)nchan, (int)nbl, (int)ntime, terms, vw, flag_windows);     \
+        } while (0)
+        if (vec && ncorr == 4 && stokes) TRI_PACK_SCAN_V(4, true);
+        else if (vec && ncorr == 4) TRI_PACK_SCAN_V(4, false);
+        else if (vec && ncorr == 2 && stokes) TRI_PACK_SCAN_V(2, true);
+        else if (vec && ncorr == 2) TRI_PACK_SCAN_V(2, false);
+        else if (vec && ncorr == 1 && stokes) TRI_PACK_SCAN_V(1, true);
+        else if (vec && ncorr == 1) TRI_PACK_SCAN_V(1, false);
+        else
+            hipLaunchKernelGGL(k_pack_scan, grid, dim3(256), 0, st, d, m, fl, rb, rt, (int)nchan, (int)ncorr,
+                               (int)nbl, (int)ntime, stokes ? 1 : 0, terms, vw, flag_windows);
+#undef TRI_PACK_SCAN_V
+        LAUNCHCHK();
+    }
+    return TRI_OK;
+}
+
+extern "C" int tri_unpack_scan(const uint8_t* flag_windows, const int32_t* row_bl, const int32_t* row_time,
+                               int64_t rows, int64_t nchan, int64_t wcorr, int64_t out_ncorr, int64_t nbl,
+                               int64_t ntime, uint8_t* out_flags, void* stream) {
+    if (!flag_windows || !row_bl || !row_time || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
+    if (rows < 0 || nchan <= 0 || out_ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
+    if (wcorr != 1 && wcorr != out_ncorr) return set_err(TRI_EINVAL, "wcorr must be 1 or out_ncorr");
+    if (rows == 0) return TRI_OK;
+    if (rows > 0x7FFFFFFF || nchan > 0x7FFFFFFF || out_ncorr > 0x7FFFFFFF || nbl > 0x7FFFFFFF || ntime > 0x7FFFFFFF)
+        return set_err(TRI_EUNSUPPORTED, "dimension too large for one call");
+    dim3 grid((unsigned)cdiv(nchan, 256), 1, 1);
+    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
+        const int64_t nr = std::min<int64_t>(65535, rows - r0);
+        grid.y = (unsigned)nr;
+        uint8_t* osl = out_flags + (size_t)r0 * nchan * out_ncorr;
+        if (out_ncorr == 4 && (uintptr_t)out_flags % 4 == 0)
+            hipLaunchKernelGGL(k_unpack_scan<4>, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0,
+                               row_time + r0, (int)nchan, (int)wcorr, 4, (int)nbl, (int)ntime, osl);
+        else
+            hipLaunchKernelGGL(k_unpack_scan<0>, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0,
+                               row_time + r0, (int)nchan, (int)wcorr, (int)out_ncorr, (int)nbl, (int)ntime, osl);
+        LAUNCHCHK();
+    }
+    return TRI_OK;
+}
+
 // Measurement / test hook: ONE rejection step of the background loop (flagging.py:553-574) as the flagger runs it for blocks
 // of >= 65536 samples: k_mr_predict, two rounds of k_mr_pass + k_mr_finish, the redo kernel (K3t).  resid: (n_win, n_chan, n_time)
 // float32 = |data - background| in the FT layout, flags_in: (n_win, n_chan, n_time) bytes; flags_out (FT bytes), flags_t4 (TF4 words,
@@ -2650,19 +2758,8 @@ extern "C" int tri_stokes_intensity(const void* vis, int vis_dtype, int64_t n, i
     StokesTerms terms;
     terms.n_pol = (int)n_pol;
     terms.n_unpol = (int)n_unpol;
-    auto fill = [&](StokesTerm* dst, const int32_t* idx, const double* alpha, int64_t cnt) -> bool {
-        for (int64_t k = 0; k < cnt; k++) {
-            dst[k].c1 = idx[4 * k];
-            dst[k].c2 = idx[4 * k + 1];
-            dst[k].s1 = idx[4 * k + 2];
-            dst[k].s2 = idx[4 * k + 3];
-            dst[k].ar = alpha[2 * k];
-            dst[k].ai = alpha[2 * k + 1];
-            if (dst[k].c1 < 0 || dst[k].c1 >= ncorr || dst[k].c2 < 0 || dst[k].c2 >= ncorr) return false;
-        }
-        return true;
-    };
-    if (!fill(terms.pol, pol_idx, pol_alpha, n_pol) || !fill(terms.unpol, unpol_idx, unpol_alpha, n_unpol))
+    if (!fill_stokes_terms(terms.pol, pol_idx, pol_alpha, n_pol, ncorr) ||
+        !fill_stokes_terms(terms.unpol, unpol_idx, unpol_alpha, n_unpol, ncorr))
         return set_err(TRI_EINVAL, "correlation index out of range");
     if (n == 0) return TRI_OK;
     if (!vis || !out) return set_err(TRI_EINVAL, "NULL pointer argument");

@@ -132,3 +132,87 @@ def unpack_data(antenna1, antenna2, time_inv, ubl, flag_windows, equalize_corr=F
     _lib.check(lib.tri_unpack_data(fw8.data_ptr(), rb.data_ptr(), rt.data_ptr(), rows, nchan,
                                    ncorr, nbl, ntime, out.data_ptr(), 1 if equalize_corr else 0, stream))
     return out.view(torch.bool)
+
+
+SCAN_MODES = {"standard": 0, "polarisation": 1, "total_power": 2}
+
+
+def pack_scan(time_inv, ubl, antenna1, antenna2, data, flags, ntime, model=None,
+              flagging_strategy="standard", stokes_terms=()):
+    """The input side of one scan (apps/tricolour/app.py:389-457) in one pass
+    over the MS rows (``tri_pack_scan``): ``vis = data - model`` (``model``
+    None: ``data``), the polarised intensity of ``stokes_terms`` (the
+    ``(c1, c2, a, s1, s2)`` tuples of :func:`tricolour_amd.stokes.stokes_corr_map`)
+    and any-over-corr flags in the ``polarisation`` / ``total_power`` modes,
+    then the scatter of :func:`pack_data`.  ``flags`` None: all unflagged
+    (``--ignore-flags``).  Returns ``(vis_windows, flag_windows)`` of shape
+    (bl, wcorr, time, chan), wcorr = ncorr in ``standard`` mode and 1
+    otherwise; data and model are taken as complex64, as :func:`pack_data`
+    does."""
+    from tricolour_amd.stokes import _term_tables
+    if flagging_strategy not in SCAN_MODES:
+        raise ValueError("Invalid flagging strategy '%s'" % flagging_strategy)
+    mode = SCAN_MODES[flagging_strategy]
+    if len(tuple(data.shape)) != 3:
+        raise ValueError("data must have shape (row, chan, corr)")
+    rows, nchan, ncorr = (int(s) for s in data.shape)
+    if flags is not None and tuple(flags.shape) != tuple(data.shape):
+        raise ValueError("flags shape %s != data shape %s" % (tuple(flags.shape), tuple(data.shape)))
+    if model is not None and tuple(model.shape) != tuple(data.shape):
+        raise ValueError("model shape %s != data shape %s" % (tuple(model.shape), tuple(data.shape)))
+    if mode != 0 and len(tuple(stokes_terms)) == 0:
+        raise ValueError("flagging strategy '%s' needs stokes terms" % flagging_strategy)
+    torch = _torch_gpu()
+    lib = _lib.lib()
+    ubl = np.asarray(ubl)
+    nbl = int(ubl.shape[0])
+    ntime = int(ntime)
+    _, row_bl, row_time = row_map(np.asarray(antenna1), np.asarray(antenna2), ubl,
+                                  np.asarray(time_inv), ntime)
+    d = _dev(torch, data, torch.complex64)
+    m = None if model is None else _dev(torch, model, torch.complex64)
+    f8 = None
+    if flags is not None:
+        f = _dev(torch, flags)
+        f8 = f.view(torch.uint8) if f.dtype == torch.bool else (f != 0).view(torch.uint8)
+    rb, rt = _dev(torch, row_bl), _dev(torch, row_time)
+    wcorr = ncorr if mode == 0 else 1
+    vis_w = torch.empty((nbl, wcorr, ntime, nchan), dtype=torch.complex64, device=d.device)
+    flag_w = torch.empty((nbl, wcorr, ntime, nchan), dtype=torch.uint8, device=d.device)
+    pidx, palpha, npol = _term_tables(stokes_terms if mode != 0 else ())
+    stream = torch.cuda.current_stream(d.device).cuda_stream
+    _lib.check(lib.tri_fill_windows(vis_w.data_ptr(), flag_w.data_ptr(), vis_w.numel(), stream))
+    _lib.check(lib.tri_pack_scan(d.data_ptr(), None if m is None else m.data_ptr(),
+                                 None if f8 is None else f8.data_ptr(), rb.data_ptr(), rt.data_ptr(),
+                                 rows, nchan, ncorr, nbl, ntime, mode,
+                                 pidx.ctypes.data, palpha.ctypes.data, npol,
+                                 vis_w.data_ptr(), flag_w.data_ptr(), stream))
+    return vis_w, flag_w.view(torch.bool)
+
+
+def unpack_scan(antenna1, antenna2, time_inv, ubl, flag_windows, ncorr):
+    """The MS flags of a scan (apps/tricolour/app.py:475-480) from its
+    (bl, wcorr, time, chan) flag windows (``tri_unpack_scan``): any over the
+    window correlations, broadcast to ``ncorr`` correlations, as a
+    (row, chan, ncorr) bool tensor; rows whose baseline is not in ``ubl``
+    stay 0.  ``wcorr`` must be 1 or ``ncorr``."""
+    torch = _torch_gpu()
+    lib = _lib.lib()
+    ubl = np.asarray(ubl)
+    nbl, wcorr, ntime, nchan = (int(s) for s in flag_windows.shape)
+    ncorr = int(ncorr)
+    if nbl != int(ubl.shape[0]):
+        raise ValueError("flag_windows and ubl disagree on the number of baselines")
+    if wcorr not in (1, ncorr):
+        raise ValueError("flag windows have %d correlations: need 1 or %d" % (wcorr, ncorr))
+    row_bl, _, row_time = row_map(np.asarray(antenna1), np.asarray(antenna2), ubl,
+                                  np.asarray(time_inv), ntime)
+    rows = len(row_bl)
+    fw = _dev(torch, flag_windows)
+    fw8 = fw.view(torch.uint8) if fw.dtype == torch.bool else (fw != 0).view(torch.uint8)
+    rb, rt = _dev(torch, row_bl), _dev(torch, row_time)
+    out = torch.empty((rows, nchan, ncorr), dtype=torch.uint8, device=fw.device)
+    stream = torch.cuda.current_stream(fw.device).cuda_stream
+    _lib.check(lib.tri_unpack_scan(fw8.data_ptr(), rb.data_ptr(), rt.data_ptr(), rows, nchan, wcorr,
+                                   ncorr, nbl, ntime, out.data_ptr(), stream))
+    return out.view(torch.bool)

@@ -1,0 +1,305 @@
+"""Whole-scan flagging: the per-(field, ddid, scan) pipeline of the tricolour
+application (``tricolour/apps/tricolour/app.py:370-486``) as one
+device-resident call, plus the host pieces around it -- static masks
+(``tricolour/mask.py:24-90``), strategy YAML and field / scan selection
+(``app.py:327-368``).
+
+:func:`flag_scan` runs residual, Stokes intensity, any-over-corr flags and
+the window scatter in one kernel (``tri_pack_scan``), the window statistics,
+the strategy chain of :mod:`tricolour_amd.strategies`, and the unpack with the
+application's broadcast to the MS's correlations (``tri_unpack_scan``).  No
+Measurement Set I/O: callers hand in columns already loaded.
+"""
+import logging
+import re
+
+import numpy as np
+
+from tricolour_amd import packing
+from tricolour_amd.stokes import STOKES_TYPES, stokes_corr_map
+
+log = logging.getLogger(__name__)
+
+VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with_input_flags", "unflag",
+               "flag_nans_zeros", "apply_static_mask")          # strat_executor.py:36-83
+
+
+# ---------------------------------------------------------------------------
+# static masks (mask.py:24-90)
+# ---------------------------------------------------------------------------
+def dilate_mask(mask_chans, mask_flags, dilate):
+    """``mask_flags`` dilated by ``dilate`` channels, or by a width in
+    ``Hz`` / ``kHz`` / ``MHz`` / ``GHz`` (``int(width / channel width) + 1``
+    channels), as ``mask.dilate_mask`` does it with scipy's
+    ``binary_dilation`` by ``[1, 1, 1]``: ``n`` iterations OR a +-n box with
+    nothing beyond the band ends; ``n < 1`` repeats until nothing changes,
+    i.e. the whole band if any channel is masked."""
+    try:
+        dilate_width = int(dilate)
+    except ValueError:
+        value, units = re.match(r"([\d.]+)([a-zA-Z]+)", dilate, re.I).groups()
+        scale = {"GHz": 1e9, "MHz": 1e6, "kHz": 1e3, "Hz": 1.0}
+        if units not in scale:
+            raise ValueError('Unrecognised units for --dilate value::  %s' % units)
+        value = float(value) * scale[units]
+        chan_width = mask_chans[1] - mask_chans[0]
+        dilate_width = int(value / chan_width) + 1
+    flags = np.asarray(mask_flags, bool)
+    if dilate_width < 1:
+        return np.full(flags.shape, bool(flags.any()))
+    n = min(dilate_width, flags.size)
+    counts = np.concatenate([[0], np.cumsum(np.concatenate([np.zeros(n, np.int64), flags,
+                                                            np.zeros(n, np.int64)]))])
+    return (counts[2 * n + 1:] - counts[:-(2 * n + 1)]) > 0
+
+
+def load_mask(filename, dilate):
+    """Masked channel frequencies of a ``.staticmask`` file: a structured
+    ``.npy`` array of dtype ``(bool, float64)`` whose row 0 holds the mask and
+    row 1 the channel frequencies (mask.py:61-90).  Returns the ``(n, 1)``
+    frequencies of the masked (after ``dilate``, if given) channels."""
+    mask = np.load(filename)
+    if mask.dtype[0] != bool or mask.dtype[1] != np.float64:
+        raise ValueError("Mask %s is not a valid static mask "
+                         "with labelled channel axis "
+                         "[dtype == (bool, float64)]" % filename)
+    mask_chans = mask["chans"][1]
+    mask_flags = mask["mask"][0]
+    if dilate:
+        mask_flags = dilate_mask(mask_chans, mask_flags, dilate)
+    masked_channels = mask_chans[np.argwhere(mask_flags)]
+    log.info("Loaded mask {0:s} {1:s} with {2:.2f}% "
+             "flagged bandwidth between {3:.3f} "
+             "and {4:.3f} GHz".format(str(filename), "(dilated)" if dilate else "(non-dilated)",
+                                      100.0 * masked_channels.size / mask_chans.size,
+                                      np.min(mask_chans) / 1.0e9, np.max(mask_chans) / 1.0e9))
+    return masked_channels
+
+
+# ---------------------------------------------------------------------------
+# configuration and selection
+# ---------------------------------------------------------------------------
+def load_strategies(path):
+    """The ``strategies:`` list of a tricolour configuration YAML
+    (``conf/default.yaml`` layout)."""
+    import yaml
+    with open(path) as fh:
+        doc = yaml.safe_load(fh)
+    if not isinstance(doc, dict) or not isinstance(doc.get("strategies"), list):
+        raise ValueError("%s has no 'strategies' list" % path)
+    return doc["strategies"]
+
+
+def check_strategies(strategies):
+    """Raises the reference's errors for a strategy without a task or with an
+    unknown one (strat_executor.py:33-36, 82-83) before any work is done."""
+    for strategy in strategies:
+        try:
+            task = strategy['task']
+        except KeyError:
+            raise ValueError("strategy has no 'task': %s" % strategy)
+        if task not in VALID_TASKS:
+            raise ValueError("Task '%s' does not name a valid task", task)
+
+
+def select_scans(scan_numbers, available):
+    """Scans to flag (app.py:327-329): those of ``scan_numbers`` that exist,
+    all of ``available`` when ``scan_numbers`` is None."""
+    return list(set(available).intersection(scan_numbers if scan_numbers is not None else available))
+
+
+def select_fields(field_names, fieldnames, ms_name=""):
+    """``{field id: field name}`` to flag (app.py:335-368).  ``field_names``:
+    user entries, each a name, a field index or a comma list of them;
+    empty / None selects every field of ``fieldnames`` (the FIELD table's
+    names).  Unknown names raise ``ValueError``."""
+    fieldnames = list(fieldnames)
+    if not field_names:
+        return {i: fn for i, fn in enumerate(fieldnames)}
+    flatten_field_names = []
+    for f in field_names:
+        flatten_field_names += [x.strip() for x in str(f).split(",")]
+    for f in flatten_field_names:
+        if re.match(r"^\d+$", f) and int(f) < len(fieldnames):
+            flatten_field_names.append(fieldnames[int(f)])
+    flatten_field_names = list(set(filter(lambda x: not re.match(r"^\d+$", x), flatten_field_names)))
+    log.info("Only considering fields '{0:s}' for flagging per user "
+             "selection criterion.".format(", ".join(flatten_field_names)))
+    if not set(flatten_field_names) <= set(fieldnames):
+        raise ValueError("One or more fields cannot be "
+                         "found in dataset '{0:s}' "
+                         "You specified {1:s}, but "
+                         "only {2:s} are available".format(ms_name, ",".join(flatten_field_names),
+                                                           ",".join(fieldnames)))
+    return {fieldnames.index(fn): fn for fn in flatten_field_names}
+
+
+# ---------------------------------------------------------------------------
+# one scan
+# ---------------------------------------------------------------------------
+def _host(a, dtype=None):
+    import torch
+    if torch.is_tensor(a):
+        a = a.cpu().numpy()
+    a = np.asarray(a)
+    return a.astype(dtype) if dtype is not None else a
+
+
+def _stokes_terms(flagging_strategy, corr_type):
+    if flagging_strategy == "standard":
+        return ()
+    if corr_type is None:
+        raise ValueError("flagging strategy '%s' needs corr_type (the CORR_TYPE of the "
+                         "polarisation table)" % flagging_strategy)
+    codes = [STOKES_TYPES[c] if isinstance(c, str) else int(c) for c in _host(corr_type).tolist()]
+    stokes_map = stokes_corr_map(codes)
+    terms = tuple(v for k, v in stokes_map.items() if flagging_strategy == "total_power" or k != "I")
+    if not terms:
+        raise ValueError("correlations %s form no Stokes parameter for flagging strategy '%s'"
+                         % (codes, flagging_strategy))
+    return terms
+
+
+def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, strategies, *, model=None,
+              flagging_strategy="standard", corr_type=None, ignore_flags=False, antenna_positions=None,
+              masked_channels=(), antenna_names=None, scan_no=0, field_name="", ddid=0):
+    """Flags one (field, ddid, scan) dataset as the tricolour application does
+    (app.py:370-486).
+
+    ``data`` / ``model`` / ``flags``: (row, chan, corr) columns (numpy or ROCm
+    tensors); ``antenna1`` / ``antenna2`` / ``time``: per-row columns;
+    ``chan_freq`` / ``chan_width``: the spectral window's channels;
+    ``strategies``: the YAML's list of strategy dicts; ``flagging_strategy``:
+    ``standard``, ``polarisation`` or ``total_power`` (the last two need
+    ``corr_type``, casacore codes or names in dataset order);
+    ``masked_channels``: a list of :func:`load_mask` results.
+
+    Returns ``(row_flags, original_stats, final_stats)``: (row, chan, corr)
+    bool flags, every correlation of a visibility flagged if any window
+    correlation is (a numpy array for numpy ``data``, a device tensor
+    otherwise), and the :class:`~tricolour_amd.window_statistics.WindowStatistics`
+    of the packed flags before and after the strategies."""
+    import torch
+    from tricolour_amd.strategies import apply_strategies
+    from tricolour_amd.window_statistics import window_stats_block
+
+    if flagging_strategy not in packing.SCAN_MODES:
+        raise ValueError("Invalid flagging strategy '%s'" % flagging_strategy)
+    strategies = list(strategies)
+    check_strategies(strategies)
+    if len(tuple(data.shape)) != 3:
+        raise ValueError("data must have shape (row, chan, corr), got %s" % (tuple(data.shape),))
+    nrow, nchan, ncorr = (int(s) for s in data.shape)
+    if not ignore_flags and flags is None:
+        raise ValueError("flags are required unless ignore_flags is set")
+    if flags is not None and tuple(flags.shape) != (nrow, nchan, ncorr):
+        raise ValueError("flags shape %s != data shape %s" % (tuple(flags.shape), (nrow, nchan, ncorr)))
+    if model is not None and tuple(model.shape) != (nrow, nchan, ncorr):
+        raise ValueError("model shape %s != data shape %s" % (tuple(model.shape), (nrow, nchan, ncorr)))
+    a1 = _host(antenna1, np.int32)
+    a2 = _host(antenna2, np.int32)
+    tm = _host(time)
+    if not (a1.shape == a2.shape == tm.shape == (nrow,)):
+        raise ValueError("antenna1 %s, antenna2 %s and time %s must have one entry per row (%d)"
+                         % (a1.shape, a2.shape, tm.shape, nrow))
+    chan_freq = _host(chan_freq, np.float64)
+    chan_width = _host(chan_width, np.float64)
+    if chan_freq.shape != (nchan,) or chan_width.shape != (nchan,):
+        raise ValueError("chan_freq %s and chan_width %s must have one entry per channel (%d)"
+                         % (chan_freq.shape, chan_width.shape, nchan))
+    terms = _stokes_terms(flagging_strategy, corr_type)
+
+    if ignore_flags:                                                           # app.py:403-410
+        log.critical("Completely ignoring measurement set flags as per '-if' request. "
+                     "Strategy WILL NOT or with original flags, even if specified!")
+    if flagging_strategy == "total_power" and model is None:                  # :424-429
+        log.critical("You requested to flag total quadrature power, but not on residuals. "
+                     "This is not advisable and the flagger may mistake fringes of "
+                     "off-axis sources for broadband RFI.")
+    elif flagging_strategy == "standard" and model is None:                   # :434-439
+        log.critical("You requested to flag per correlation, but not on residuals. "
+                     "This is not advisable and the flagger may mistake fringes of off-axis sources "
+                     "for broadband RFI.")
+
+    from_numpy = not torch.is_tensor(data)
+    ubl = packing.unique_baselines(a1, a2)                                     # :441-450
+    utime, time_inv = np.unique(tm, return_inverse=True)
+    time_inv = time_inv.reshape(-1).astype(np.int32)
+    ntime = int(utime.shape[0])
+    if antenna_names is None:
+        nant = len(antenna_positions) if antenna_positions is not None else int(max(a1.max(initial=-1),
+                                                                                    a2.max(initial=-1))) + 1
+        antenna_names = [str(i) for i in range(nant)]
+    antenna_names = [str(n) for n in _host(antenna_names).tolist()]
+
+    vis_w, flag_w = packing.pack_scan(time_inv, ubl, a1, a2, data, None if ignore_flags else flags, ntime,
+                                      model=model, flagging_strategy=flagging_strategy, stokes_terms=terms)
+    original = window_stats_block(flag_w, ubl, chan_freq, antenna_names, scan_no, field_name, ddid)
+    flag_w = apply_strategies(strategies, flag_w, vis_w, ubl=ubl,
+                              ant_pos=None if antenna_positions is None else _host(antenna_positions),
+                              chan_freq=chan_freq, chan_width=chan_width, masked_channels=list(masked_channels))
+    final = window_stats_block(flag_w, ubl, chan_freq, antenna_names, scan_no, field_name, ddid)
+    row_flags = packing.unpack_scan(a1, a2, time_inv, ubl, flag_w, ncorr)     # :475-480
+    if from_numpy:
+        row_flags = row_flags.cpu().numpy()
+    return row_flags, original, final
+
+
+# ---------------------------------------------------------------------------
+# every scan
+# ---------------------------------------------------------------------------
+def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fieldnames=None, ms_name="",
+               flagging_strategy="standard", ignore_flags=False, antenna_positions=None, masked_channels=(),
+               antenna_names=None):
+    """The dataset loop of the application (app.py:327-486) over datasets
+    already loaded, one dict per (field, ddid, scan) with the keys
+    ``DATA``, ``FLAG``, ``ANTENNA1``, ``ANTENNA2``, ``TIME``, ``FIELD_ID``,
+    ``DATA_DESC_ID``, ``SCAN_NUMBER``, ``CHAN_FREQ``, ``CHAN_WIDTH``,
+    ``CORR_TYPE`` (Stokes modes) and, to flag residuals, ``MODEL``.
+    ``fieldnames``: names of the FIELD table (default ``"0"``, ``"1"``, ...).
+
+    Returns ``(row_flags, summary)``: a list with the row flags of each
+    dataset (None for datasets the field / scan selection skips) and the
+    lines of ``summarise_stats`` over all flagged datasets (an empty list if
+    none was flagged)."""
+    from tricolour_amd.window_statistics import summarise_stats
+
+    datasets = list(datasets)
+    strategies = list(strategies)
+    check_strategies(strategies)
+    if fieldnames is None:
+        nfield = max([int(ds["FIELD_ID"]) for ds in datasets], default=-1) + 1
+        fieldnames = [str(i) for i in range(nfield)]
+    scans = select_scans(scan_numbers, [int(ds["SCAN_NUMBER"]) for ds in datasets])
+    if scans != []:
+        log.info("Only considering scans '{0:s}' as per user selection criterion"
+                 .format(", ".join(map(str, map(int, scans)))))
+    field_dict = select_fields(field_names, fieldnames, ms_name)
+
+    out, original_stats, final_stats = [], [], []
+    for ds in datasets:
+        field_id, scan_no = int(ds["FIELD_ID"]), int(ds["SCAN_NUMBER"])
+        if field_id not in field_dict or scan_no not in scans:
+            out.append(None)
+            continue
+        log.info("Flagging field '{0:s}' scan {1:d}".format(field_dict[field_id], scan_no))
+        row_flags, original, final = flag_scan(
+            ds["DATA"], ds.get("FLAG"), ds["ANTENNA1"], ds["ANTENNA2"], ds["TIME"], ds["CHAN_FREQ"],
+            ds["CHAN_WIDTH"], strategies, model=ds.get("MODEL"), flagging_strategy=flagging_strategy,
+            corr_type=ds.get("CORR_TYPE"), ignore_flags=ignore_flags, antenna_positions=antenna_positions,
+            masked_channels=masked_channels, antenna_names=antenna_names, scan_no=scan_no,
+            field_name=field_dict[field_id], ddid=int(ds["DATA_DESC_ID"]))
+        out.append(row_flags)
+        original_stats.append(original)
+        final_stats.append(final)
+    if not final_stats:
+        return out, []
+    return out, summarise_stats(_combine(final_stats), _combine(original_stats))
+
+
+def _combine(stats):
+    """combine_window_stats (window_statistics.py:143-168) of computed tallies."""
+    total = stats[0].copy()
+    for one in stats[1:]:
+        total.update(one)
+    return total
