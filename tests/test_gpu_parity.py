@@ -289,6 +289,42 @@ def test_exact_row_filter_vs_oracle(gpu, oracle, shape, radius):
     assert passes == 4 * 2 * w * t and 0 < seq <= 4 * 2 * w * 6, (passes, seq)
 
 
+def test_failed_boxfilter_hook_leaves_the_flagger_routes(gpu):
+    """tri_bench_boxfilter switches the box-filter routes of its thread for its own launches; a call refused after the
+    switch (stage 1, variant 4 on lines of n_col % 4 != 0: no exact row filter) must leave the flagger's routes as they
+    were: the same kernels (K4q / K4w on the time axis at r = 30) and the same flags before and after it."""
+    import ctypes as C
+    import torch
+    from tricolour_amd import _lib
+    rs = np.random.RandomState(5)
+    shape = (1, 1, 64, 128)
+    vis = (rs.standard_normal(shape) + 1j * rs.standard_normal(shape)).astype(np.complex64)
+    vis[..., 40] *= 8.0
+    vis_d, flags_d = torch.from_numpy(vis).cuda(), torch.zeros(shape, dtype=torch.bool, device="cuda")
+    kw = dict(num_major_iterations=1, spike_width_time=35.0)      # time-axis radius 30: 2r = 60
+
+    def flag_once():
+        _lib.kernel_log_begin()
+        out = gpu.sum_threshold_flagger(vis_d, flags_d, **kw)
+        torch.cuda.synchronize()
+        return _lib.kernel_log_end(), out.cpu().numpy()
+
+    log0, out0 = flag_once()
+    assert any(k.startswith("k_boxq") for k in log0) and any(k.startswith("k_boxw") for k in log0), log0
+    w, t, f = 1, 8, 130
+    d = torch.zeros((w, f, t), dtype=torch.float32, device="cuda")
+    both = torch.zeros((w, 2, t, f), dtype=torch.float32, device="cuda")
+    ow = torch.zeros((w, f, t), dtype=torch.float32, device="cuda")
+    oo = torch.zeros((w, f, t), dtype=torch.float32, device="cuda")
+    ms = C.c_float(0)
+    rc = _lib.lib().tri_bench_boxfilter(d.data_ptr(), both.data_ptr(), ow.data_ptr(), oo.data_ptr(), w, t, f, 60,
+                                        1, 4, 1, C.byref(ms), None)
+    assert rc == _lib.TRI_EUNSUPPORTED, rc
+    log1, out1 = flag_once()
+    assert log1 == log0
+    assert np.array_equal(out1, out0)
+
+
 def test_exact_row_filter_random_stress(gpu, oracle):
     """Seeded sweep over line lengths, radii and dynamic ranges that straddle the exactness boundary of K4x (2^28 between a
     window's total and its smallest term): whichever lines and passes take the sequential redo, the result must equal the

@@ -227,7 +227,7 @@ k_mr_pass(const float* __restrict__ resid, const uint8_t* __restrict__ flags_in,
     }
     const MrtLayout lay{gscratch + win * scratch_ws, G, ccap, ucap};
     MrtPar* par = lay.par(g);
-    // (the status word may be cleared by another tile of the block at any time: ONE thread reads it for the workgroup)
+    // (ONE thread reads the status word for the workgroup)
     __shared__ unsigned sh_status;
     if (tid == 0) sh_status = __hip_atomic_load(&par->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
@@ -256,7 +256,6 @@ k_mr_pass(const float* __restrict__ resid, const uint8_t* __restrict__ flags_in,
     __syncthreads();
     unsigned mb1 = 0;
     unsigned ccnt = 0, ucnt = 0;                                       // this wave's list fill (uniform)
-    bool over = false;
 #pragma unroll
     for (int q = 0; q < 16; q++) {
         const int l = l0 + ty + 4 * q;
@@ -315,7 +314,7 @@ k_mr_pass(const float* __restrict__ resid, const uint8_t* __restrict__ flags_in,
         __builtin_amdgcn_raw_buffer_store_b32(fn, fors, (int)(valid ? i * 4u : OOBR), 0, 0);
         tile[ty + 4 * q][tx] = fn;
     }
-    over = false;                                                       // (a full wave list spills to the block's list: nothing fails here)
+    // (a full wave list spilled to the block's list above: nothing fails here)
     ccnt = min(ccnt, (unsigned)MRT_WCAND);                              // what is left in LDS
     ucnt = min(ucnt, (unsigned)MRT_WUND);
     mb1 = wave_max_u32(mb1);
@@ -323,9 +322,8 @@ k_mr_pass(const float* __restrict__ resid, const uint8_t* __restrict__ flags_in,
     unsigned cbase = 0, ubase = 0;
     if (lane == 0) {
         if (mb1) atomicMax(&par->below1, mb1);
-        if (over) { atomicExch(&par->status, 0u); par->pad[1] = 2 + (ccnt > MRT_WCAND ? 0 : 8); }   // a wave's list overflowed: the block is redone
-        if (ccnt && !over) cbase = atomicAdd(&par->ncand, ccnt);
-        if (ucnt && !over) ubase = atomicAdd(&par->nund, ucnt);
+        if (ccnt) cbase = atomicAdd(&par->ncand, ccnt);
+        if (ucnt) ubase = atomicAdd(&par->nund, ucnt);
     }
     cbase = (unsigned)__builtin_amdgcn_readfirstlane((int)cbase);
     ubase = (unsigned)__builtin_amdgcn_readfirstlane((int)ubase);
@@ -344,14 +342,12 @@ k_mr_pass(const float* __restrict__ resid, const uint8_t* __restrict__ flags_in,
             if (h) atomicAdd(&ghist[u * 256 + tid], h);
         }
     }
-    if (!over) {
-        unsigned* gc = lay.cand(g);
-        uint2* gu = reinterpret_cast<uint2*>(lay.und(g));
-        for (unsigned j = lane; j < ccnt; j += 64)
-            if ((size_t)cbase + j < ccap) gc[cbase + j] = lcand[wave][j];
-        for (unsigned j = lane; j < ucnt; j += 64)
-            if ((size_t)ubase + j < ucap) gu[ubase + j] = lund[wave][j];
-    }
+    unsigned* gc = lay.cand(g);
+    uint2* gu = reinterpret_cast<uint2*>(lay.und(g));
+    for (unsigned j = lane; j < ccnt; j += 64)
+        if ((size_t)cbase + j < ccap) gc[cbase + j] = lcand[wave][j];
+    for (unsigned j = lane; j < ucnt; j += 64)
+        if ((size_t)ubase + j < ucap) gu[ubase + j] = lund[wave][j];
 }
 
 // ---- finish: one workgroup per block ------------------------------------------------------------------------------------

@@ -63,6 +63,53 @@ static int set_err(int code, const char* fmt, ...) {
     } while (0)
 
 // ---------------------------------------------------------------------------
+// scoped ownership for the measurement / test hooks (the flagger itself allocates nothing): every early return
+// through HIPCHK / LAUNCHCHK / set_err releases what the hook made and restores what it switched.
+// ---------------------------------------------------------------------------
+// device buffer of `count` T: HIPCHK(buf.alloc(count)); freed on scope exit
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    hipError_t alloc(size_t count) { return hipMalloc(&p_, count * sizeof(T)); }
+    T* get() const { return p_; }
+};
+
+// stream / event handle: HIPCHK(hipEventCreate(ev.out())); destroyed on scope exit unless release()d
+template <class H, hipError_t (*Destroy)(H)>
+class HipHandle {
+    H h_ = nullptr;
+public:
+    HipHandle() = default;
+    HipHandle(const HipHandle&) = delete;
+    HipHandle& operator=(const HipHandle&) = delete;
+    HipHandle(HipHandle&& o) noexcept : h_(o.release()) {}
+    ~HipHandle() { if (h_) (void)Destroy(h_); }
+    H* out() { return &h_; }
+    H get() const { return h_; }
+    H release() { H h = h_; h_ = nullptr; return h; }
+};
+using HipEvent = HipHandle<hipEvent_t, hipEventDestroy>;
+using HipStream = HipHandle<hipStream_t, hipStreamDestroy>;
+
+// sets a (thread-local) switch for the rest of the scope and restores its previous value on exit
+template <class T>
+class ScopedSet {
+    T& ref_;
+    const T saved_;
+public:
+    ScopedSet(T& ref, T value) : ref_(ref), saved_(ref) { ref_ = value; }
+    ScopedSet(const ScopedSet&) = delete;
+    ScopedSet& operator=(const ScopedSet&) = delete;
+    ~ScopedSet() { ref_ = saved_; }
+};
+
+// ---------------------------------------------------------------------------
 // Kernel log (measurement hook, off by default): every launch of this translation unit goes through the macro
 // below, which counts launches per kernel symbol while the calling thread has the log switched on
 // (tri_kernel_log()).  bench.py uses it to name the device kernels a roofline leg timed and to count the launches

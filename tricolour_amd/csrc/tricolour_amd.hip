@@ -1970,11 +1970,19 @@ int get_substreams(SubStreams** out) {
         if (g_sub.device >= 0) return set_err(TRI_EUNSUPPORTED, "a calling thread must stay on one device");
         int lo = 0, hi = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));    // lo = least, hi = greatest priority (numerically lower)
-        HIPCHK(hipStreamCreateWithPriority(&g_sub.st[0], hipStreamNonBlocking, hi));
-        HIPCHK(hipStreamCreateWithPriority(&g_sub.st[1], hipStreamNonBlocking, lo));
-        HIPCHK(hipEventCreateWithFlags(&g_sub.fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&g_sub.join[0], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&g_sub.join[1], hipEventDisableTiming));
+        // (made in owning locals and kept only once all five exist: a failed create leaks nothing)
+        HipStream st0, st1;
+        HipEvent fork, join0, join1;
+        HIPCHK(hipStreamCreateWithPriority(st0.out(), hipStreamNonBlocking, hi));
+        HIPCHK(hipStreamCreateWithPriority(st1.out(), hipStreamNonBlocking, lo));
+        HIPCHK(hipEventCreateWithFlags(fork.out(), hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(join0.out(), hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(join1.out(), hipEventDisableTiming));
+        g_sub.st[0] = st0.release();
+        g_sub.st[1] = st1.release();
+        g_sub.fork = fork.release();
+        g_sub.join[0] = join0.release();
+        g_sub.join[1] = join1.release();
         g_sub.device = dev;
     }
     *out = &g_sub;
@@ -2079,6 +2087,20 @@ extern "C" int tri_fill_windows(void* vis_windows_c64, uint8_t* flag_windows, in
     return TRI_OK;
 }
 
+// Rows of the pack / unpack entry points: launch(r0, nr) for each slab [r0, r0 + nr) of [0, rows), at most 65535 rows
+// (gridDim.y) each.  The kernels index with int: a dimension above 2^31 - 1 is refused.
+template <class Launch>
+static int for_row_slabs(int64_t rows, int64_t nchan, int64_t ncorr, int64_t nbl, int64_t ntime, Launch&& launch) {
+    if (rows == 0) return TRI_OK;
+    if (rows > 0x7FFFFFFF || nchan > 0x7FFFFFFF || ncorr > 0x7FFFFFFF || nbl > 0x7FFFFFFF || ntime > 0x7FFFFFFF)
+        return set_err(TRI_EUNSUPPORTED, "dimension too large for one call");
+    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
+        launch(r0, (unsigned)std::min<int64_t>(65535, rows - r0));
+        LAUNCHCHK();
+    }
+    return TRI_OK;
+}
+
 extern "C" int tri_pack_data(const void* data_c64, const uint8_t* flag, const int32_t* row_bl,
                              const int32_t* row_time, int64_t rows, int64_t nchan, int64_t ncorr,
                              int64_t nbl, int64_t ntime, void* vis_windows_c64,
@@ -2086,33 +2108,27 @@ extern "C" int tri_pack_data(const void* data_c64, const uint8_t* flag, const in
     if (!data_c64 || !flag || !row_bl || !row_time || !vis_windows_c64 || !flag_windows)
         return set_err(TRI_EINVAL, "NULL pointer argument");
     if (rows < 0 || nchan <= 0 || ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (rows == 0) return TRI_OK;
-    if (rows > 0x7FFFFFFF) return set_err(TRI_EUNSUPPORTED, "too many rows in one call");
-    dim3 grid((unsigned)cdiv(nchan, 256), 1, 1);
-    // gridDim.y is limited to 65535: walk the rows in slabs
-    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
-        int64_t nr = std::min<int64_t>(65535, rows - r0);
-        grid.y = (unsigned)nr;
+    // 1 / 2 / 4 correlations with 16-byte aligned rows: vector loads of a thread's (chan, corr) piece
+    const bool al = ((uintptr_t)data_c64 % 16 == 0) && ((uintptr_t)flag % 4 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return for_row_slabs(rows, nchan, ncorr, nbl, ntime, [&](int64_t r0, unsigned nr) {
+        const dim3 grid((unsigned)cdiv(nchan, 256), nr, 1);
         const float2* dsl = (const float2*)data_c64 + (size_t)r0 * nchan * ncorr;
         const uint8_t* fsl = flag + (size_t)r0 * nchan * ncorr;
-        // 1 / 2 / 4 correlations with 16-byte aligned rows: vector loads of a thread's (chan, corr) piece
-        const bool al = ((uintptr_t)data_c64 % 16 == 0) && ((uintptr_t)flag % 4 == 0);
         if (ncorr == 4 && al)
-            hipLaunchKernelGGL(k_pack_v<4>, grid, dim3(256), 0, (hipStream_t)stream, dsl, fsl, row_bl + r0, row_time + r0,
+            hipLaunchKernelGGL(k_pack_v<4>, grid, dim3(256), 0, st, dsl, fsl, row_bl + r0, row_time + r0,
                                (int)nchan, (int)nbl, (int)ntime, (float2*)vis_windows_c64, flag_windows);
         else if (ncorr == 2 && al)
-            hipLaunchKernelGGL(k_pack_v<2>, grid, dim3(256), 0, (hipStream_t)stream, dsl, fsl, row_bl + r0, row_time + r0,
+            hipLaunchKernelGGL(k_pack_v<2>, grid, dim3(256), 0, st, dsl, fsl, row_bl + r0, row_time + r0,
                                (int)nchan, (int)nbl, (int)ntime, (float2*)vis_windows_c64, flag_windows);
         else if (ncorr == 1)
-            hipLaunchKernelGGL(k_pack_v<1>, grid, dim3(256), 0, (hipStream_t)stream, dsl, fsl, row_bl + r0, row_time + r0,
+            hipLaunchKernelGGL(k_pack_v<1>, grid, dim3(256), 0, st, dsl, fsl, row_bl + r0, row_time + r0,
                                (int)nchan, (int)nbl, (int)ntime, (float2*)vis_windows_c64, flag_windows);
         else
-            hipLaunchKernelGGL(k_pack, grid, dim3(256), 0, (hipStream_t)stream, dsl, fsl,
+            hipLaunchKernelGGL(k_pack, grid, dim3(256), 0, st, dsl, fsl,
                                row_bl + r0, row_time + r0, (int)nchan, (int)ncorr, (int)nbl, (int)ntime,
                                (float2*)vis_windows_c64, flag_windows);
-        LAUNCHCHK();
-    }
-    return TRI_OK;
+    });
 }
 
 extern "C" int tri_unpack_data(const uint8_t* flag_windows, const int32_t* row_bl,
@@ -2121,27 +2137,24 @@ extern "C" int tri_unpack_data(const uint8_t* flag_windows, const int32_t* row_b
                                void* stream) {
     if (!flag_windows || !row_bl || !row_time || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
     if (rows < 0 || nchan <= 0 || ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
-    dim3 grid((unsigned)cdiv(nchan, 256), 1, 1);
-    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
-        int64_t nr = std::min<int64_t>(65535, rows - r0);
-        grid.y = (unsigned)nr;
+    const bool al = (uintptr_t)out_flags % 4 == 0;
+    hipStream_t st = (hipStream_t)stream;
+    return for_row_slabs(rows, nchan, ncorr, nbl, ntime, [&](int64_t r0, unsigned nr) {
+        const dim3 grid((unsigned)cdiv(nchan, 256), nr, 1);
         uint8_t* osl = out_flags + (size_t)r0 * nchan * ncorr;
-        const bool al = (uintptr_t)out_flags % 4 == 0;
         if (ncorr == 4 && al)
-            hipLaunchKernelGGL(k_unpack_v<4>, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0, row_time + r0,
+            hipLaunchKernelGGL(k_unpack_v<4>, grid, dim3(256), 0, st, flag_windows, row_bl + r0, row_time + r0,
                                (int)nchan, (int)nbl, (int)ntime, osl, any_corr);
         else if (ncorr == 2 && al)
-            hipLaunchKernelGGL(k_unpack_v<2>, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0, row_time + r0,
+            hipLaunchKernelGGL(k_unpack_v<2>, grid, dim3(256), 0, st, flag_windows, row_bl + r0, row_time + r0,
                                (int)nchan, (int)nbl, (int)ntime, osl, any_corr);
         else if (ncorr == 1)
-            hipLaunchKernelGGL(k_unpack_v<1>, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0, row_time + r0,
+            hipLaunchKernelGGL(k_unpack_v<1>, grid, dim3(256), 0, st, flag_windows, row_bl + r0, row_time + r0,
                                (int)nchan, (int)nbl, (int)ntime, osl, any_corr);
         else
-            hipLaunchKernelGGL(k_unpack, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0, row_time + r0,
+            hipLaunchKernelGGL(k_unpack, grid, dim3(256), 0, st, flag_windows, row_bl + r0, row_time + r0,
                                (int)nchan, (int)ncorr, (int)nbl, (int)ntime, osl, any_corr);
-        LAUNCHCHK();
-    }
-    return TRI_OK;
+    });
 }
 
 // host term tables (idx = (c1, c2, s1, s2), alpha = (re, im) per term) -> StokesTerm; false if a
@@ -2179,26 +2192,20 @@ extern "C" int tri_pack_scan(const void* data_c64, const void* model_c64, const 
         if (!fill_stokes_terms(terms.pol, pol_idx, pol_alpha, n_pol, ncorr))
             return set_err(TRI_EINVAL, "correlation index out of range");
     }
-    if (rows == 0) return TRI_OK;
-    if (rows > 0x7FFFFFFF || nchan > 0x7FFFFFFF || ncorr > 0x7FFFFFFF || nbl > 0x7FFFFFFF || ntime > 0x7FFFFFFF)
-        return set_err(TRI_EUNSUPPORTED, "dimension too large for one call");
     const bool stokes = mode != 0;
     // 1 / 2 / 4 correlations with 16-byte aligned rows: vector loads of a thread's (chan, corr) piece
     const bool al = (uintptr_t)data_c64 % 16 == 0 && (uintptr_t)model_c64 % 16 == 0 && (uintptr_t)flag % 4 == 0;
     const bool vec = al && (ncorr == 4 || ncorr == 2 || ncorr == 1);
-    dim3 grid((unsigned)cdiv(nchan, 256), 1, 1);
-    // gridDim.y is limited to 65535: walk the rows in slabs
-    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
-        const int64_t nr = std::min<int64_t>(65535, rows - r0);
-        grid.y = (unsigned)nr;
+    hipStream_t st = (hipStream_t)stream;
+    float2* vw = (float2*)vis_windows_c64;
+    return for_row_slabs(rows, nchan, ncorr, nbl, ntime, [&](int64_t r0, unsigned nr) {
+        const dim3 grid((unsigned)cdiv(nchan, 256), nr, 1);
         const size_t off = (size_t)r0 * nchan * ncorr;
         const float2* d = (const float2*)data_c64 + off;
         const float2* m = model_c64 ? (const float2*)model_c64 + off : nullptr;
         const uint8_t* fl = flag ? flag + off : nullptr;
         const int32_t* rb = row_bl + r0;
         const int32_t* rt = row_time + r0;
-        hipStream_t st = (hipStream_t)stream;
-        float2* vw = (float2*)vis_windows_c64;
 #define TRI_PACK_SCAN_V(NC, S)                                                                                      \
         do {                                                                                                         \
             if (m && fl)  hipLaunchKernelGGL((k_pack_scan_v<NC, S, true, true>), grid, dim3(256), 0, st, d, m, fl,   \
@@ -2220,9 +2227,7 @@ extern "C" int tri_pack_scan(const void* data_c64, const void* model_c64, const 
             hipLaunchKernelGGL(k_pack_scan, grid, dim3(256), 0, st, d, m, fl, rb, rt, (int)nchan, (int)ncorr,
                                (int)nbl, (int)ntime, stokes ? 1 : 0, terms, vw, flag_windows);
 #undef TRI_PACK_SCAN_V
-        LAUNCHCHK();
-    }
-    return TRI_OK;
+    });
 }
 
 extern "C" int tri_unpack_scan(const uint8_t* flag_windows, const int32_t* row_bl, const int32_t* row_time,
@@ -2231,23 +2236,17 @@ extern "C" int tri_unpack_scan(const uint8_t* flag_windows, const int32_t* row_b
     if (!flag_windows || !row_bl || !row_time || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
     if (rows < 0 || nchan <= 0 || out_ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
     if (wcorr != 1 && wcorr != out_ncorr) return set_err(TRI_EINVAL, "wcorr must be 1 or out_ncorr");
-    if (rows == 0) return TRI_OK;
-    if (rows > 0x7FFFFFFF || nchan > 0x7FFFFFFF || out_ncorr > 0x7FFFFFFF || nbl > 0x7FFFFFFF || ntime > 0x7FFFFFFF)
-        return set_err(TRI_EUNSUPPORTED, "dimension too large for one call");
-    dim3 grid((unsigned)cdiv(nchan, 256), 1, 1);
-    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
-        const int64_t nr = std::min<int64_t>(65535, rows - r0);
-        grid.y = (unsigned)nr;
+    hipStream_t st = (hipStream_t)stream;
+    return for_row_slabs(rows, nchan, out_ncorr, nbl, ntime, [&](int64_t r0, unsigned nr) {
+        const dim3 grid((unsigned)cdiv(nchan, 256), nr, 1);
         uint8_t* osl = out_flags + (size_t)r0 * nchan * out_ncorr;
         if (out_ncorr == 4 && (uintptr_t)out_flags % 4 == 0)
-            hipLaunchKernelGGL(k_unpack_scan<4>, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0,
+            hipLaunchKernelGGL(k_unpack_scan<4>, grid, dim3(256), 0, st, flag_windows, row_bl + r0,
                                row_time + r0, (int)nchan, (int)wcorr, 4, (int)nbl, (int)ntime, osl);
         else
-            hipLaunchKernelGGL(k_unpack_scan<0>, grid, dim3(256), 0, (hipStream_t)stream, flag_windows, row_bl + r0,
+            hipLaunchKernelGGL(k_unpack_scan<0>, grid, dim3(256), 0, st, flag_windows, row_bl + r0,
                                row_time + r0, (int)nchan, (int)wcorr, (int)out_ncorr, (int)nbl, (int)ntime, osl);
-        LAUNCHCHK();
-    }
-    return TRI_OK;
+    });
 }
 
 // Measurement / test hook: ONE rejection step of the background loop (flagging.py:553-574) as the flagger runs it for blocks
@@ -2276,18 +2275,20 @@ extern "C" int tri_bench_reject(const float* resid, const uint8_t* flags_in, uin
     const size_t N = (size_t)Fa * T;
     const size_t nb = (size_t)maxchunk * T, ccap = (nb / 4) & ~(size_t)3, ucap = (nb / 8) & ~(size_t)3;
     const size_t wsS = mrt_scratch_words(G, ccap, ucap);
-    unsigned* sc = nullptr;
-    int64_t* d_ends = nullptr;
-    HIPCHK(hipMalloc(&sc, (size_t)n_win * wsS * sizeof(unsigned)));
-    HIPCHK(hipMalloc(&d_ends, (size_t)n_chunk_ends * sizeof(int64_t)));
+    DevBuf<unsigned> scb;
+    DevBuf<int64_t> endsb;
+    HIPCHK(scb.alloc((size_t)n_win * wsS));
+    HIPCHK(endsb.alloc((size_t)n_chunk_ends));
+    unsigned* sc = scb.get();
+    int64_t* d_ends = endsb.get();
     HIPCHK(hipMemcpyAsync(d_ends, chunk_ends, (size_t)n_chunk_ends * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     const double rej = TRI_MAD_NORMAL * reject;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    HipEvent e0, e1;
+    HIPCHK(hipEventCreate(e0.out()));
+    HIPCHK(hipEventCreate(e1.out()));
     const unsigned W = (unsigned)n_win;
-    HIPCHK(hipEventRecord(e0, st));
+    HIPCHK(hipEventRecord(e0.get(), st));
     for (int i = 0; i < repeats; i++) {
         hipLaunchKernelGGL(k_mr_predict, dim3((unsigned)G, W), dim3(256), 0, st, resid, flags_in, d_ends, rej, T / 4, G, N, N, sc, wsS, ccap, ucap, 0);
         for (unsigned round = 1; round <= 2; round++) {
@@ -2299,13 +2300,11 @@ extern "C" int tri_bench_reject(const float* resid, const uint8_t* flags_in, uin
         hipLaunchKernelGGL(k_median_reject, dim3((unsigned)G, W), dim3(256), 0, st, resid, flags_in, flags_out, flags_t4, med, d_ends, rej, Fa, T / 4, G,
                            N, N, sc, wsS, 0u, 0u, 1, (const unsigned*)sc, wsS, (int)MRT_PARW, 11);
     }
-    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipEventRecord(e1.get(), st));
     hipError_t le = hipGetLastError();
-    hipError_t se = hipEventSynchronize(e1);
+    hipError_t se = hipEventSynchronize(e1.get());
     float ms = 0.f;
-    if (le == hipSuccess && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(sc); (void)hipFree(d_ends);
+    if (le == hipSuccess && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0.get(), e1.get());
     if (le != hipSuccess) return set_err(TRI_EHIP, "launch: %s", hipGetErrorString(le));
     if (se != hipSuccess) return set_err(TRI_EHIP, "sync: %s", hipGetErrorString(se));
     *ms_per_step = ms / (float)repeats;
@@ -2325,23 +2324,7 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     if (rc) return rc;
     double thr_scale = outlier_nsigma * TRI_MAD_NORMAL;
     size_t nthreads = (size_t)n_win * n_col;
-    double* ring = nullptr;
-    uint8_t* acc = nullptr;
-    int64_t* d_ends = nullptr;
-    HIPCHK(hipMalloc(&ring, nthreads * sw.ringtot * sizeof(double)));
-    HIPCHK(hipMalloc(&acc, nthreads * sw.acccap));
-    HIPCHK(hipMalloc(&d_ends, 2 * sizeof(int64_t)));
-    int64_t ends[2] = {0, n_line};
-    HIPCHK(hipMemcpyAsync(d_ends, ends, sizeof(ends), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
     int C = (int)n_col, L = (int)n_line;
-    int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-    if (const char* e = getenv("TRI_ST_BLK")) { int b = atoi(e); if (b >= 64 && b <= ST_MAXBLK && C >= b) blk = b; }
-    dim3 grid((unsigned)cdiv(C, blk), 1, (unsigned)n_win);
-    size_t ws = (size_t)n_line * n_col;
     bool can_fuse = sw.nw == 4 && sw.w[0] == 1 && sw.w[1] == 2 && sw.w[2] == 4 && sw.w[3] == 8;
     if ((variant == 2 || variant == 3) && !can_fuse) return set_err(TRI_EUNSUPPORTED, "register cascade needs windows (1,2,4,8)");
     if (variant == 3 && !((uint64_t)L * (uint64_t)C * 4u < (1ull << 31)))
@@ -2352,61 +2335,81 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     if (variant == 5 && !(can_fuse && C % 64 == 0 && (uint64_t)L * (uint64_t)C * 4u < (1ull << 31)))
         return set_err(TRI_EUNSUPPORTED, "panel SumThreshold: windows (1,2,4,8), a multiple of 64 columns, a window below 2^31 bytes");
     if (variant == 0 && can_fuse) variant = st_use_mask(L, C) ? ((C % 64 == 0 && !no_panel) ? 5 : 3) : 2;
-    float* pdata = nullptr;
-    uint8_t* pout = nullptr;
-    if (variant == 5) {
-        HIPCHK(hipMalloc(&pdata, (size_t)n_win * ws * sizeof(float)));
-        HIPCHK(hipMalloc(&pout, (size_t)n_win * ws));
-        const bool klog = g_klog_on;
-        g_klog_on = false;                                   // (re-layout helpers are not part of what is measured)
-        hipLaunchKernelGGL(k_panelize<float>, dim3((unsigned)cdiv((int64_t)ws, 256), (unsigned)n_win), dim3(256), 0, st, data, pdata, L, C, ws);
-        g_klog_on = klog;
-        LAUNCHCHK();
-    }
     if (variant == 4) {
         if (sw.nw > 8 || stp_lds_bytes(sw) > 160 * 1024) return set_err(TRI_EUNSUPPORTED, "stage pipeline: more than eight windows, or the flag ring does not fit LDS");
         HIPCHK(lds_optin(reinterpret_cast<const void*>(&k_colst_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
+    DevBuf<double> ring;
+    DevBuf<uint8_t> acc;
+    DevBuf<int64_t> d_ends;
+    HIPCHK(ring.alloc(nthreads * sw.ringtot));
+    HIPCHK(acc.alloc(nthreads * sw.acccap));
+    HIPCHK(d_ends.alloc(2));
+    int64_t ends[2] = {0, n_line};
+    HIPCHK(hipMemcpyAsync(d_ends.get(), ends, sizeof(ends), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HipEvent e0, e1;
+    HIPCHK(hipEventCreate(e0.out()));
+    HIPCHK(hipEventCreate(e1.out()));
+    int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
+    if (const char* e = getenv("TRI_ST_BLK")) { int b = atoi(e); if (b >= 64 && b <= ST_MAXBLK && C >= b) blk = b; }
+    dim3 grid((unsigned)cdiv(C, blk), 1, (unsigned)n_win);
+    size_t ws = (size_t)n_line * n_col;
+    DevBuf<float> pdata;
+    DevBuf<uint8_t> pout;
+    if (variant == 5) {
+        HIPCHK(pdata.alloc((size_t)n_win * ws));
+        HIPCHK(pout.alloc((size_t)n_win * ws));
+        {
+            ScopedSet<bool> pause(g_klog_on, false);         // (re-layout helpers are not part of what is measured)
+            hipLaunchKernelGGL(k_panelize<float>, dim3((unsigned)cdiv((int64_t)ws, 256), (unsigned)n_win), dim3(256), 0, st, data, pdata.get(), L, C, ws);
+        }
+        LAUNCHCHK();
+    }
     bool fused = variant == 2;
     StFusedArgs fa;
     for (int j = 0; j < 4; j++) fa.tf[j] = sw.tf[j < sw.nw ? j : 0];
-    HIPCHK(hipEventRecord(e0, st));
+    HIPCHK(hipEventRecord(e0.get(), st));
     for (int i = 0; i < repeats; i++) {
         if (variant == 5)
-            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8, true>), grid, dim3(blk), 0, st, (const float*)pdata, mad, pout, d_ends, fa, thr_scale, L, C, 1, ws, ws);
+            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8, true>), grid, dim3(blk), 0, st, (const float*)pdata.get(), mad, pout.get(), d_ends.get(), fa, thr_scale, L, C, 1, ws, ws);
         else if (variant == 3)
-            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, mad, out, d_ends, fa, thr_scale, L, C, 1, ws, ws);
+            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, mad, out, d_ends.get(), fa, thr_scale, L, C, 1, ws, ws);
         else if (fused)
-            hipLaunchKernelGGL((k_colst_fused<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, mad, out, d_ends, fa, thr_scale, L, C, 1, ws, ws);
+            hipLaunchKernelGGL((k_colst_fused<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, mad, out, d_ends.get(), fa, thr_scale, L, C, 1, ws, ws);
         else if (variant == 4)
             hipLaunchKernelGGL(k_colst_pipe, dim3((unsigned)cdiv(C, 64), 1, (unsigned)n_win), dim3(64 * sw.nw), stp_lds_bytes(sw), st,
-                               data, mad, out, d_ends, sw, stp_plan(sw), thr_scale, L, C, 1, ws, ws);
+                               data, mad, out, d_ends.get(), sw, stp_plan(sw), thr_scale, L, C, 1, ws, ws);
         else
-            hipLaunchKernelGGL(k_colst_dyn, grid, dim3(blk), 0, st, data, mad, out, ring, acc, d_ends, sw, thr_scale, L, C, 1, ws, ws);
+            hipLaunchKernelGGL(k_colst_dyn, grid, dim3(blk), 0, st, data, mad, out, ring.get(), acc.get(), d_ends.get(), sw, thr_scale, L, C, 1, ws, ws);
     }
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventRecord(e1.get(), st));
+    HIPCHK(hipEventSynchronize(e1.get()));
     LAUNCHCHK();
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
     *ms_per_launch = ms / repeats;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (variant == 5) {
-        const bool klog = g_klog_on;
-        g_klog_on = false;
-        hipLaunchKernelGGL(k_unpanel_w<uint8_t>, dim3((unsigned)cdiv((int64_t)ws, 256), (unsigned)n_win), dim3(256), 0, st, (const uint8_t*)pout, out, L, C, ws);
-        g_klog_on = klog;
+        {
+            ScopedSet<bool> pause(g_klog_on, false);
+            hipLaunchKernelGGL(k_unpanel_w<uint8_t>, dim3((unsigned)cdiv((int64_t)ws, 256), (unsigned)n_win), dim3(256), 0, st, (const uint8_t*)pout.get(), out, L, C, ws);
+        }
         LAUNCHCHK();
         HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(pdata);
-        (void)hipFree(pout);
     }
-    (void)hipFree(ring);
-    (void)hipFree(acc);
-    (void)hipFree(d_ends);
     return TRI_OK;
 }
+
+// The thread-local route overrides of the box filters, saved on entry and restored on exit: a hook that switches routes
+// leaves the flagger's routes as it found them on every return.
+struct RouteOverrides {
+    const int r = g_boxr_override, w = g_boxw_override, p = g_boxp_override, q = g_boxq_override,
+              q8 = g_boxq_b8_override, x = g_boxx_override;
+    ~RouteOverrides() {
+        g_boxr_override = r; g_boxw_override = w; g_boxp_override = p;
+        g_boxq_override = q; g_boxq_b8_override = q8; g_boxx_override = x;
+    }
+};
 
 // Measurement / test hook: one axis stage of the masked box filter in the launch geometry of
 // the step (see include/tricolour_amd.h).
@@ -2424,10 +2427,11 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     r.st = (hipStream_t)stream;
     r.p = nullptr;
     r.dbg = nullptr;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    HipEvent e0, e1;
+    HIPCHK(hipEventCreate(e0.out()));
+    HIPCHK(hipEventCreate(e1.out()));
     const size_t N = (size_t)n_line * n_col;
+    const RouteOverrides saved;
     g_boxr_override = variant == 0 ? -1 : (variant == 1 ? 0 : 1);
     g_boxw_override = variant == 0 ? -1 : 0;            // the named variants run BOTH images through their own kernels
     // stage 2: 0 = the flagger's route, 1 = register rings, 2 / 3 = stage pipeline with blocks of 16 / 8
@@ -2443,26 +2447,26 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     // stage 1, variant 4: K4x works on rows -- the amplitudes are taken to the TF layout once (untimed), the rows it
     // writes go back to FT inside the timed loop (as in the flagger); out_w doubles as the row buffer.
     // ms_per_launch then covers kernel + transpose; the counters in stats[] are printed with TRI_BOXX_STATS=1
-    float* x_data_tf = nullptr;
-    unsigned long long* x_stats = nullptr;
+    DevBuf<float> x_data_tf;
+    DevBuf<unsigned long long> x_stats;
     int xl = 0;
     if (stage == 1 && variant == 4) {
         g_boxx_override = 1;
         xl = boxx_pick_l((int)radius, (int)n_col);
         g_boxx_override = -1;
         if (!xl) return set_err(TRI_EUNSUPPORTED, "no exact row filter for radius %d on lines of %d", (int)radius, (int)n_col);
-        HIPCHK(hipMalloc(&x_data_tf, (size_t)n_win * N * sizeof(float)));
-        HIPCHK(hipMalloc(&x_stats, 2 * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(x_stats, 0, 2 * sizeof(unsigned long long), r.st));
-        rc = launch_transpose<float>(r, data, x_data_tf, (int)n_col, (int)n_line, N, N, n_win);
+        HIPCHK(x_data_tf.alloc((size_t)n_win * N));
+        HIPCHK(x_stats.alloc(2));
+        HIPCHK(hipMemsetAsync(x_stats.get(), 0, 2 * sizeof(unsigned long long), r.st));
+        rc = launch_transpose<float>(r, data, x_data_tf.get(), (int)n_col, (int)n_line, N, N, n_win);
         if (rc) return rc;
     }
-    HIPCHK(hipEventRecord(e0, r.st));
+    HIPCHK(hipEventRecord(e0.get(), r.st));
     for (int i = 0; i < repeats && rc == TRI_OK; i++) {
         if (xl) {
             const float* srcW = reinterpret_cast<const float*>(flags4);
-            rc = launch_boxx<1>(r, xl, srcW, srcW + N, x_data_tf, nullptr, out_w, nullptr, (int)n_col, (int)n_line, (int)n_col, (int)radius,
-                                2 * N, N, 0, N, 0, n_win, nullptr, x_stats);
+            rc = launch_boxx<1>(r, xl, srcW, srcW + N, x_data_tf.get(), nullptr, out_w, nullptr, (int)n_col, (int)n_line, (int)n_col, (int)radius,
+                                2 * N, N, 0, N, 0, n_win, nullptr, x_stats.get());
             if (rc == TRI_OK) rc = launch_transpose<float>(r, out_w, out_o, (int)n_line, (int)n_col, N, N, n_win);
         } else if (stage == 2) {
             // spectrum path: byte flags [n_line][n_col] + data -> filtered weight and data images
@@ -2492,29 +2496,20 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
             }
         }
     }
-    g_boxr_override = -1;
-    g_boxp_override = -1;
-    g_boxq_override = -1;
-    g_boxq_b8_override = -1;
-    g_boxw_override = -1;
     if (rc) return rc;
-    HIPCHK(hipEventRecord(e1, r.st));
-    HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventRecord(e1.get(), r.st));
+    HIPCHK(hipEventSynchronize(e1.get()));
     LAUNCHCHK();
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
     *ms_per_launch = ms / repeats;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (xl) {
         unsigned long long h[2] = {0, 0};
-        HIPCHK(hipMemcpy(h, x_stats, sizeof(h), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h, x_stats.get(), sizeof(h), hipMemcpyDeviceToHost));
         g_boxx_last_stats[0] = h[0];
         g_boxx_last_stats[1] = h[1];
         if (const char* e = getenv("TRI_BOXX_STATS")) if (e[0] == '1')
             fprintf(stderr, "k_boxx r=%d L=%d x %d threads: %llu line passes, %llu redone sequentially\n", (int)radius, xl & 255, xl >> 8, h[0], h[1]);
-        (void)hipFree(x_data_tf);
-        (void)hipFree(x_stats);
     }
     return TRI_OK;
 }
@@ -2596,15 +2591,14 @@ __global__ void k_check_box_divide(BoxDenom dn, unsigned long long* out) {
 extern "C" int tri_test_box_divide(int64_t radius, uint64_t* mismatches, void* stream) {
     if (!mismatches || radius < 0 || radius > (1 << 20)) return set_err(TRI_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_check_box_divide, dim3(4096), dim3(256), 0, st, box_reciprocal(box_denominator(radius)), d);
+    DevBuf<unsigned long long> d;
+    HIPCHK(d.alloc(1));
+    HIPCHK(hipMemsetAsync(d.get(), 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_check_box_divide, dim3(4096), dim3(256), 0, st, box_reciprocal(box_denominator(radius)), d.get());
     LAUNCHCHK();
     unsigned long long h = 0;
-    HIPCHK(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&h, d.get(), sizeof(h), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(d);
     *mismatches = h;
     return TRI_OK;
 }
@@ -2635,27 +2629,27 @@ extern "C" int tri_test_median(const float* data, const uint8_t* flags, double* 
         maxlen = std::max(maxlen, len[g]);
         al4 = al4 && start[g] % 4 == 0 && len[g] % 4 == 0;
     }
-    int64_t *d_start = nullptr, *d_len = nullptr;
-    HIPCHK(hipMalloc(&d_start, G * sizeof(int64_t)));
-    HIPCHK(hipMalloc(&d_len, G * sizeof(int64_t)));
-    HIPCHK(hipMemcpy(d_start, start.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_len, len.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
+    DevBuf<int64_t> d_start_b, d_len_b;
+    HIPCHK(d_start_b.alloc(G));
+    HIPCHK(d_len_b.alloc(G));
+    const int64_t* d_start = d_start_b.get();
+    const int64_t* d_len = d_len_b.get();
+    HIPCHK(hipMemcpy(d_start_b.get(), start.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_len_b.get(), len.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
     size_t WS = (size_t)rows * row_len, RS = (size_t)row_len;
     int R = (int)rows;
     if (variant == 8) {
         // multi-workgroup two-pass select (K3d): one segment spanning each whole row
         if (G != 1 || seg_ends[0] != 0 || seg_ends[1] != row_len) return set_err(TRI_EINVAL, "variant 8 takes one segment covering the row");
         const int64_t B = n_win * rows;
-        MedBigPar* par = nullptr;
-        unsigned *ghist = nullptr, *gcand = nullptr;
-        HIPCHK(hipMalloc(&par, B * sizeof(MedBigPar)));
-        HIPCHK(hipMalloc(&ghist, B * SEL_BINS * sizeof(unsigned)));
-        HIPCHK(hipMalloc(&gcand, B * (size_t)MEDBIG_CAND * sizeof(unsigned)));
-        int rcb = launch_median_big(st, data, flags, (size_t)row_len, B, nullptr, med, par, ghist, gcand,
+        DevBuf<MedBigPar> par;
+        DevBuf<unsigned> ghist, gcand;
+        HIPCHK(par.alloc(B));
+        HIPCHK(ghist.alloc(B * SEL_BINS));
+        HIPCHK(gcand.alloc(B * (size_t)MEDBIG_CAND));
+        int rcb = launch_median_big(st, data, flags, (size_t)row_len, B, nullptr, med, par.get(), ghist.get(), gcand.get(),
                                     row_len % 4 == 0 && ((uintptr_t)data % 16 == 0) && ((uintptr_t)flags % 4 == 0));
         HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(par); (void)hipFree(ghist); (void)hipFree(gcand);
-        (void)hipFree(d_start); (void)hipFree(d_len);
         return rcb;
     }
     if (variant == 0) variant = maxlen <= 64 * MW_K ? 1 : (al4 ? 3 : 2);
@@ -2701,18 +2695,17 @@ extern "C" int tri_test_median(const float* data, const uint8_t* flags, double* 
     else if (variant == 9 || variant == 10) {
         // K3c with the predicted-window candidates in global scratch (9: vector loads, 10: scalar)
         if (variant == 9 && row_len % 4 != 0) return set_err(TRI_EINVAL, "variant 9 needs row_len % 4 == 0");
-        unsigned* gc = nullptr;
+        DevBuf<unsigned> gc;
         const size_t cap = ((size_t)maxlen + 3) & ~(size_t)3, per_win = cap * (size_t)R * G;
-        HIPCHK(hipMalloc(&gc, per_win * (size_t)n_win * sizeof(unsigned)));
+        HIPCHK(gc.alloc(per_win * (size_t)n_win));
         if (variant == 9)
             hipLaunchKernelGGL(k_median2<true>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                               med, WS, WS, RS, (size_t)1, d_start, d_len, R, G, gc, per_win, (unsigned)cap);
+                               med, WS, WS, RS, (size_t)1, d_start, d_len, R, G, gc.get(), per_win, (unsigned)cap);
         else
             hipLaunchKernelGGL(k_median2<false>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                               med, WS, WS, RS, (size_t)1, d_start, d_len, R, G, gc, per_win, (unsigned)cap);
+                               med, WS, WS, RS, (size_t)1, d_start, d_len, R, G, gc.get(), per_win, (unsigned)cap);
         hipError_t le = hipGetLastError();
         hipError_t se = hipStreamSynchronize(st);
-        (void)hipFree(gc); (void)hipFree(d_start); (void)hipFree(d_len);
         if (le != hipSuccess || se != hipSuccess) return set_err(TRI_EHIP, "median variant %d failed", variant);
         return TRI_OK;
     } else if (variant == 7) {
@@ -2727,8 +2720,6 @@ extern "C" int tri_test_median(const float* data, const uint8_t* flags, double* 
                            med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
     LAUNCHCHK();
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(d_start);
-    (void)hipFree(d_len);
     return TRI_OK;
 }
 
