@@ -671,6 +671,114 @@ def test_median_wave_corners(gpu, row_len, ends):
         assert np.array_equal(got, exp), "variant %d: %d medians differ" % (variant, (got != exp).sum())
 
 
+def _median_hook_kernels(variant, row_len, ends):
+    """The kernel tri_test_median launches for `variant` on rows of `row_len` cut at `ends`, as the header documents it
+    (None: the hook refuses the call).  MW_SPW / MW_SPW16 at their shipped values, 8 and 1 rows per wave."""
+    lens = np.diff(ends)
+    maxlen, G = int(lens.max()), len(lens)
+    al4 = row_len % 4 == 0 and all(e % 4 == 0 for e in ends)
+    full_row = G == 1 and ends[0] == 0 and ends[-1] == row_len
+    if variant == 0:
+        variant = 1 if maxlen <= 1024 else (3 if al4 else 2)
+    old = variant in (11, 14)
+    if old:
+        variant -= 10
+    if variant in (1, 4) and maxlen > 1024:
+        return None
+    if variant == 4 and (row_len % 4 or maxlen + 3 > 1024):
+        return None
+    if variant in (3, 5) and not al4:
+        return None
+    if variant in (7, 9) and row_len % 4:
+        return None
+    spw8, spw16 = (1, 1) if old else (8, 1)
+    if variant == 1 and maxlen <= 512:
+        return "k_median_wave<8, false, %d>" % spw8
+    if variant == 4 and maxlen + 3 <= 512:
+        return "k_median_wave<8, true, %d>" % spw8
+    if variant == 4 or (variant == 1 and full_row and al4):
+        return "k_median_wave<16, true, %d>" % spw16
+    if variant == 1:
+        return "k_median_wave<16, false, %d>" % spw16
+    return {3: "k_median<true>", 5: "k_median2<true, false, 4>", 6: "k_median2<false, false, 4>",
+            7: "k_median2<true, false, 4>", 9: "k_median2<true, false, 4>",
+            10: "k_median2<false, false, 4>"}.get(variant, "k_median<false>")
+
+
+@pytest.mark.parametrize("row_len,ends", [
+    (512, [0, 200, 512]),            # segments <= 512, 4-aligned
+    (512, [0, 512]),                 # one aligned full row of 512
+    (301, [0, 150, 301]),            # segments <= 512, not aligned
+    (2000, [0, 1000, 2000]),         # segments <= 1021, aligned
+    (1000, [0, 1000]),               # one aligned full row of at most 1021
+    (1024, [0, 1024]),               # one aligned full row of 1024
+    (1024, [2, 1022]),               # segments <= 1021 of a 4-aligned row, not 4-aligned themselves
+    (3000, [0, 1500, 3000]),         # long segments, aligned
+    (3001, [0, 1501, 3001]),         # long segments, not aligned
+])
+def test_median_hook_dispatch(gpu, row_len, ends):
+    """Which kernel each tri_test_median variant launches (kernel log), and which calls it refuses: the hook must
+    keep launching the kernels its header names on every branch of its choice."""
+    import ctypes as C
+    import torch
+    from tricolour_amd import _lib
+    rs = np.random.RandomState(row_len)
+    n_win, rows = 2, 3
+    d = torch.from_numpy(rs.standard_normal((n_win, rows, row_len)).astype(np.float32)).cuda()
+    f = torch.from_numpy(rs.uniform(size=(n_win, rows, row_len)) < 0.2).cuda().view(torch.uint8)
+    e = (C.c_int64 * len(ends))(*ends)
+    med = torch.empty((n_win, rows, len(ends) - 1), dtype=torch.float64, device="cuda")
+    got, want = {}, {}
+    for variant in (0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 14):
+        _lib.kernel_log_begin()
+        rc = _lib.lib().tri_test_median(d.data_ptr(), f.data_ptr(), med.data_ptr(), n_win, rows, row_len, e, len(ends),
+                                        variant, None)
+        torch.cuda.synchronize()
+        log = _lib.kernel_log_end()
+        got[variant] = None if rc else log
+        k = _median_hook_kernels(variant, row_len, ends)
+        want[variant] = None if k is None else {k: 1}
+    assert got == want
+
+
+@pytest.mark.parametrize("windows,n_col", [
+    ((1, 2, 4, 8), 128),             # register cascade windows, 64-column panels possible
+    ((1, 2, 4, 8), 130),             # ... and not
+    ((32, 48, 64, 128), 128),        # a K7p list
+    ((32, 48, 64, 128), 70),
+])
+def test_sumthreshold_hook_dispatch(gpu, windows, n_col):
+    """Which kernel each tri_bench_sumthreshold variant launches (kernel log, two timed launches each; the panel
+    re-layout of variant 5 is not logged), and which calls it refuses."""
+    import ctypes as C
+    import torch
+    from tricolour_amd import _lib
+    rs = np.random.RandomState(n_col)
+    n_win, n_line = 2, 200
+    d = torch.from_numpy(rs.standard_normal((n_win, n_line, n_col)).astype(np.float32)).cuda()
+    m = torch.ones((n_win, n_col), dtype=torch.float64, device="cuda")
+    out = torch.zeros((n_win, n_line, n_col), dtype=torch.uint8, device="cuda")
+    warr = (C.c_int64 * len(windows))(*windows)
+    ms = C.c_float(0)
+    fusable = tuple(windows) == (1, 2, 4, 8)
+    want = {0: ("k_colst_mask<1, 2, 4, 8, true>" if n_col % 64 == 0 else "k_colst_mask<1, 2, 4, 8, false>")
+               if fusable else "k_colst_dyn",
+            1: "k_colst_dyn",
+            2: "k_colst_fused<1, 2, 4, 8>" if fusable else None,
+            3: "k_colst_mask<1, 2, 4, 8, false>" if fusable else None,
+            4: "k_colst_pipe",
+            5: "k_colst_mask<1, 2, 4, 8, true>" if fusable and n_col % 64 == 0 else None}
+    got = {}
+    for variant in range(6):
+        _lib.kernel_log_begin()
+        rc = _lib.lib().tri_bench_sumthreshold(d.data_ptr(), m.data_ptr(), out.data_ptr(), n_win, n_line, n_col, warr,
+                                               len(windows), 5.0, 1.5, variant, 2, C.byref(ms), None)
+        torch.cuda.synchronize()
+        log = _lib.kernel_log_end()
+        got[variant] = None if rc else log
+    assert got == {v: None if k is None else {k: 2} for v, k in want.items()}
+
+
 @pytest.mark.parametrize("n_win,F,T,ends,reject", [
     (2, 256, 1024, [0, 128, 256], 2.0),
     (3, 200, 1024, [0, 67, 131, 200], 1.5),        # chunks that are not multiples of the 64-row tiles

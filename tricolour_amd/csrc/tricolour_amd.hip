@@ -411,81 +411,110 @@ bool st_use_mask(int L, int C) {
 // launch_median() can OR a second flag image and per-column flags into the flags it reads when the segments fit the wave kernels
 static bool median_takes_extra_flags(int64_t max_len) { return max_len <= 64 * MW_K; }
 
-int launch_median(const Run& r, const float* data, const uint8_t* flags, double* med, size_t WSd,
-                  size_t WSf, size_t RS, size_t ES, const int64_t* seg_start,
-                  const int64_t* seg_len, int R, int G, int64_t W, int64_t max_len, bool vec_ok = false,
-                  bool rows_aligned = false, bool segs_aligned = false,
-                  unsigned* gcand = nullptr, size_t cand_ws = 0, unsigned cand_cap = 0,
-                  const uint8_t* flags2 = nullptr, const uint8_t* colflags = nullptr, size_t WScol = 0, int panel_rows = 0) {
+// One segmented-median job: exact medians of |data| over the unflagged samples of each segment
+// [seg_start[g], + seg_len[g]) of each of R rows, in each of W windows; med[w][row][g].
+struct MedianJob {
+    const float* data = nullptr; const uint8_t* flags = nullptr; double* med = nullptr;
+    size_t WSd = 0, WSf = 0, RS = 0, ES = 1;    // window strides of data and flags, row stride, element stride
+    const int64_t* seg_start = nullptr; const int64_t* seg_len = nullptr;
+    int R = 0, G = 0;                           // rows, segments per row
+    int64_t W = 0, max_len = 0;                 // windows, longest segment
+    bool vec_ok = false;                        // segments contiguous, 16-byte aligned, a multiple of 4 long
+    bool rows_aligned = false;                  // rows 4-aligned
+    bool segs_aligned = false;                  // segment starts 4-aligned (no masked slots ahead of a segment)
+    // wave kernels: a second flag image and per-column flags (WScol bytes per window) OR-ed in; data / flags2 as column panels
+    const uint8_t* flags2 = nullptr; const uint8_t* colflags = nullptr; size_t WScol = 0; int panel_rows = 0;
+    // two-pass kernel: candidate scratch, cand_ws keys per window, cand_cap per segment
+    unsigned* gcand = nullptr; size_t cand_ws = 0; unsigned cand_cap = 0;
+};
+
+// The segmented-median kernels (kernels_median.hpp)
+enum class MedianKernel {
+    Wave8, Wave8Vec,            // k_median_wave<8, VEC>: segments of at most 512
+    Wave16, Wave16Vec,          // k_median_wave<MW_K, VEC>: at most 1024
+    Select, SelectVec,          // k_median<VEC>: three-pass select
+    TwoPass, TwoPassVec,        // k_median2<VEC>: two-pass select (K3c)
+    TwoPassVecLong,             // k_median2<true, false, 16>: sixteen 16-byte groups in flight per thread
+};
+
+template <int KS, bool VEC, int SPW>
+static void median_wave(hipStream_t st, const MedianJob& j) {
+    hipLaunchKernelGGL((k_median_wave<KS, VEC, SPW>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)j.R, SPW) * j.G, 4), (unsigned)j.W),
+                       dim3(256), 0, st, j.data, j.flags, j.med, j.WSd, j.WSf, j.RS, j.ES, j.seg_start, j.seg_len, j.R, j.G,
+                       j.flags2, j.colflags, j.WScol, j.panel_rows);
+}
+template <bool VEC>
+static void median_select(hipStream_t st, const MedianJob& j) {
+    hipLaunchKernelGGL(k_median<VEC>, dim3((unsigned)(j.R * j.G), (unsigned)j.W), dim3(256), 0, st,
+                       j.data, j.flags, j.med, j.WSd, j.WSf, j.RS, j.ES, j.seg_start, j.seg_len, j.R, j.G);
+}
+template <bool VEC, int UNR = MED2_UNROLL>
+static void median_two_pass(hipStream_t st, const MedianJob& j) {
+    hipLaunchKernelGGL((k_median2<VEC, false, UNR>), dim3((unsigned)(j.R * j.G), (unsigned)j.W), dim3(256), 0, st,
+                       j.data, j.flags, j.med, j.WSd, j.WSf, j.RS, j.ES, j.seg_start, j.seg_len, j.R, j.G, j.gcand, j.cand_ws, j.cand_cap);
+}
+
+// Launches kernel `k` on job `j` (the flagger's launch_median and the test hook tri_test_median); the caller checks the launch.
+// The wave kernels take MW_SPW (8 slots) / MW_SPW16 (16 slots) rows of a segment per wave, one segment with seg_per_wave.
+static void launch_median_kernel(hipStream_t st, MedianKernel k, bool seg_per_wave, const MedianJob& j) {
+    switch (k) {
+    case MedianKernel::Wave8: seg_per_wave ? median_wave<8, false, 1>(st, j) : median_wave<8, false, MW_SPW>(st, j); break;
+    case MedianKernel::Wave8Vec: seg_per_wave ? median_wave<8, true, 1>(st, j) : median_wave<8, true, MW_SPW>(st, j); break;
+    case MedianKernel::Wave16: seg_per_wave ? median_wave<MW_K, false, 1>(st, j) : median_wave<MW_K, false, MW_SPW16>(st, j); break;
+    case MedianKernel::Wave16Vec: seg_per_wave ? median_wave<MW_K, true, 1>(st, j) : median_wave<MW_K, true, MW_SPW16>(st, j); break;
+    case MedianKernel::Select: median_select<false>(st, j); break;
+    case MedianKernel::SelectVec: median_select<true>(st, j); break;
+    case MedianKernel::TwoPass: median_two_pass<false>(st, j); break;
+    case MedianKernel::TwoPassVec: median_two_pass<true>(st, j); break;
+    case MedianKernel::TwoPassVecLong: median_two_pass<true, 16>(st, j); break;
+    }
+}
+
+// The flagger's segmented medians: the kernel that fits the job, launched on the run's stream.
+int launch_median(const Run& r, MedianJob j) {
+    const int R = j.R, G = j.G;
+    const int64_t W = j.W, max_len = j.max_len;
     if ((int64_t)R * G <= 0 || W <= 0) return TRI_OK;
-    // (data / flags2 as column panels: only the 16-byte wave kernels read them -- see median_takes_panels())
-    if (panel_rows > 0 && !(ES == 1 && RS % 64 == 0 && rows_aligned && max_len + (segs_aligned ? 0 : 3) <= 64 * MW_K &&
-                            WSd % 4 == 0 && WSf % 4 == 0 && ((uintptr_t)data % 16 == 0) && ((uintptr_t)flags % 4 == 0)))
+    // (data / flags2 as column panels: only the 16-byte wave kernels read them)
+    if (j.panel_rows > 0 && !(j.ES == 1 && j.RS % 64 == 0 && j.rows_aligned && max_len + (j.segs_aligned ? 0 : 3) <= 64 * MW_K &&
+                              j.WSd % 4 == 0 && j.WSf % 4 == 0 && ((uintptr_t)j.data % 16 == 0) && ((uintptr_t)j.flags % 4 == 0)))
         return set_err(TRI_EUNSUPPORTED, "panel images need wave-sized segments of 64-column aligned rows");
     // (extra flag sources: the wave kernels only -- see median_takes_extra_flags())
-    if ((flags2 || colflags) && (max_len > 64 * MW_K || (colflags && ES != 1) || ((uintptr_t)flags2 % 4 != 0) ||
-                                 ((uintptr_t)colflags % 4 != 0) || WScol % 4 != 0))
+    if ((j.flags2 || j.colflags) && (max_len > 64 * MW_K || (j.colflags && j.ES != 1) || ((uintptr_t)j.flags2 % 4 != 0) ||
+                                     ((uintptr_t)j.colflags % 4 != 0) || j.WScol % 4 != 0))
         return set_err(TRI_EUNSUPPORTED, "extra flag sources need wave-sized segments of contiguous, 4-byte aligned rows");
     if ((int64_t)R * G > 0x7FFFFFFF || W > 65535) return set_err(TRI_EUNSUPPORTED, "median grid too large");
     // segments of contiguous 4-aligned rows can be loaded 16 bytes at a time
     // (misaligned segment ends are masked, costing up to 3 extra slots)
     // (the 16-byte wave kernels address a window's image through 32-bit buffer offsets: below 4 GB)
-    const bool row4 = ES == 1 && RS % 4 == 0 && WSd % 4 == 0 && WSf % 4 == 0 &&
-                      ((uintptr_t)data % 16 == 0) && ((uintptr_t)flags % 4 == 0) && rows_aligned &&
-                      (uint64_t)RS * (uint64_t)std::max(R, panel_rows) * 4u < (1ull << 32);
-    if (panel_rows > 0 && !row4) return set_err(TRI_EUNSUPPORTED, "panel images of 4 GB or more per window");
-    const int64_t slack = segs_aligned ? 0 : 3;   // misaligned segment starts cost up to 3 masked slots
+    const bool row4 = j.ES == 1 && j.RS % 4 == 0 && j.WSd % 4 == 0 && j.WSf % 4 == 0 &&
+                      ((uintptr_t)j.data % 16 == 0) && ((uintptr_t)j.flags % 4 == 0) && j.rows_aligned &&
+                      (uint64_t)j.RS * (uint64_t)std::max(R, j.panel_rows) * 4u < (1ull << 32);
+    if (j.panel_rows > 0 && !row4) return set_err(TRI_EUNSUPPORTED, "panel images of 4 GB or more per window");
+    const int64_t slack = j.segs_aligned ? 0 : 3;   // misaligned segment starts cost up to 3 masked slots
     // wave medians: MW_SPW rows of a segment per wave, the next row's loads in flight (round 4; TRI_MEDIAN_WAVE_OLD=1: one segment per wave)
     static const bool wave_old = [] { const char* e = getenv("TRI_MEDIAN_WAVE_OLD"); return e && e[0] == '1'; }();
-    if (max_len <= 64 * MW_K && !wave_old) {
-        if (max_len + slack <= 64 * 8 && row4)
-            hipLaunchKernelGGL((k_median_wave<8, true, MW_SPW>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                               data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol, panel_rows);
-        else if (max_len <= 64 * 8 && panel_rows == 0)               // (panel images: the 16-byte kernels only)
-            hipLaunchKernelGGL((k_median_wave<8, false, MW_SPW>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                               data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol);
-        else if (max_len + slack <= 64 * MW_K && row4)
-            hipLaunchKernelGGL((k_median_wave<MW_K, true, MW_SPW16>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW16) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                               data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol, panel_rows);
-        else if (max_len <= 64 * MW_K)
-            hipLaunchKernelGGL((k_median_wave<MW_K, false, MW_SPW16>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW16) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                               data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol);
-        LAUNCHCHK();
-        return TRI_OK;
-    }
-    if (max_len + slack <= 64 * 8 && row4)
-        hipLaunchKernelGGL((k_median_wave<8, true, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                           data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol, panel_rows);
-    else if (max_len <= 64 * 8 && panel_rows == 0)               // (panel images: the 16-byte kernels only)
-        hipLaunchKernelGGL((k_median_wave<8, false, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                           data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol);
-    else if (max_len + slack <= 64 * MW_K && row4)
-        hipLaunchKernelGGL((k_median_wave<MW_K, true, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                           data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol, panel_rows);
-    else if (max_len <= 64 * MW_K)
-        hipLaunchKernelGGL((k_median_wave<MW_K, false, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)W), dim3(256), 0, r.st,
-                           data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, flags2, colflags, WScol);
+    MedianKernel k;
+    if (max_len + slack <= 64 * 8 && row4) k = MedianKernel::Wave8Vec;
+    else if (max_len <= 64 * 8 && j.panel_rows == 0) k = MedianKernel::Wave8;     // (panel images: the 16-byte kernels only)
+    else if (max_len + slack <= 64 * MW_K && row4) k = MedianKernel::Wave16Vec;
+    else if (max_len <= 64 * MW_K) k = MedianKernel::Wave16;
     else {
         // long segments: two-pass select (K3c); TRI_MEDIAN_3PASS=1 keeps the three-pass kernel (A/B runs, tests)
         static const bool three = [] { const char* e = getenv("TRI_MEDIAN_3PASS"); return e && e[0] == '1'; }();
-        const dim3 grid((unsigned)(R * G), (unsigned)W);
-        if (three && vec_ok)
-            hipLaunchKernelGGL(k_median<true>, grid, dim3(256), 0, r.st, data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G);
-        else if (three)
-            hipLaunchKernelGGL(k_median<false>, grid, dim3(256), 0, r.st, data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G);
+        if (three) k = j.vec_ok ? MedianKernel::SelectVec : MedianKernel::Select;
         else {
             // scratch for the predicted-window candidates (K3c): one read of the segment instead of two
             static const bool no_predict = [] { const char* e = getenv("TRI_MEDIAN_NO_PREDICT"); return e && e[0] == '1'; }();
-            if (no_predict || cand_cap < max_len || cand_ws % 4 != 0 || cand_cap % 4 != 0 || ((uintptr_t)gcand % 16 != 0)) { gcand = nullptr; cand_ws = 0; cand_cap = 0; }
+            if (no_predict || j.cand_cap < max_len || j.cand_ws % 4 != 0 || j.cand_cap % 4 != 0 || ((uintptr_t)j.gcand % 16 != 0)) {
+                j.gcand = nullptr; j.cand_ws = 0; j.cand_cap = 0;
+            }
             // few, long segments (fewer workgroups than the machine holds at six per CU): sixteen 16-byte groups in flight per thread
-            if ((vec_ok || row4) && (int64_t)R * G * W < 1536 && max_len >= (int64_t)1 << 20)
-                hipLaunchKernelGGL((k_median2<true, false, 16>), grid, dim3(256), 0, r.st, data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, gcand, cand_ws, cand_cap);
-            else if (vec_ok || row4)
-                hipLaunchKernelGGL(k_median2<true>, grid, dim3(256), 0, r.st, data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, gcand, cand_ws, cand_cap);
-            else
-                hipLaunchKernelGGL(k_median2<false>, grid, dim3(256), 0, r.st, data, flags, med, WSd, WSf, RS, ES, seg_start, seg_len, R, G, gcand, cand_ws, cand_cap);
+            if ((j.vec_ok || row4) && (int64_t)R * G * W < 1536 && max_len >= (int64_t)1 << 20) k = MedianKernel::TwoPassVecLong;
+            else k = (j.vec_ok || row4) ? MedianKernel::TwoPassVec : MedianKernel::TwoPass;
         }
     }
+    launch_median_kernel(r.st, k, wave_old, j);
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -923,42 +952,58 @@ bool st_use_pipe(const StWin& sw) {
     return !off && sw.nw >= 1 && sw.nw <= 8 && stp_lds_bytes(sw) <= 160 * 1024;
 }
 
+// TRI_ST_NO_PANEL=1: the time-axis SumThreshold and whoever shares its images read plain rows, never column panels (A/B runs)
+static bool st_no_panel() { static const bool off = [] { const char* e = getenv("TRI_ST_NO_PANEL"); return e && e[0] == '1'; }(); return off; }
+
+static hipError_t st_pipe_optin() {
+    return lds_optin(reinterpret_cast<const void*>(&k_colst_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+// The SumThreshold kernels (kernels_sumthreshold.hpp): k_colst_dyn (any windows), k_colst_fused (register cascade),
+// k_colst_mask (lane-mask cascade) on rows or on 64-column panels, k_colst_pipe (up to eight windows, K7p)
+enum class StKernel { Dyn, Fused, Mask, MaskPanel, Pipe };
+
+// Launches SumThreshold kernel `k` over the [L][C] images of W windows, G line groups each (the flagger's launch_colst and
+// the measurement hook tri_bench_sumthreshold).  ring / acc: the scratch of k_colst_dyn.
+int st_launch(hipStream_t st, StKernel k, const StWin& sw, const float* data, const double* med, uint8_t* out,
+              const int64_t* d_chunk_ends, double thr_scale, int L, int C, int G, size_t ws_data, size_t ws_out, int64_t W,
+              double* ring, uint8_t* acc) {
+    int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
+    if (const char* e = getenv("TRI_ST_BLK")) { int b = atoi(e); if (b >= 64 && b <= ST_MAXBLK && C >= b) blk = b; }
+    const dim3 grid((unsigned)cdiv(C, blk), (unsigned)G, (unsigned)W);
+    StFusedArgs fa;
+    for (int j = 0; j < 4; j++) fa.tf[j] = sw.tf[j < sw.nw ? j : 0];
+    if (k == StKernel::MaskPanel)
+        hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8, true>), grid, dim3(blk), 0, st, data, med, out, d_chunk_ends, fa, thr_scale, L, C, G, ws_data, ws_out);
+    else if (k == StKernel::Mask)
+        hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, med, out, d_chunk_ends, fa, thr_scale, L, C, G, ws_data, ws_out);
+    else if (k == StKernel::Fused)
+        hipLaunchKernelGGL((k_colst_fused<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, med, out, d_chunk_ends, fa, thr_scale, L, C, G, ws_data, ws_out);
+    else if (k == StKernel::Pipe) {
+        HIPCHK(st_pipe_optin());
+        hipLaunchKernelGGL(k_colst_pipe, dim3((unsigned)cdiv(C, 64), (unsigned)G, (unsigned)W), dim3(64 * sw.nw), stp_lds_bytes(sw), st,
+                           data, med, out, d_chunk_ends, sw, stp_plan(sw), thr_scale, L, C, G, ws_data, ws_out);
+    } else
+        hipLaunchKernelGGL(k_colst_dyn, grid, dim3(blk), 0, st, data, med, out, ring, acc, d_chunk_ends, sw, thr_scale, L, C, G, ws_data, ws_out);
+    LAUNCHCHK();
+    return TRI_OK;
+}
+
 int launch_colst(const Run& r, const StWin& sw, const float* data, const double* med,
                  uint8_t* out, const int64_t* d_chunk_ends, int L, int C, int G, size_t ws_data,
                  size_t ws_out, int64_t W, bool panel = false) {
-    double thr_scale = r.p->outlier_nsigma * TRI_MAD_NORMAL;  // flagging.py:623
-    int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-    if (const char* e = getenv("TRI_ST_BLK")) { int b = atoi(e); if (b >= 64 && b <= ST_MAXBLK && C >= b) blk = b; }
-    dim3 grid((unsigned)cdiv(C, blk), (unsigned)G, (unsigned)W);
+    StKernel k;
     if (st_use_fused(sw)) {
-        StFusedArgs fa;
-        for (int j = 0; j < 4; j++) fa.tf[j] = sw.tf[j];
         if (panel && !(st_use_mask(L, C) && C % 64 == 0)) return set_err(TRI_EUNSUPPORTED, "panel images: lane-mask SumThreshold kernel on 64-column panels only");
-        if (panel)
-            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8, true>), grid, dim3(blk), 0, r.st, data, med, out,
-                               d_chunk_ends, fa, thr_scale, L, C, G, ws_data, ws_out);
-        else if (st_use_mask(L, C))
-            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8>), grid, dim3(blk), 0, r.st, data, med, out,
-                               d_chunk_ends, fa, thr_scale, L, C, G, ws_data, ws_out);
-        else
-            hipLaunchKernelGGL((k_colst_fused<1, 2, 4, 8>), grid, dim3(blk), 0, r.st, data, med, out,
-                               d_chunk_ends, fa, thr_scale, L, C, G, ws_data, ws_out);
+        k = panel ? StKernel::MaskPanel : (st_use_mask(L, C) ? StKernel::Mask : StKernel::Fused);
     } else if (panel) {
         return set_err(TRI_EUNSUPPORTED, "panel images: windows (1, 2, 4, 8) only");
-    } else if (st_use_pipe(sw)) {
-        // any list of up to eight windows: one window per wave, lagging twin accumulators (K7p)
-        const hipError_t attr = lds_optin(reinterpret_cast<const void*>(&k_colst_pipe),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        HIPCHK(attr);
-        dim3 gridp((unsigned)cdiv(C, 64), (unsigned)G, (unsigned)W);
-        hipLaunchKernelGGL(k_colst_pipe, gridp, dim3(64 * sw.nw), stp_lds_bytes(sw), r.st, data, med, out, d_chunk_ends, sw,
-                           stp_plan(sw), thr_scale, L, C, G, ws_data, ws_out);
     } else {
-        hipLaunchKernelGGL(k_colst_dyn, grid, dim3(blk), 0, r.st, data, med, out, r.ws.ring, r.ws.acc,
-                           d_chunk_ends, sw, thr_scale, L, C, G, ws_data, ws_out);
+        // any list of up to eight windows: one window per wave, lagging twin accumulators (K7p)
+        k = st_use_pipe(sw) ? StKernel::Pipe : StKernel::Dyn;
     }
-    LAUNCHCHK();
-    return TRI_OK;
+    const double thr_scale = r.p->outlier_nsigma * TRI_MAD_NORMAL;  // flagging.py:623
+    return st_launch(r.st, k, sw, data, med, out, d_chunk_ends, thr_scale, L, C, G, ws_data, ws_out, W, r.ws.ring, r.ws.acc);
 }
 
 // _linearly_interpolate_nans1d along the line axis of [L][C] images (K6 / K6p)
@@ -1336,8 +1381,11 @@ int spectrum_medians(const Run& r, const float* img, const uint8_t* flg) {
     if (rc) return rc;
     bool seg4 = Fa % 4 == 0;
     for (int64_t g = 0; g < pl.G + 1 && seg4; g++) seg4 = r.p->chunk_ends[g] % 4 == 0;
-    return launch_median(r, ws.srowsf, ws.srowsu, ws.smed, 0, 0, (size_t)Fa, 1, ws.segC_start, ws.segC_len, Wn, G, 1, pl.maxchunk,
-                         seg4, Fa % 4 == 0, seg4);
+    MedianJob j;
+    j.data = ws.srowsf; j.flags = ws.srowsu; j.med = ws.smed; j.RS = (size_t)Fa;
+    j.seg_start = ws.segC_start; j.seg_len = ws.segC_len; j.R = Wn; j.G = G; j.W = 1; j.max_len = pl.maxchunk;
+    j.vec_ok = j.segs_aligned = seg4; j.rows_aligned = Fa % 4 == 0;
+    return launch_median(r, j);
 }
 
 int spectrum_background(const Run& r) {
@@ -1552,6 +1600,7 @@ int background2d(const Run& r, bool flagsFT_current) {
                     unsigned* gc = reinterpret_cast<unsigned*>(ws.Aw);          // the weight rows are dead: candidate scratch
                     unsigned cap = (unsigned)(std::min<size_t>((wsA / 2) / (size_t)G, 0x7fffffffu) & ~(size_t)3);
                     if (no_predict || (int64_t)cap < pl.maxchunk * pl.T || wsA % 4 != 0) { gc = nullptr; cap = 0; }
+                    // (not through launch_median_kernel: a block of rows with TF4 flag words, not row segments)
                     hipLaunchKernelGGL((k_median2<false, true>), dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Ao,
                                        (const uint8_t*)ws.bgfTF, ws.med, wsA, N, (size_t)0, (size_t)1, ws.segC_start, ws.segC_len, 1, G,
                                        gc, gc ? wsA : (size_t)0, cap, T / 4, Fa);
@@ -1650,9 +1699,13 @@ int background2d(const Run& r, bool flagsFT_current) {
             }
             // block medians over (all times) x (chunk channels): contiguous in FT
             // (the time stage's images in ws.Aw / ws.Ao are dead here: candidate scratch, wsA / G keys per block)
-            rc = launch_median(r, ws.Bo, cur_ft, ws.med, wsB, N, 0, 1, ws.segB_start, ws.segB_len, 1, G, W, pl.maxchunk * pl.T,
-                               T % 4 == 0 && wsB % 4 == 0 && N % 4 == 0, false, false,
-                               reinterpret_cast<unsigned*>(ws.Aw), wsA, (unsigned)(std::min<size_t>(wsA / (size_t)G, 0x7fffffffu) & ~(size_t)3));
+            MedianJob j;
+            j.data = ws.Bo; j.flags = cur_ft; j.med = ws.med; j.WSd = wsB; j.WSf = N;
+            j.seg_start = ws.segB_start; j.seg_len = ws.segB_len; j.R = 1; j.G = G; j.W = W; j.max_len = pl.maxchunk * pl.T;
+            j.vec_ok = T % 4 == 0 && wsB % 4 == 0 && N % 4 == 0;
+            j.gcand = reinterpret_cast<unsigned*>(ws.Aw); j.cand_ws = wsA;
+            j.cand_cap = (unsigned)(std::min<size_t>(wsA / (size_t)G, 0x7fffffffu) & ~(size_t)3);
+            rc = launch_median(r, j);
             if (rc) return rc;
             if (r.pl.vec && wsB % 4 == 0 && packed && !no_fuse) {
                 // rejection + TF4 re-pack of the flags in one pass
@@ -1724,7 +1777,14 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     }
 
     // flagging.py:944  _time_median: rows of the FT layout are contiguous in time
-    rc = launch_median(r, ws.dataFT, ws.flagsFT, ws.med, N, N, (size_t)T, 1, ws.segT_start, ws.segT_len, Fa, 1, W, pl.T, false, T % 4 == 0, true);
+    auto time_medians = [&](const float* dataFT, size_t ws_data) {
+        MedianJob j;
+        j.data = dataFT; j.flags = ws.flagsFT; j.med = ws.med; j.WSd = ws_data; j.WSf = N; j.RS = (size_t)T;
+        j.seg_start = ws.segT_start; j.seg_len = ws.segT_len; j.R = Fa; j.G = 1; j.W = W; j.max_len = pl.T;
+        j.rows_aligned = T % 4 == 0; j.segs_aligned = true;
+        return launch_median(r, j);
+    };
+    rc = time_medians(ws.dataFT, N);
     if (rc) return rc;
     hipLaunchKernelGGL(k_spec_from_med, dim3((unsigned)cdiv((size_t)Fa * Wn, 256)), dim3(256), 0, r.st, ws.med, ws.sdata, ws.sflags, Fa, Wn);
     LAUNCHCHK();
@@ -1776,10 +1836,9 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     // column kernel's row walk is one linear stream.  Who else touches the two images reads panels too: the frequency-axis MAD
     // (wave medians over row segments: an aligned group of four channels is contiguous either way) and the fused combine /
     // dilate pass.  Only on the route where exactly those kernels run (TRI_ST_NO_PANEL=1: plain rows everywhere).
-    static const bool no_panel = [] { const char* e = getenv("TRI_ST_NO_PANEL"); return e && e[0] == '1'; }();
     static const bool no_fused_or_p = [] { const char* e = getenv("TRI_NO_FUSED_OR"); return e && e[0] == '1'; }();
     static const bool no_fdil_p = [] { const char* e = getenv("TRI_NO_FUSED_DILATE"); return e && e[0] == '1'; }();
-    const bool panel_t = !no_panel && defer_tf && !no_fused_or_p && !no_fdil_p && Fa % 64 == 0 && Fa == F &&
+    const bool panel_t = !st_no_panel() && defer_tf && !no_fused_or_p && !no_fdil_p && Fa % 64 == 0 && Fa == F &&
                          median_takes_extra_flags(pl.maxchunk + 3) && st_use_fused(pl.swT) && st_use_mask(T, Fa) &&
                          [&] { int64_t e = p->freq_extend; int64_t h = e >= 0 ? e / 2 : -((-e + 1) / 2); return -h == -1 && -h + e == 2; }();
     rc = launch_transpose<float>(r, residFT, residTF, Fa, T, wsB, N, W, 0.0f, panel_t);
@@ -1791,7 +1850,7 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
         rc = launch_transpose<uint8_t>(r, ws.flagsTF, ws.flagsFT, T, Fa, N, N, W);
         if (rc) return rc;
     }
-    rc = launch_median(r, residFT, ws.flagsFT, ws.med, wsB, N, (size_t)T, 1, ws.segT_start, ws.segT_len, Fa, 1, W, pl.T, false, T % 4 == 0, true);
+    rc = time_medians(residFT, wsB);
     if (rc) return rc;
     rc = launch_colst(r, pl.swT, residTF, ws.med, ws.tflTF, ws.d_tends, T, Fa, 1, N, N, W, panel_t);
     if (rc) return rc;
@@ -1801,9 +1860,13 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     // (the union is read by this MAD only -- the next major iteration rebuilds the TF flags -- so when the chunk medians are
     //  wave medians they take the three sources as they are and no pass writes the union; TRI_NO_FUSED_OR=1: the pass)
     static const bool no_fused_or = [] { const char* e = getenv("TRI_NO_FUSED_OR"); return e && e[0] == '1'; }();
+    MedianJob cj;
+    cj.data = residTF; cj.flags = ws.flagsTF; cj.med = ws.med; cj.WSd = cj.WSf = N; cj.RS = (size_t)Fa;
+    cj.seg_start = ws.segC_start; cj.seg_len = ws.segC_len; cj.R = T; cj.G = G; cj.W = W; cj.max_len = pl.maxchunk;
+    cj.rows_aligned = Fa % 4 == 0;
     if (defer_tf && !no_fused_or && median_takes_extra_flags(pl.maxchunk) && Fa % 4 == 0) {
-        rc = launch_median(r, residTF, ws.flagsTF, ws.med, N, N, (size_t)Fa, 1, ws.segC_start, ws.segC_len, T, G, W, pl.maxchunk, false, Fa % 4 == 0,
-                           false, nullptr, 0, 0, ws.tflTF, ws.srows, (size_t)Fa, panel_t ? T : 0);
+        cj.flags2 = ws.tflTF; cj.colflags = ws.srows; cj.WScol = (size_t)Fa; cj.panel_rows = panel_t ? T : 0;
+        rc = launch_median(r, cj);
         if (rc) return rc;
     } else {
         if (panel_t) return set_err(TRI_EUNSUPPORTED, "internal: panel images on a route that reads rows");
@@ -1814,7 +1877,7 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
             rc = launch_u8<1>(r, ws.tflTF, ws.flagsTF, N, N, N, W);
             if (rc) return rc;
         }
-        rc = launch_median(r, residTF, ws.flagsTF, ws.med, N, N, (size_t)Fa, 1, ws.segC_start, ws.segC_len, T, G, W, pl.maxchunk, false, Fa % 4 == 0);
+        rc = launch_median(r, cj);
         if (rc) return rc;
     }
     rc = launch_colst(r, pl.swF, residFT, ws.med, ws.fflFT, ws.d_chunk_ends, Fa, T, G, wsB, N, W);
@@ -2331,13 +2394,12 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
         return set_err(TRI_EUNSUPPORTED, "lane-mask cascade needs a window below 2^31 bytes");
     // variant 5 (round 4): the lane-mask cascade on COLUMN PANELS, as the flagger's time-axis pass runs it -- the row images
     // handed in are re-laid out before the timed region and the flags taken back to rows after it
-    static const bool no_panel = [] { const char* e = getenv("TRI_ST_NO_PANEL"); return e && e[0] == '1'; }();
     if (variant == 5 && !(can_fuse && C % 64 == 0 && (uint64_t)L * (uint64_t)C * 4u < (1ull << 31)))
         return set_err(TRI_EUNSUPPORTED, "panel SumThreshold: windows (1,2,4,8), a multiple of 64 columns, a window below 2^31 bytes");
-    if (variant == 0 && can_fuse) variant = st_use_mask(L, C) ? ((C % 64 == 0 && !no_panel) ? 5 : 3) : 2;
+    if (variant == 0 && can_fuse) variant = st_use_mask(L, C) ? ((C % 64 == 0 && !st_no_panel()) ? 5 : 3) : 2;
     if (variant == 4) {
         if (sw.nw > 8 || stp_lds_bytes(sw) > 160 * 1024) return set_err(TRI_EUNSUPPORTED, "stage pipeline: more than eight windows, or the flag ring does not fit LDS");
-        HIPCHK(lds_optin(reinterpret_cast<const void*>(&k_colst_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(st_pipe_optin());
     }
     DevBuf<double> ring;
     DevBuf<uint8_t> acc;
@@ -2351,9 +2413,6 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     HipEvent e0, e1;
     HIPCHK(hipEventCreate(e0.out()));
     HIPCHK(hipEventCreate(e1.out()));
-    int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-    if (const char* e = getenv("TRI_ST_BLK")) { int b = atoi(e); if (b >= 64 && b <= ST_MAXBLK && C >= b) blk = b; }
-    dim3 grid((unsigned)cdiv(C, blk), 1, (unsigned)n_win);
     size_t ws = (size_t)n_line * n_col;
     DevBuf<float> pdata;
     DevBuf<uint8_t> pout;
@@ -2366,22 +2425,14 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
         }
         LAUNCHCHK();
     }
-    bool fused = variant == 2;
-    StFusedArgs fa;
-    for (int j = 0; j < 4; j++) fa.tf[j] = sw.tf[j < sw.nw ? j : 0];
+    const StKernel k = variant == 5 ? StKernel::MaskPanel : variant == 3 ? StKernel::Mask : variant == 2 ? StKernel::Fused :
+                       variant == 4 ? StKernel::Pipe : StKernel::Dyn;
+    const float* kdata = variant == 5 ? (const float*)pdata.get() : data;
+    uint8_t* kout = variant == 5 ? pout.get() : out;
     HIPCHK(hipEventRecord(e0.get(), st));
     for (int i = 0; i < repeats; i++) {
-        if (variant == 5)
-            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8, true>), grid, dim3(blk), 0, st, (const float*)pdata.get(), mad, pout.get(), d_ends.get(), fa, thr_scale, L, C, 1, ws, ws);
-        else if (variant == 3)
-            hipLaunchKernelGGL((k_colst_mask<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, mad, out, d_ends.get(), fa, thr_scale, L, C, 1, ws, ws);
-        else if (fused)
-            hipLaunchKernelGGL((k_colst_fused<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, mad, out, d_ends.get(), fa, thr_scale, L, C, 1, ws, ws);
-        else if (variant == 4)
-            hipLaunchKernelGGL(k_colst_pipe, dim3((unsigned)cdiv(C, 64), 1, (unsigned)n_win), dim3(64 * sw.nw), stp_lds_bytes(sw), st,
-                               data, mad, out, d_ends.get(), sw, stp_plan(sw), thr_scale, L, C, 1, ws, ws);
-        else
-            hipLaunchKernelGGL(k_colst_dyn, grid, dim3(blk), 0, st, data, mad, out, ring.get(), acc.get(), d_ends.get(), sw, thr_scale, L, C, 1, ws, ws);
+        rc = st_launch(st, k, sw, kdata, mad, kout, d_ends.get(), thr_scale, L, C, 1, ws, ws, n_win, ring.get(), acc.get());
+        if (rc) return rc;
     }
     HIPCHK(hipEventRecord(e1.get(), st));
     HIPCHK(hipEventSynchronize(e1.get()));
@@ -2632,8 +2683,6 @@ extern "C" int tri_test_median(const float* data, const uint8_t* flags, double* 
     DevBuf<int64_t> d_start_b, d_len_b;
     HIPCHK(d_start_b.alloc(G));
     HIPCHK(d_len_b.alloc(G));
-    const int64_t* d_start = d_start_b.get();
-    const int64_t* d_len = d_len_b.get();
     HIPCHK(hipMemcpy(d_start_b.get(), start.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_len_b.get(), len.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
     size_t WS = (size_t)rows * row_len, RS = (size_t)row_len;
@@ -2660,64 +2709,36 @@ extern "C" int tri_test_median(const float* data, const uint8_t* flags, double* 
     if (variant == 4 && (row_len % 4 != 0 || maxlen + 3 > 64 * MW_K)) return set_err(TRI_EINVAL, "masked vector variant needs row_len % 4 == 0 and segments <= 1021");
     if ((uint64_t)rows * (uint64_t)row_len * 4u >= (1ull << 32) && (variant == 4 || variant == 1)) return set_err(TRI_EUNSUPPORTED, "wave kernels: a window below 4 GB");
     if ((variant == 3 || variant == 5) && !al4) return set_err(TRI_EINVAL, "vector loads need 4-aligned segments");
-    if (wave_old && variant == 1 && maxlen <= 64 * 8)
-        hipLaunchKernelGGL((k_median_wave<8, false, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (wave_old && variant == 4 && row_len % 4 == 0 && maxlen + 3 <= 64 * 8)
-        hipLaunchKernelGGL((k_median_wave<8, true, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (wave_old && ((variant == 4 && row_len % 4 == 0 && maxlen + 3 <= 64 * MW_K) ||
-             (variant == 1 && G == 1 && al4 && seg_ends[0] == 0 && seg_ends[1] == row_len)))
-        hipLaunchKernelGGL((k_median_wave<MW_K, true, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (wave_old && variant == 1)
-        hipLaunchKernelGGL((k_median_wave<MW_K, false, 1>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, 1) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (variant == 1 && maxlen <= 64 * 8)
-        hipLaunchKernelGGL((k_median_wave<8, false, MW_SPW>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (variant == 4 && row_len % 4 == 0 && maxlen + 3 <= 64 * 8)
-        hipLaunchKernelGGL((k_median_wave<8, true, MW_SPW>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if ((variant == 4 && row_len % 4 == 0 && maxlen + 3 <= 64 * MW_K) ||
-             (variant == 1 && G == 1 && al4 && seg_ends[0] == 0 && seg_ends[1] == row_len))
-        hipLaunchKernelGGL((k_median_wave<MW_K, true, MW_SPW16>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW16) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (variant == 1)
-        hipLaunchKernelGGL((k_median_wave<MW_K, false, MW_SPW16>), dim3((unsigned)cdiv((int64_t)cdiv((int64_t)R, MW_SPW16) * G, 4), (unsigned)n_win), dim3(256), 0, st,
-                           data, flags, med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (variant == 3)
-        hipLaunchKernelGGL(k_median<true>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                           med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else if (variant == 5)
-        hipLaunchKernelGGL(k_median2<true>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                           med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
+    MedianJob j;
+    j.data = data; j.flags = flags; j.med = med; j.WSd = j.WSf = WS; j.RS = RS;
+    j.seg_start = d_start_b.get(); j.seg_len = d_len_b.get(); j.R = R; j.G = G; j.W = n_win; j.max_len = maxlen;
+    const bool full_row = G == 1 && al4 && seg_ends[0] == 0 && seg_ends[1] == row_len;
+    MedianKernel k = MedianKernel::Select;
+    DevBuf<unsigned> gc;
+    if (variant == 1 && maxlen <= 64 * 8) k = MedianKernel::Wave8;
+    else if (variant == 4 && row_len % 4 == 0 && maxlen + 3 <= 64 * 8) k = MedianKernel::Wave8Vec;
+    else if ((variant == 4 && row_len % 4 == 0 && maxlen + 3 <= 64 * MW_K) || (variant == 1 && full_row)) k = MedianKernel::Wave16Vec;
+    else if (variant == 1) k = MedianKernel::Wave16;
+    else if (variant == 3) k = MedianKernel::SelectVec;
+    else if (variant == 5) k = MedianKernel::TwoPassVec;
     else if (variant == 9 || variant == 10) {
         // K3c with the predicted-window candidates in global scratch (9: vector loads, 10: scalar)
         if (variant == 9 && row_len % 4 != 0) return set_err(TRI_EINVAL, "variant 9 needs row_len % 4 == 0");
-        DevBuf<unsigned> gc;
         const size_t cap = ((size_t)maxlen + 3) & ~(size_t)3, per_win = cap * (size_t)R * G;
         HIPCHK(gc.alloc(per_win * (size_t)n_win));
-        if (variant == 9)
-            hipLaunchKernelGGL(k_median2<true>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                               med, WS, WS, RS, (size_t)1, d_start, d_len, R, G, gc.get(), per_win, (unsigned)cap);
-        else
-            hipLaunchKernelGGL(k_median2<false>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                               med, WS, WS, RS, (size_t)1, d_start, d_len, R, G, gc.get(), per_win, (unsigned)cap);
+        j.gcand = gc.get(); j.cand_ws = per_win; j.cand_cap = (unsigned)cap;
+        k = variant == 9 ? MedianKernel::TwoPassVec : MedianKernel::TwoPass;
+    } else if (variant == 7) {
+        if (row_len % 4 != 0) return set_err(TRI_EINVAL, "variant 7 needs row_len % 4 == 0");
+        k = MedianKernel::TwoPassVec;
+    } else if (variant == 6) k = MedianKernel::TwoPass;
+    launch_median_kernel(st, k, wave_old, j);
+    if (variant == 9 || variant == 10) {
         hipError_t le = hipGetLastError();
         hipError_t se = hipStreamSynchronize(st);
         if (le != hipSuccess || se != hipSuccess) return set_err(TRI_EHIP, "median variant %d failed", variant);
         return TRI_OK;
-    } else if (variant == 7) {
-        if (row_len % 4 != 0) return set_err(TRI_EINVAL, "variant 7 needs row_len % 4 == 0");
-        hipLaunchKernelGGL(k_median2<true>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                           med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    } else if (variant == 6)
-        hipLaunchKernelGGL(k_median2<false>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                           med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
-    else
-        hipLaunchKernelGGL(k_median<false>, dim3((unsigned)(R * G), (unsigned)n_win), dim3(256), 0, st, data, flags,
-                           med, WS, WS, RS, (size_t)1, d_start, d_len, R, G);
+    }
     LAUNCHCHK();
     HIPCHK(hipStreamSynchronize(st));
     return TRI_OK;
