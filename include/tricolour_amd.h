@@ -201,6 +201,36 @@ int tri_unpack_scan(const uint8_t *flag_windows,
                     int64_t nbl, int64_t ntime, uint8_t *out_flags, void *stream);
 
 /*
+ * tri_pack_scan for a list of n rows, one baseline chunk of a scan at a time:
+ * entry i reads source row src_row[i] (NULL: row i, a compact slab) of the
+ * (src_rows, nchan, ncorr) data, model (optional) and flags (optional) and
+ * scatters it to cell (row_bl[i], row_time[i]) of the (nbl, wcorr, ntime,
+ * nchan) windows with tri_pack_scan's arithmetic.  Entries whose source row
+ * is outside [0, src_rows) or whose cell is outside the windows are skipped.
+ * Only the list is launched.  Initialise the windows with tri_fill_windows.
+ */
+int tri_pack_scan_rows(const void *data_c64, const void *model_c64, const uint8_t *flag,
+                       const int64_t *src_row, int64_t src_rows,
+                       const int32_t *row_bl, const int32_t *row_time,
+                       int64_t n, int64_t nchan, int64_t ncorr,
+                       int64_t nbl, int64_t ntime, int mode,
+                       const int32_t *pol_idx, const double *pol_alpha, int64_t n_pol,
+                       void *vis_windows_c64, uint8_t *flag_windows, void *stream);
+
+/*
+ * tri_unpack_scan for a list of n rows: entry i writes destination row
+ * dst_row[i] (NULL: row i) of the (out_rows, nchan, out_ncorr) flags from
+ * cell (row_bl[i], row_time[i]) of the flag windows (0 if the cell is
+ * outside them).  Entries whose destination is outside [0, out_rows) are
+ * skipped; rows not in the list are never written.
+ */
+int tri_unpack_scan_rows(const uint8_t *flag_windows,
+                         const int64_t *dst_row, int64_t out_rows,
+                         const int32_t *row_bl, const int32_t *row_time,
+                         int64_t n, int64_t nchan, int64_t wcorr, int64_t out_ncorr,
+                         int64_t nbl, int64_t ntime, uint8_t *out_flags, void *stream);
+
+/*
  * Replaces tricolour.stokes.polarised_intensity (stokes.py:157-209, mode 0)
  * and unpolarised_intensity (stokes.py:79-153, mode 1) on (row, chan, corr)
  * visibilities, n = row * chan samples:

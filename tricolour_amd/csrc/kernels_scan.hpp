@@ -2,6 +2,8 @@
 // (apps/tricolour/app.py:389-457 and :475-480) fused into one pass each way:
 //   k_pack_scan    residual (data - model), Stokes intensity, any-over-corr flags, scatter into windows
 //   k_unpack_scan  gather of the flag windows, any over the window correlations, broadcast to the MS's ncorr
+// and their row-list variants (k_pack_scan_rows*, k_unpack_scan_rows), which run one baseline chunk of a scan through
+// the same per-sample code
 #pragma once
 
 // ---------------------------------------------------------------------------
@@ -59,18 +61,13 @@ __device__ __forceinline__ void load_flags(const uint8_t* __restrict__ p, uint8_
     }
 }
 
-// NC = 1, 2 or 4 with 16-byte aligned rows.  grid (ceil(nchan / 256), rows of the slab)
+// One sample of the fused pack: the NC correlations at data / model / flag + i go to cell (bl, t, f) of the
+// (nbl, wcorr, ntime, nchan) windows.  Shared by the whole-scan kernel and the row-list kernel.
 template <int NC, bool STOKES, bool MODEL, bool FLAGS>
-__global__ void __launch_bounds__(256) k_pack_scan_v(const float2* __restrict__ data, const float2* __restrict__ model,
-                                                     const uint8_t* __restrict__ flag, const int32_t* __restrict__ row_bl,
-                                                     const int32_t* __restrict__ row_time, int nchan, int nbl, int ntime,
-                                                     StokesTerms terms, float2* __restrict__ vw, uint8_t* __restrict__ fw) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t r = blockIdx.y;
-    if (f >= nchan) return;
-    const int bl = row_bl[r], t = row_time[r];
-    if (bl < 0 || bl >= nbl || t < 0 || t >= ntime) return;
-    const size_t i = (r * nchan + f) * (size_t)NC;
+__device__ __forceinline__ void pack_scan_sample_v(const float2* __restrict__ data, const float2* __restrict__ model,
+                                                   const uint8_t* __restrict__ flag, size_t i, int bl, int t, int f,
+                                                   int nchan, int ntime, const StokesTerms& terms,
+                                                   float2* __restrict__ vw, uint8_t* __restrict__ fw) {
     float2 v[NC];
     load_corrs<NC>(data + i, v);
     if (MODEL) {
@@ -107,18 +104,46 @@ __global__ void __launch_bounds__(256) k_pack_scan_v(const float2* __restrict__ 
     }
 }
 
-// any ncorr / alignment: correlations read one at a time
-__global__ void __launch_bounds__(256) k_pack_scan(const float2* __restrict__ data, const float2* __restrict__ model,
-                                                   const uint8_t* __restrict__ flag, const int32_t* __restrict__ row_bl,
-                                                   const int32_t* __restrict__ row_time, int nchan, int ncorr, int nbl,
-                                                   int ntime, int stokes, StokesTerms terms, float2* __restrict__ vw,
-                                                   uint8_t* __restrict__ fw) {
+// NC = 1, 2 or 4 with 16-byte aligned rows.  grid (ceil(nchan / 256), rows of the slab)
+template <int NC, bool STOKES, bool MODEL, bool FLAGS>
+__global__ void __launch_bounds__(256) k_pack_scan_v(const float2* __restrict__ data, const float2* __restrict__ model,
+                                                     const uint8_t* __restrict__ flag, const int32_t* __restrict__ row_bl,
+                                                     const int32_t* __restrict__ row_time, int nchan, int nbl, int ntime,
+                                                     StokesTerms terms, float2* __restrict__ vw, uint8_t* __restrict__ fw) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     const size_t r = blockIdx.y;
     if (f >= nchan) return;
     const int bl = row_bl[r], t = row_time[r];
     if (bl < 0 || bl >= nbl || t < 0 || t >= ntime) return;
-    const size_t i = (r * nchan + f) * (size_t)ncorr;
+    pack_scan_sample_v<NC, STOKES, MODEL, FLAGS>(data, model, flag, (r * nchan + f) * (size_t)NC, bl, t, f, nchan, ntime,
+                                                 terms, vw, fw);
+}
+
+// Row-list variant: entry e = e0 + blockIdx.y of a list reads source row src_row[e] (nullptr: e) of a
+// (src_rows, nchan, NC) slab and scatters it to (row_bl[e], row_time[e]) of the windows.  The grid covers the list
+// only: a baseline chunk of a scan launches its own rows, not every row of the scan.
+template <int NC, bool STOKES, bool MODEL, bool FLAGS>
+__global__ void __launch_bounds__(256) k_pack_scan_rows_v(const float2* __restrict__ data, const float2* __restrict__ model,
+                                                          const uint8_t* __restrict__ flag, const int64_t* __restrict__ src_row,
+                                                          int64_t src_rows, const int32_t* __restrict__ row_bl,
+                                                          const int32_t* __restrict__ row_time, int64_t e0, int nchan,
+                                                          int nbl, int ntime, StokesTerms terms, float2* __restrict__ vw,
+                                                          uint8_t* __restrict__ fw) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = e0 + blockIdx.y;
+    if (f >= nchan) return;
+    const int64_t r = src_row ? src_row[e] : e;
+    const int bl = row_bl[e], t = row_time[e];
+    if (r < 0 || r >= src_rows || bl < 0 || bl >= nbl || t < 0 || t >= ntime) return;
+    pack_scan_sample_v<NC, STOKES, MODEL, FLAGS>(data, model, flag, ((size_t)r * nchan + f) * (size_t)NC, bl, t, f, nchan,
+                                                 ntime, terms, vw, fw);
+}
+
+// any ncorr / alignment: correlations read one at a time
+__device__ __forceinline__ void pack_scan_sample(const float2* __restrict__ data, const float2* __restrict__ model,
+                                                 const uint8_t* __restrict__ flag, size_t i, int bl, int t, int f,
+                                                 int nchan, int ncorr, int ntime, int stokes, const StokesTerms& terms,
+                                                 float2* __restrict__ vw, uint8_t* __restrict__ fw) {
     auto resid = [&](int c) {
         const float2 d = data[i + c];
         if (!model) return d;
@@ -145,11 +170,56 @@ __global__ void __launch_bounds__(256) k_pack_scan(const float2* __restrict__ da
     }
 }
 
+__global__ void __launch_bounds__(256) k_pack_scan(const float2* __restrict__ data, const float2* __restrict__ model,
+                                                   const uint8_t* __restrict__ flag, const int32_t* __restrict__ row_bl,
+                                                   const int32_t* __restrict__ row_time, int nchan, int ncorr, int nbl,
+                                                   int ntime, int stokes, StokesTerms terms, float2* __restrict__ vw,
+                                                   uint8_t* __restrict__ fw) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t r = blockIdx.y;
+    if (f >= nchan) return;
+    const int bl = row_bl[r], t = row_time[r];
+    if (bl < 0 || bl >= nbl || t < 0 || t >= ntime) return;
+    pack_scan_sample(data, model, flag, (r * nchan + f) * (size_t)ncorr, bl, t, f, nchan, ncorr, ntime, stokes, terms,
+                     vw, fw);
+}
+
+__global__ void __launch_bounds__(256) k_pack_scan_rows(const float2* __restrict__ data, const float2* __restrict__ model,
+                                                        const uint8_t* __restrict__ flag, const int64_t* __restrict__ src_row,
+                                                        int64_t src_rows, const int32_t* __restrict__ row_bl,
+                                                        const int32_t* __restrict__ row_time, int64_t e0, int nchan,
+                                                        int ncorr, int nbl, int ntime, int stokes, StokesTerms terms,
+                                                        float2* __restrict__ vw, uint8_t* __restrict__ fw) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = e0 + blockIdx.y;
+    if (f >= nchan) return;
+    const int64_t r = src_row ? src_row[e] : e;
+    const int bl = row_bl[e], t = row_time[e];
+    if (r < 0 || r >= src_rows || bl < 0 || bl >= nbl || t < 0 || t >= ntime) return;
+    pack_scan_sample(data, model, flag, ((size_t)r * nchan + f) * (size_t)ncorr, bl, t, f, nchan, ncorr, ntime, stokes,
+                     terms, vw, fw);
+}
+
 // ---------------------------------------------------------------------------
 // Broadcast unpack.  One thread per (row, chan): any over the wcorr window correlations of the cell (each a
 // load contiguous along chan across the wave), written to all OC output correlations (one OC-byte word).
 // OC = 4: vector store; OC = 0: runtime out_ncorr.  Rows of no baseline get 0.
 // ---------------------------------------------------------------------------
+template <int OC>
+__device__ __forceinline__ void unpack_scan_sample(const uint8_t* __restrict__ fw, int bl, int t, int f, int nchan,
+                                                   int wcorr, int out_ncorr, int nbl, int ntime,
+                                                   uint8_t* __restrict__ out_row) {
+    uint8_t any = 0;
+    if (!(bl < 0 || bl >= nbl || t < 0 || t >= ntime))
+        for (int c = 0; c < wcorr; c++) any |= fw[(((size_t)bl * wcorr + c) * ntime + t) * (size_t)nchan + f];
+    any = any ? 1 : 0;
+    if (OC == 4) {
+        *reinterpret_cast<uchar4*>(out_row + (size_t)f * 4) = make_uchar4(any, any, any, any);
+    } else {
+        for (int c = 0; c < out_ncorr; c++) out_row[(size_t)f * out_ncorr + c] = any;
+    }
+}
+
 template <int OC>
 __global__ void __launch_bounds__(256) k_unpack_scan(const uint8_t* __restrict__ fw, const int32_t* __restrict__ row_bl,
                                                      const int32_t* __restrict__ row_time, int nchan, int wcorr,
@@ -157,14 +227,23 @@ __global__ void __launch_bounds__(256) k_unpack_scan(const uint8_t* __restrict__
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     const size_t r = blockIdx.y;
     if (f >= nchan) return;
-    const int bl = row_bl[r], t = row_time[r];
-    uint8_t any = 0;
-    if (!(bl < 0 || bl >= nbl || t < 0 || t >= ntime))
-        for (int c = 0; c < wcorr; c++) any |= fw[(((size_t)bl * wcorr + c) * ntime + t) * (size_t)nchan + f];
-    any = any ? 1 : 0;
-    if (OC == 4) {
-        *reinterpret_cast<uchar4*>(out + (r * nchan + f) * 4) = make_uchar4(any, any, any, any);
-    } else {
-        for (int c = 0; c < out_ncorr; c++) out[(r * nchan + f) * (size_t)out_ncorr + c] = any;
-    }
+    unpack_scan_sample<OC>(fw, row_bl[r], row_time[r], f, nchan, wcorr, out_ncorr, nbl, ntime,
+                           out + r * nchan * (size_t)(OC == 4 ? 4 : out_ncorr));
+}
+
+// Row-list variant: entry e = e0 + blockIdx.y writes destination row dst_row[e] (nullptr: e) of the
+// (out_rows, nchan, out_ncorr) flags from cell (row_bl[e], row_time[e]); rows not in the list are not touched.
+template <int OC>
+__global__ void __launch_bounds__(256) k_unpack_scan_rows(const uint8_t* __restrict__ fw, const int64_t* __restrict__ dst_row,
+                                                          int64_t out_rows, const int32_t* __restrict__ row_bl,
+                                                          const int32_t* __restrict__ row_time, int64_t e0, int nchan,
+                                                          int wcorr, int out_ncorr, int nbl, int ntime,
+                                                          uint8_t* __restrict__ out) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = e0 + blockIdx.y;
+    if (f >= nchan) return;
+    const int64_t r = dst_row ? dst_row[e] : e;
+    if (r < 0 || r >= out_rows) return;
+    unpack_scan_sample<OC>(fw, row_bl[e], row_time[e], f, nchan, wcorr, out_ncorr, nbl, ntime,
+                           out + (size_t)r * nchan * (size_t)(OC == 4 ? 4 : out_ncorr));
 }

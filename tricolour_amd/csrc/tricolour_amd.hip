@@ -2235,16 +2235,10 @@ static bool fill_stokes_terms(StokesTerm* dst, const int32_t* idx, const double*
     return true;
 }
 
-extern "C" int tri_pack_scan(const void* data_c64, const void* model_c64, const uint8_t* flag,
-                             const int32_t* row_bl, const int32_t* row_time, int64_t rows, int64_t nchan,
-                             int64_t ncorr, int64_t nbl, int64_t ntime, int mode, const int32_t* pol_idx,
-                             const double* pol_alpha, int64_t n_pol, void* vis_windows_c64,
-                             uint8_t* flag_windows, void* stream) {
-    if (!data_c64 || !row_bl || !row_time || !vis_windows_c64 || !flag_windows)
-        return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (rows < 0 || nchan <= 0 || ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
+// mode and term tables of the scan pack entry points -> terms (none in mode 0)
+static int scan_stokes_terms(int mode, const int32_t* pol_idx, const double* pol_alpha, int64_t n_pol, int64_t ncorr,
+                             StokesTerms& terms) {
     if (mode < 0 || mode > 2) return set_err(TRI_EINVAL, "mode must be 0 (standard), 1 (polarisation) or 2 (total_power)");
-    StokesTerms terms;
     terms.n_pol = 0;
     terms.n_unpol = 0;
     if (mode != 0) {
@@ -2255,6 +2249,19 @@ extern "C" int tri_pack_scan(const void* data_c64, const void* model_c64, const 
         if (!fill_stokes_terms(terms.pol, pol_idx, pol_alpha, n_pol, ncorr))
             return set_err(TRI_EINVAL, "correlation index out of range");
     }
+    return TRI_OK;
+}
+
+extern "C" int tri_pack_scan(const void* data_c64, const void* model_c64, const uint8_t* flag,
+                             const int32_t* row_bl, const int32_t* row_time, int64_t rows, int64_t nchan,
+                             int64_t ncorr, int64_t nbl, int64_t ntime, int mode, const int32_t* pol_idx,
+                             const double* pol_alpha, int64_t n_pol, void* vis_windows_c64,
+                             uint8_t* flag_windows, void* stream) {
+    if (!data_c64 || !row_bl || !row_time || !vis_windows_c64 || !flag_windows)
+        return set_err(TRI_EINVAL, "NULL pointer argument");
+    if (rows < 0 || nchan <= 0 || ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
+    StokesTerms terms;
+    if (const int rc = scan_stokes_terms(mode, pol_idx, pol_alpha, n_pol, ncorr, terms)) return rc;
     const bool stokes = mode != 0;
     // 1 / 2 / 4 correlations with 16-byte aligned rows: vector loads of a thread's (chan, corr) piece
     const bool al = (uintptr_t)data_c64 % 16 == 0 && (uintptr_t)model_c64 % 16 == 0 && (uintptr_t)flag % 4 == 0;
@@ -2309,6 +2316,78 @@ extern "C" int tri_unpack_scan(const uint8_t* flag_windows, const int32_t* row_b
         else
             hipLaunchKernelGGL(k_unpack_scan<0>, grid, dim3(256), 0, st, flag_windows, row_bl + r0,
                                row_time + r0, (int)nchan, (int)wcorr, (int)out_ncorr, (int)nbl, (int)ntime, osl);
+    });
+}
+
+extern "C" int tri_pack_scan_rows(const void* data_c64, const void* model_c64, const uint8_t* flag,
+                                  const int64_t* src_row, int64_t src_rows, const int32_t* row_bl,
+                                  const int32_t* row_time, int64_t n, int64_t nchan, int64_t ncorr, int64_t nbl,
+                                  int64_t ntime, int mode, const int32_t* pol_idx, const double* pol_alpha,
+                                  int64_t n_pol, void* vis_windows_c64, uint8_t* flag_windows, void* stream) {
+    if (!data_c64 || !row_bl || !row_time || !vis_windows_c64 || !flag_windows)
+        return set_err(TRI_EINVAL, "NULL pointer argument");
+    if (n < 0 || src_rows < 0 || nchan <= 0 || ncorr <= 0 || nbl < 0 || ntime < 0) return set_err(TRI_EINVAL, "bad shape");
+    if (!src_row && n > src_rows) return set_err(TRI_EINVAL, "a list without src_row reads rows [0, n): n > src_rows");
+    StokesTerms terms;
+    if (const int rc = scan_stokes_terms(mode, pol_idx, pol_alpha, n_pol, ncorr, terms)) return rc;
+    const bool stokes = mode != 0;
+    // the vector path of tri_pack_scan: 1 / 2 / 4 correlations with 16-byte aligned rows
+    const bool al = (uintptr_t)data_c64 % 16 == 0 && (uintptr_t)model_c64 % 16 == 0 && (uintptr_t)flag % 4 == 0;
+    const bool vec = al && (ncorr == 4 || ncorr == 2 || ncorr == 1);
+    hipStream_t st = (hipStream_t)stream;
+    const float2* d = (const float2*)data_c64;
+    const float2* m = (const float2*)model_c64;
+    const uint8_t* fl = flag;
+    float2* vw = (float2*)vis_windows_c64;
+    return for_row_slabs(n, nchan, ncorr, nbl, ntime, [&](int64_t e0, unsigned nr) {
+        const dim3 grid((unsigned)cdiv(nchan, 256), nr, 1);
+#define TRI_PACK_SCAN_ROWS_V(NC, S)                                                                                 \
+        do {                                                                                                         \
+            if (m && fl)  hipLaunchKernelGGL((k_pack_scan_rows_v<NC, S, true, true>), grid, dim3(256), 0, st, d, m,  \
+                                             fl, src_row, src_rows, row_bl, row_time, e0, (int)nchan, (int)nbl,      \
+                                             (int)ntime, terms, vw, flag_windows);                                   \
+            else if (m)   hipLaunchKernelGGL((k_pack_scan_rows_v<NC, S, true, false>), grid, dim3(256), 0, st, d, m, \
+                                             fl, src_row, src_rows, row_bl, row_time, e0, (int)nchan, (int)nbl,      \
+                                             (int)ntime, terms, vw, flag_windows);                                   \
+            else if (fl)  hipLaunchKernelGGL((k_pack_scan_rows_v<NC, S, false, true>), grid, dim3(256), 0, st, d, m, \
+                                             fl, src_row, src_rows, row_bl, row_time, e0, (int)nchan, (int)nbl,      \
+                                             (int)ntime, terms, vw, flag_windows);                                   \
+            else          hipLaunchKernelGGL((k_pack_scan_rows_v<NC, S, false, false>), grid, dim3(256), 0, st, d,   \
+                                             m, fl, src_row, src_rows, row_bl, row_time, e0, (int)nchan, (int)nbl,   \
+                                             (int)ntime, terms, vw, flag_windows);                                   \
+        } while (0)
+        if (vec && ncorr == 4 && stokes) TRI_PACK_SCAN_ROWS_V(4, true);
+        else if (vec && ncorr == 4) TRI_PACK_SCAN_ROWS_V(4, false);
+        else if (vec && ncorr == 2 && stokes) TRI_PACK_SCAN_ROWS_V(2, true);
+        else if (vec && ncorr == 2) TRI_PACK_SCAN_ROWS_V(2, false);
+        else if (vec && ncorr == 1 && stokes) TRI_PACK_SCAN_ROWS_V(1, true);
+        else if (vec && ncorr == 1) TRI_PACK_SCAN_ROWS_V(1, false);
+        else
+            hipLaunchKernelGGL(k_pack_scan_rows, grid, dim3(256), 0, st, d, m, fl, src_row, src_rows, row_bl, row_time,
+                               e0, (int)nchan, (int)ncorr, (int)nbl, (int)ntime, stokes ? 1 : 0, terms, vw,
+                               flag_windows);
+#undef TRI_PACK_SCAN_ROWS_V
+    });
+}
+
+extern "C" int tri_unpack_scan_rows(const uint8_t* flag_windows, const int64_t* dst_row, int64_t out_rows,
+                                    const int32_t* row_bl, const int32_t* row_time, int64_t n, int64_t nchan,
+                                    int64_t wcorr, int64_t out_ncorr, int64_t nbl, int64_t ntime, uint8_t* out_flags,
+                                    void* stream) {
+    if (!flag_windows || !row_bl || !row_time || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
+    if (n < 0 || out_rows < 0 || nchan <= 0 || out_ncorr <= 0 || nbl < 0 || ntime < 0)
+        return set_err(TRI_EINVAL, "bad shape");
+    if (wcorr != 1 && wcorr != out_ncorr) return set_err(TRI_EINVAL, "wcorr must be 1 or out_ncorr");
+    if (!dst_row && n > out_rows) return set_err(TRI_EINVAL, "a list without dst_row writes rows [0, n): n > out_rows");
+    hipStream_t st = (hipStream_t)stream;
+    return for_row_slabs(n, nchan, out_ncorr, nbl, ntime, [&](int64_t e0, unsigned nr) {
+        const dim3 grid((unsigned)cdiv(nchan, 256), nr, 1);
+        if (out_ncorr == 4 && (uintptr_t)out_flags % 4 == 0)
+            hipLaunchKernelGGL(k_unpack_scan_rows<4>, grid, dim3(256), 0, st, flag_windows, dst_row, out_rows, row_bl,
+                               row_time, e0, (int)nchan, (int)wcorr, 4, (int)nbl, (int)ntime, out_flags);
+        else
+            hipLaunchKernelGGL(k_unpack_scan_rows<0>, grid, dim3(256), 0, st, flag_windows, dst_row, out_rows, row_bl,
+                               row_time, e0, (int)nchan, (int)wcorr, (int)out_ncorr, (int)nbl, (int)ntime, out_flags);
     });
 }
 

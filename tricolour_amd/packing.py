@@ -216,3 +216,104 @@ def unpack_scan(antenna1, antenna2, time_inv, ubl, flag_windows, ncorr):
     _lib.check(lib.tri_unpack_scan(fw8.data_ptr(), rb.data_ptr(), rt.data_ptr(), rows, nchan, wcorr,
                                    ncorr, nbl, ntime, out.data_ptr(), stream))
     return out.view(torch.bool)
+
+
+class ScanChunk:
+    """One baseline chunk ``[b0, b1)`` of a scan (:func:`scan_chunks`).
+
+    ``rows``: every MS row of the chunk's baselines, ascending (int64), the
+    unpack list; ``bl``: the rows' baseline within the chunk (``row_bl - b0``,
+    int32); ``time``: their time index (int32); ``pack``: positions in
+    ``rows`` of the rows :func:`row_map` keeps for packing (int64, ascending);
+    ``runs``: ``(n, 2)`` int64 ``[start, stop)`` of the maximal runs of
+    consecutive MS rows in ``rows``, in order."""
+    __slots__ = ("b0", "b1", "rows", "bl", "time", "pack", "runs")
+
+    def __init__(self, b0, b1, rows, bl, time, pack, runs):
+        self.b0, self.b1, self.rows, self.bl, self.time, self.pack, self.runs = b0, b1, rows, bl, time, pack, runs
+
+    @property
+    def pack_rows(self):
+        return self.rows[self.pack]
+
+
+def scan_chunks(ant1, ant2, ubl, time_inv, ntime, baseline_chunks):
+    """Splits a scan into chunks of ``baseline_chunks`` consecutive baselines
+    of ``ubl`` and yields one :class:`ScanChunk` per chunk, in baseline order.
+    Every row whose baseline is in ``ubl`` lies in exactly one chunk; when rows
+    duplicate a (baseline, time) cell, the pack list keeps the last one, as
+    :func:`row_map` does."""
+    n = int(baseline_chunks)
+    if n < 1:
+        raise ValueError("baseline_chunks must be >= 1, got %d" % n)
+    ubl = np.asarray(ubl)
+    nbl = int(ubl.shape[0])
+    row_bl, row_bl_pack, row_time = row_map(np.asarray(ant1), np.asarray(ant2), ubl, np.asarray(time_inv), ntime)
+    mapped = np.nonzero(row_bl >= 0)[0]
+    chunk = row_bl[mapped] // n
+    order = mapped[np.argsort(chunk, kind="stable")]          # rows grouped by chunk, ascending within one
+    bounds = np.searchsorted(np.sort(chunk, kind="stable"), np.arange(-(-nbl // n) + 1))
+    for k in range(len(bounds) - 1):
+        rows = order[bounds[k]:bounds[k + 1]].astype(np.int64)
+        b0 = k * n
+        cut = np.nonzero(np.diff(rows) != 1)[0] + 1
+        starts = np.concatenate([[0], cut]).astype(np.int64)
+        stops = np.concatenate([cut, [rows.size]]).astype(np.int64)
+        runs = np.stack([rows[starts], rows[stops - 1] + 1], axis=1) if rows.size else np.zeros((0, 2), np.int64)
+        yield ScanChunk(b0, min(b0 + n, nbl), rows, (row_bl[rows] - b0).astype(np.int32), row_time[rows],
+                        np.nonzero(row_bl_pack[rows] >= 0)[0].astype(np.int64), runs)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _term_args(mode, stokes_terms):
+    from tricolour_amd.stokes import _term_tables
+    return _term_tables(stokes_terms if mode != 0 else ())
+
+
+def pack_scan_rows(data, model, flags, src_row, row_bl, row_time, nbl, ntime, vis_windows, flag_windows,
+                   flagging_strategy="standard", stokes_terms=()):
+    """``tri_pack_scan_rows`` on device tensors: entry ``i`` of the lists
+    packs row ``src_row[i]`` (None: row ``i``) of the (rows, chan, corr)
+    ``data`` (complex64), ``model`` (complex64 or None) and ``flags`` (uint8
+    or None) into cell ``(row_bl[i], row_time[i])`` of the (nbl, wcorr,
+    ntime, chan) windows, on the current stream.  ``src_row``: int64,
+    ``row_bl`` / ``row_time``: int32 device tensors."""
+    import torch
+    lib = _lib.lib()
+    mode = SCAN_MODES[flagging_strategy]
+    src_rows, nchan, ncorr = (int(s) for s in data.shape)
+    for name, col in (("model", model), ("flags", flags)):
+        if col is not None and tuple(col.shape) != tuple(data.shape):
+            raise ValueError("%s shape %s != data shape %s" % (name, tuple(col.shape), tuple(data.shape)))
+    if not (row_bl.numel() == row_time.numel() and (src_row is None or src_row.numel() == row_bl.numel())):
+        raise ValueError("src_row, row_bl and row_time must have one entry per list entry")
+    pidx, palpha, npol = _term_args(mode, stokes_terms)
+    stream = torch.cuda.current_stream(data.device).cuda_stream
+    _lib.check(lib.tri_pack_scan_rows(data.data_ptr(), _ptr(model), _ptr(flags), _ptr(src_row), src_rows,
+                                      row_bl.data_ptr(), row_time.data_ptr(), int(row_bl.numel()), nchan, ncorr,
+                                      int(nbl), int(ntime), mode, pidx.ctypes.data, palpha.ctypes.data, npol,
+                                      vis_windows.data_ptr(), flag_windows.data_ptr(), stream))
+
+
+def unpack_scan_rows(flag_windows, dst_row, row_bl, row_time, out):
+    """``tri_unpack_scan_rows`` on device tensors: entry ``i`` writes row
+    ``dst_row[i]`` (None: row ``i``) of the (rows, chan, ncorr) uint8 ``out``
+    from cell ``(row_bl[i], row_time[i])`` of the (bl, wcorr, time, chan)
+    ``flag_windows``, on the current stream; other rows keep their contents."""
+    import torch
+    lib = _lib.lib()
+    nbl, wcorr, ntime, nchan = (int(s) for s in flag_windows.shape)
+    out_rows, onchan, ncorr = (int(s) for s in out.shape)
+    if onchan != nchan:
+        raise ValueError("flag windows have %d channels, the output %d" % (nchan, onchan))
+    if wcorr not in (1, ncorr):
+        raise ValueError("flag windows have %d correlations: need 1 or %d" % (wcorr, ncorr))
+    if not (row_bl.numel() == row_time.numel() and (dst_row is None or dst_row.numel() == row_bl.numel())):
+        raise ValueError("dst_row, row_bl and row_time must have one entry per list entry")
+    stream = torch.cuda.current_stream(out.device).cuda_stream
+    _lib.check(lib.tri_unpack_scan_rows(flag_windows.data_ptr(), _ptr(dst_row), out_rows, row_bl.data_ptr(),
+                                        row_time.data_ptr(), int(row_bl.numel()), nchan, wcorr, ncorr, nbl, ntime,
+                                        out.data_ptr(), stream))

@@ -11,7 +11,10 @@ application's broadcast to the MS's correlations (``tri_unpack_scan``).  No
 Measurement Set I/O: callers hand in columns already loaded.
 """
 import logging
+import numbers
 import re
+import threading
+import time
 
 import numpy as np
 
@@ -19,6 +22,7 @@ from tricolour_amd import packing
 from tricolour_amd.stokes import STOKES_TYPES, stokes_corr_map
 
 log = logging.getLogger(__name__)
+_tls = threading.local()
 
 VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with_input_flags", "unflag",
                "flag_nans_zeros", "apply_static_mask")          # strat_executor.py:36-83
@@ -160,9 +164,19 @@ def _stokes_terms(flagging_strategy, corr_type):
     return terms
 
 
+def _check_baseline_chunks(baseline_chunks):
+    if baseline_chunks is None:
+        return None
+    if isinstance(baseline_chunks, (bool, np.bool_)) or not isinstance(baseline_chunks, numbers.Integral):
+        raise ValueError("baseline_chunks must be None or an integer >= 1, got %r" % (baseline_chunks,))
+    if int(baseline_chunks) < 1:
+        raise ValueError("baseline_chunks must be None or an integer >= 1, got %d" % int(baseline_chunks))
+    return int(baseline_chunks)
+
+
 def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, strategies, *, model=None,
               flagging_strategy="standard", corr_type=None, ignore_flags=False, antenna_positions=None,
-              masked_channels=(), antenna_names=None, scan_no=0, field_name="", ddid=0):
+              masked_channels=(), antenna_names=None, scan_no=0, field_name="", ddid=0, baseline_chunks=None):
     """Flags one (field, ddid, scan) dataset as the tricolour application does
     (app.py:370-486).
 
@@ -178,11 +192,20 @@ def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, stra
     bool flags, every correlation of a visibility flagged if any window
     correlation is (a numpy array for numpy ``data``, a device tensor
     otherwise), and the :class:`~tricolour_amd.window_statistics.WindowStatistics`
-    of the packed flags before and after the strategies."""
+    of the packed flags before and after the strategies.
+
+    ``baseline_chunks``: None holds the whole scan on the device at once; an
+    integer N >= 1 streams it through the device in chunks of N consecutive
+    baselines (:func:`tricolour_amd.packing.scan_chunks`), with the same
+    flags and tallies.  Then only one chunk's rows, windows and row flags
+    (and the next chunk's rows, in flight) are held on the device besides
+    the caller's own device tensors, and host ``data`` (numpy or a CPU
+    tensor) gives a numpy result."""
     import torch
     from tricolour_amd.strategies import apply_strategies
     from tricolour_amd.window_statistics import window_stats_block
 
+    baseline_chunks = _check_baseline_chunks(baseline_chunks)
     if flagging_strategy not in packing.SCAN_MODES:
         raise ValueError("Invalid flagging strategy '%s'" % flagging_strategy)
     strategies = list(strategies)
@@ -232,6 +255,13 @@ def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, stra
         antenna_names = [str(i) for i in range(nant)]
     antenna_names = [str(n) for n in _host(antenna_names).tolist()]
 
+    ant_pos = None if antenna_positions is None else _host(antenna_positions)
+    if baseline_chunks is not None and ubl.shape[0] > 0:
+        return _flag_scan_streamed(
+            data, None if ignore_flags else flags, model, a1, a2, time_inv, ntime, ubl, baseline_chunks,
+            flagging_strategy, terms, strategies,
+            dict(ant_pos=ant_pos, chan_freq=chan_freq, chan_width=chan_width, masked_channels=list(masked_channels)),
+            (chan_freq, antenna_names, scan_no, field_name, ddid))
     vis_w, flag_w = packing.pack_scan(time_inv, ubl, a1, a2, data, None if ignore_flags else flags, ntime,
                                       model=model, flagging_strategy=flagging_strategy, stokes_terms=terms)
     original = window_stats_block(flag_w, ubl, chan_freq, antenna_names, scan_no, field_name, ddid)
@@ -245,12 +275,196 @@ def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, stra
     return row_flags, original, final
 
 
+def last_stream_stats():
+    """Timings of this thread's latest streamed :func:`flag_scan` call (host
+    inputs): ``upload_s`` / ``upload_bytes`` of the row uploads,
+    ``upload_wait_s`` the part of it the flagging waited for (the rest ran
+    under the previous chunk's work), ``d2h_s`` / ``d2h_bytes`` of the row
+    flags returned, ``chunks``."""
+    return dict(getattr(_tls, "stream_stats", {}))
+
+
+def _host_rows(torch, a, dtype):
+    """A host column as a CPU tensor without copying it (numpy, CPU or device tensor)."""
+    if a is None:
+        return None
+    if torch.is_tensor(a):
+        a = a.detach().cpu()
+    else:
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if dtype == torch.bool and a.dtype not in (torch.bool, torch.uint8):
+        a = a != 0
+    return a.contiguous()
+
+
+def _flag_scan_streamed(data, flags, model, a1, a2, time_inv, ntime, ubl, baseline_chunks, flagging_strategy, terms,
+                        strategies, strategy_args, stats_args):
+    """:func:`flag_scan` one baseline chunk at a time.  For each chunk of
+    :func:`~tricolour_amd.packing.scan_chunks`: its rows onto the device
+    (device inputs: read in place through ``src_row``; host inputs: the
+    chunk's runs of rows copied into a compact slab, on a side stream by a
+    worker thread while the previous chunk is flagged), ``tri_fill_windows``
+    + ``tri_pack_scan_rows``, the window statistics, the strategies on
+    ``ubl[b0:b1]``, the statistics again and ``tri_unpack_scan_rows``.  The
+    chunks' tallies are summed in baseline order."""
+    import contextlib
+    from concurrent.futures import ThreadPoolExecutor
+
+    from tricolour_amd import flagging
+    from tricolour_amd.strategies import apply_strategies
+    from tricolour_amd.window_statistics import window_stats_block
+
+    torch = packing._torch_gpu()
+    nrow, nchan, ncorr = (int(s) for s in data.shape)
+    wcorr = ncorr if flagging_strategy == "standard" else 1
+    on_device = torch.is_tensor(data) and data.is_cuda
+    device = data.device if on_device else torch.device("cuda", torch.cuda.current_device())
+    chunks = list(packing.scan_chunks(a1, a2, ubl, time_inv, ntime, baseline_chunks))
+    link = flagging._H2D_TURN if flagging._LINK_TURNS else contextlib.nullcontext()
+    times = dict(upload_s=0.0, upload_bytes=0, upload_wait_s=0.0, d2h_s=0.0, d2h_bytes=0, chunks=len(chunks))
+
+    def idx(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(device)
+
+    originals, finals = [], []
+    with torch.cuda.device(device):
+        main = torch.cuda.current_stream(device)
+        if on_device:
+            cols = [packing._dev(torch, data, torch.complex64),
+                    None if model is None else packing._dev(torch, model, torch.complex64), None]
+            if flags is not None:
+                f = packing._dev(torch, flags)
+                cols[2] = f.view(torch.uint8) if f.dtype == torch.bool else (f != 0).view(torch.uint8)
+            result = torch.zeros((nrow, nchan, ncorr), dtype=torch.uint8, device=device)
+        else:
+            host = [_host_rows(torch, data, torch.complex64), _host_rows(torch, model, torch.complex64),
+                    _host_rows(torch, flags, torch.bool)]
+            slab_rows = max(c.rows.size for c in chunks)
+            dtypes = (torch.complex64, torch.complex64, torch.bool)
+            # two row slabs: chunk k + 1 is copied into one while chunk k is packed from the other
+            slabs = [[None if h is None else torch.empty((slab_rows, nchan, ncorr), dtype=dt, device=device)
+                      for h, dt in zip(host, dtypes)] for _ in range(2)]
+            side = torch.cuda.Stream(device)
+            result = np.zeros((nrow, nchan, ncorr), np.bool_)
+            pool = ThreadPoolExecutor(max_workers=1)
+
+            def upload(c, slot, after):
+                # runs on the worker thread: the chunk's runs of rows into slot `slot`, once the main stream has
+                # passed `after` (the last use of the slot and of any memory the slabs share)
+                t0 = time.perf_counter()
+                nbytes = 0
+                with torch.cuda.device(device), torch.cuda.stream(side):
+                    side.wait_event(after)
+                    with link:
+                        t1 = time.perf_counter()
+                        j = 0
+                        for r0, r1 in c.runs.tolist():
+                            for h, dst in zip(host, slabs[slot]):
+                                if h is not None:
+                                    dst[j:j + r1 - r0].copy_(h[r0:r1], non_blocking=True)
+                                    nbytes += dst[j:j + r1 - r0].nbytes
+                            j += r1 - r0
+                        side.synchronize()
+                    done = torch.cuda.Event()
+                    done.record(side)
+                t2 = time.perf_counter()
+                return done, t2 - t1, t2 - t0, nbytes
+
+            def submit(k):
+                after = torch.cuda.Event()
+                after.record(main)
+                return pool.submit(upload, chunks[k], k % 2, after)
+
+        pending = None
+        try:
+            if not on_device:
+                pending = submit(0)
+            for k, c in enumerate(chunks):
+                nbl_c, nr = c.b1 - c.b0, int(c.rows.size)
+                whole_pack = c.pack.size == nr          # no duplicate cells in the chunk: pack every row
+                if on_device:
+                    src = idx(c.rows if whole_pack else c.rows[c.pack], np.int64)
+                    data_c, model_c, flag_c = cols
+                else:
+                    t0 = time.perf_counter()
+                    done, copy_s, _, nbytes = pending.result()
+                    times["upload_wait_s"] += time.perf_counter() - t0
+                    times["upload_s"] += copy_s
+                    times["upload_bytes"] += nbytes
+                    pending = None
+                    main.wait_event(done)
+                    src = None if whole_pack else idx(c.pack, np.int64)
+                    data_c, model_c, flag_c = (None if s_ is None else s_[:nr] for s_ in slabs[k % 2])
+                    if flag_c is not None:
+                        flag_c = flag_c.view(torch.uint8)
+                vis_w = torch.empty((nbl_c, wcorr, ntime, nchan), dtype=torch.complex64, device=device)
+                flag_w = torch.empty((nbl_c, wcorr, ntime, nchan), dtype=torch.uint8, device=device)
+                _lib_check_fill(torch, vis_w, flag_w)
+                pb = c.bl if whole_pack else c.bl[c.pack]
+                pt = c.time if whole_pack else c.time[c.pack]
+                packing.pack_scan_rows(data_c, model_c, flag_c, src, idx(pb, np.int32), idx(pt, np.int32), nbl_c,
+                                       ntime, vis_w, flag_w, flagging_strategy=flagging_strategy,
+                                       stokes_terms=terms)
+                if not on_device and k + 1 < len(chunks):
+                    pending = submit(k + 1)               # under this chunk's statistics and strategies
+                flag_w = flag_w.view(torch.bool)
+                ubl_c = ubl[c.b0:c.b1]
+                originals.append(window_stats_block(flag_w, ubl_c, *stats_args))
+                flag_w = apply_strategies(strategies, flag_w, vis_w, ubl=ubl_c, **strategy_args)
+                finals.append(window_stats_block(flag_w, ubl_c, *stats_args))
+                del vis_w
+                fw8 = flag_w.view(torch.uint8) if flag_w.dtype == torch.bool else (flag_w != 0).view(torch.uint8)
+                ub, ut = idx(c.bl, np.int32), idx(c.time, np.int32)
+                if on_device:
+                    packing.unpack_scan_rows(fw8, idx(c.rows, np.int64), ub, ut, result)
+                else:
+                    out = torch.empty((nr, nchan, ncorr), dtype=torch.uint8, device=device)
+                    packing.unpack_scan_rows(fw8, None, ub, ut, out)
+                    _chunk_to_host(torch, flagging, link, main, out, c.rows, result, times)
+        finally:
+            if pending is not None:
+                try:
+                    pending.result()
+                except Exception:
+                    pass
+            if not on_device:
+                pool.shutdown()
+                main.synchronize()
+    flagging.release_workspace()
+    _tls.stream_stats = times
+    return (result.view(torch.bool) if on_device else result), _combine(originals), _combine(finals)
+
+
+def _lib_check_fill(torch, vis_w, flag_w):
+    from tricolour_amd import _lib
+    stream = torch.cuda.current_stream(vis_w.device).cuda_stream
+    _lib.check(_lib.lib().tri_fill_windows(vis_w.data_ptr(), flag_w.data_ptr(), vis_w.numel(), stream))
+
+
+def _chunk_to_host(torch, flagging, link, main, out, rows, result, times):
+    """A chunk's (rows, chan, corr) device flags into rows ``rows`` of the numpy ``result``: through this thread's
+    pinned staging buffer (a copy into pageable pages runs at a fraction of the link rate), then a host scatter."""
+    main.synchronize()
+    t0 = time.perf_counter()
+    stage = flagging._d2h_stage(torch, out.numel())
+    with link:
+        if stage is None:
+            got = out.cpu().numpy()
+        else:
+            stage[:out.numel()].copy_(out.reshape(-1), non_blocking=True)
+            main.synchronize()
+            got = stage[:out.numel()].numpy().reshape(out.shape)
+    times["d2h_s"] += time.perf_counter() - t0
+    times["d2h_bytes"] += out.numel()
+    result[rows] = got.view(np.bool_)
+
+
 # ---------------------------------------------------------------------------
 # every scan
 # ---------------------------------------------------------------------------
 def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fieldnames=None, ms_name="",
                flagging_strategy="standard", ignore_flags=False, antenna_positions=None, masked_channels=(),
-               antenna_names=None):
+               antenna_names=None, baseline_chunks=None):
     """The dataset loop of the application (app.py:327-486) over datasets
     already loaded, one dict per (field, ddid, scan) with the keys
     ``DATA``, ``FLAG``, ``ANTENNA1``, ``ANTENNA2``, ``TIME``, ``FIELD_ID``,
@@ -261,9 +475,10 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
     Returns ``(row_flags, summary)``: a list with the row flags of each
     dataset (None for datasets the field / scan selection skips) and the
     lines of ``summarise_stats`` over all flagged datasets (an empty list if
-    none was flagged)."""
+    none was flagged).  ``baseline_chunks``: as for :func:`flag_scan`."""
     from tricolour_amd.window_statistics import summarise_stats
 
+    baseline_chunks = _check_baseline_chunks(baseline_chunks)
     datasets = list(datasets)
     strategies = list(strategies)
     check_strategies(strategies)
@@ -288,7 +503,7 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
             ds["CHAN_WIDTH"], strategies, model=ds.get("MODEL"), flagging_strategy=flagging_strategy,
             corr_type=ds.get("CORR_TYPE"), ignore_flags=ignore_flags, antenna_positions=antenna_positions,
             masked_channels=masked_channels, antenna_names=antenna_names, scan_no=scan_no,
-            field_name=field_dict[field_id], ddid=int(ds["DATA_DESC_ID"]))
+            field_name=field_dict[field_id], ddid=int(ds["DATA_DESC_ID"]), baseline_chunks=baseline_chunks)
         out.append(row_flags)
         original_stats.append(original)
         final_stats.append(final)
