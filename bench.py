@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mvis/s flagged by sum_threshold_flagger on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload slab|chain|ska] [--params stage1|defaults|very_broad]
+    python bench.py --gpus N --steps K --warmup W [--workload slab|chain|ska] [--params stage1|defaults|very_broad] [--full]
 
 Workloads (BASELINE.json configs):
   slab   (default) one sum_threshold_flagger call per step over one HBM-resident slab of the MeerKAT-64
@@ -17,13 +17,16 @@ Workloads (BASELINE.json configs):
          device-resident rate over the same slabs; the PCIe-inclusive sustained rate is reported beside it.
 
 Baselines are independent (flagging.py:765-774): ranks own contiguous baseline slabs and only meet at the
-timing barriers.  For N > 1 a separately timed leg scatters a small slab set from rank 0 and gathers the
+timing barriers.  For N > 1 with --full a separately timed leg scatters a small slab set from rank 0 and gathers the
 flags back over RCCL (tricolour_amd.distributed), which is how a single-root data set would be fanned out.
 
 `--gpus N` without a torchrun environment starts the N ranks itself (python -m torch.distributed.run ...)
 before any GPU call and relays rank 0's line.
 
-Prints ONE JSON line (rank 0): metric / value = whole-job Mvis/s with inputs already resident in HBM, plus
+Prints ONE JSON line (rank 0): metric / value = whole-job Mvis/s with inputs already resident in HBM.  A plain run does
+only what that figure needs: it sets up the inputs, runs the warm-up and the timed steps, writes --dump-outputs if
+asked, and prints the line.  With --full the line also carries the legs below (each can be left out with its --no-*
+option), and for N > 1 the scatter / gather leg runs:
   "roofline"      ONE object: the kernel with the largest share of the step (the fused frequency-axis box
                   filter stage), timed live with HIP events on its launch stream in the step's own launch
                   geometry; "roofline_kernels" lists every kernel measured that way (SumThreshold included);
@@ -32,7 +35,7 @@ Prints ONE JSON line (rank 0): metric / value = whole-job Mvis/s with inputs alr
                   here) on a bounded sample of the same workload on this box's host cores (rank 0, N=1);
   "other_params"  the same slab with the other shipped parameter sets (slab workload, N=1);
   "other_workloads"  short `chain` (configs[3]) and `ska` (configs[4], 1-GPU half) legs with their own parity_check,
-                  so that the one command the driver times carries every single-GPU configuration (slab workload, N=1).
+                  so that one --full run carries every single-GPU configuration (slab workload, N=1).
 A parity_check that fails (any mismatch on a bit-exact leg, < 99.9 % agreement on the chain leg) is reported in the
 line ("parity_ok": false) and the process exits with code 4 after printing it.
 """
@@ -703,12 +706,15 @@ def main():
     ap.add_argument("--scatter-bl", type=int, default=8, help="baselines per rank in the N > 1 scatter / gather leg")
     ap.add_argument("--no-scatter", action="store_true")
     ap.add_argument("--scatter-timeout", type=int, default=240, help="seconds the N > 1 scatter / gather leg may take")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs that measure or check anything else: other parameter sets, "
+                         "roofline, CPU baseline, parity check, other workloads, and for N > 1 the scatter / gather leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-parity-check", action="store_true")
     ap.add_argument("--no-other-params", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short chain / ska legs of the default (slab, N = 1) run")
+                    help="skip the short chain / ska legs of a --full (slab, N = 1) run")
     ap.add_argument("--roofline-only", action="store_true",
                     help="run only the per-kernel roofline legs (what the rocprofv3 --pmc passes of profiles/ wrap)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -847,10 +853,11 @@ def main():
     else:
         step_launches = {}
         for w in range(warmup):
-            if rank == 0 and w == warmup - 1:
+            log = args.full and rank == 0 and w == warmup - 1   # for the roofline legs
+            if log:
                 _lib.kernel_log_begin()            # untimed: which kernels one step launches, and how often
             out = step()
-            if rank == 0 and w == warmup - 1:
+            if log:
                 step_launches = _lib.kernel_log_end()
         barrier()
         t0 = time.perf_counter()
@@ -893,8 +900,8 @@ def main():
             },
         }
         res.update(extra)
-    # the same slab under the other shipped parameter sets (extra keys, N = 1, slab workload)
-    if wl == "slab" and world == 1 and not args.no_other_params:
+    # --full: the same slab under the other shipped parameter sets (extra keys, N = 1, slab workload)
+    if args.full and wl == "slab" and world == 1 and not args.no_other_params:
         others = {}
         for other in sorted(PARAM_SETS):
             if other == pname:
@@ -916,7 +923,7 @@ def main():
     out = None
     flagging.release_workspace()
     torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         nwin = min(nbl * ncorr, 1008 if wl != "ska" else 64)
         if not args.no_roofline:
             kernels = [roofline_sumthreshold(torch, device, T, F, kw, nwin)] + \
@@ -961,7 +968,7 @@ def main():
     leg_failed = False
     # N > 1: the scatter -> flag -> gather leg comes last, under a watchdog -- a stuck point-to-point transfer
     # must not take the measured line with it
-    if dist is not None and not args.no_scatter:
+    if dist is not None and args.full and not args.no_scatter:
         import threading
 
         def give_up():

@@ -1,12 +1,16 @@
 # GPU box: the round's record -- bench lines of the three workloads, per-kernel summaries of the three parameter sets,
-# the PMC traffic files bench.py reads, the exact row filter's timings and counters.  Outputs under gpurun_out/.
+# the PMC traffic files bench.py reads, the exact row filter's timings and counters.  The three bench lines
+# (bench.py --full) go to $RECORD_DIR (default records/); the rest goes where scripts/prof.sh
+# writes its own outputs.
 set -euo pipefail
 cd $GRAFT_REPO_ROOT
-if [ -z "$SKIP_SLAB" ]; then timeout -k 10 500 python bench.py > gpurun_out/c_bench_slab_stage1.log 2>&1; tail -1 gpurun_out/c_bench_slab_stage1.log | cut -c1-200; fi
-timeout -k 10 400 python bench.py --workload chain > gpurun_out/c_bench_chain.log 2>&1
-tail -1 gpurun_out/c_bench_chain.log | cut -c1-200
-timeout -k 10 400 python bench.py --workload ska --steps 16 > gpurun_out/c_bench_ska.log 2>&1
-tail -1 gpurun_out/c_bench_ska.log | cut -c1-200
+OUT=${RECORD_DIR:-records}
+mkdir -p "$OUT"
+if [ -z "${SKIP_SLAB:-}" ]; then timeout -k 10 500 python bench.py --full > "$OUT/c_bench_slab_stage1.log" 2>&1; tail -1 "$OUT/c_bench_slab_stage1.log" | cut -c1-200; fi
+timeout -k 10 400 python bench.py --workload chain --full > "$OUT/c_bench_chain.log" 2>&1
+tail -1 "$OUT/c_bench_chain.log" | cut -c1-200
+timeout -k 10 400 python bench.py --workload ska --steps 16 --full > "$OUT/c_bench_ska.log" 2>&1
+tail -1 "$OUT/c_bench_ska.log" | cut -c1-200
 for p in stage1 defaults very_broad; do
   bash scripts/prof.sh c_$p --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-other-params --no-scatter --params $p
   cd $GRAFT_REPO_ROOT
