@@ -300,6 +300,30 @@ int tri_uvcontsub_flagger(const void *vis_c64, const uint8_t *flags, uint8_t *ou
                           int64_t taylor_degrees, double sigma,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Scale-invariant rank (SIR) operator (Offringa, van de Gronde & Roerdink
+ * 2012, A&A 539, A95) over (n_win, ntime, nchan) uint8 flag windows
+ * (nonzero = flagged).  For one line f[0..n) and 0 <= eta < 1:
+ *   U(i)   = number of unflagged samples in [0, i), i = 0..n
+ *   W(i)   = eta * (double)i - (double)U(i)     (IEEE multiply, then subtract)
+ *   out[x] = max_{x < j <= n} W(j) >= min_{0 <= k <= x} W(k)
+ * i.e. x is flagged iff some interval [k, j) containing it has at most
+ * eta * (j - k) unflagged samples.  Per window
+ *   out_flags = f | SIR_time(f, eta_time) | SIR_freq(f, eta_freq)
+ * where both axes read the INPUT mask (not chained; the result does not
+ * depend on the order), and eta = 0 skips an axis.  out_flags receives 0/1
+ * and must not overlap flags.  TRI_EINVAL for NULL pointers, negative shapes,
+ * eta NaN or outside [0, 1) and overlapping buffers; TRI_EWORKSPACE when
+ * workspace_bytes < tri_sir_workspace_bytes() (0 unless a line is longer
+ * than one workgroup's span: ntime > 1024 or nchan > 65536).  Empty shapes
+ * return TRI_OK without a launch.
+ */
+size_t tri_sir_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan);
+int tri_scale_invariant_rank(const uint8_t *flags, uint8_t *out_flags,
+                             int64_t n_win, int64_t ntime, int64_t nchan,
+                             double eta_time, double eta_freq,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

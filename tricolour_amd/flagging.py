@@ -680,3 +680,50 @@ def uvcontsub_flagger(vis, flags, major_cycles=5, or_original_from_cycle=1,
                 float(sigma), ws.data_ptr(), ws.numel(),
                 torch.cuda.current_stream(device).cuda_stream))
     return _like_flags(torch, out, flags, from_numpy)
+
+
+def scale_invariant_rank_operator(flags, eta_time=0.2, eta_freq=0.2):
+    """Scale-invariant rank operator (Offringa, van de Gronde & Roerdink 2012,
+    A&A 539, A95) on (bl, corr, time, chan) flags: a sample becomes flagged
+    when some interval along time (``eta_time``) or frequency (``eta_freq``)
+    that contains it has at most ``eta * length`` unflagged samples.  Both axes
+    read the input mask: ``out = f | SIR_time(f) | SIR_freq(f)``; ``eta = 0``
+    leaves an axis out.  Returns a new array in the container / dtype of
+    ``flags``; the input is not modified."""
+    shape = tuple(flags.shape)
+    if len(shape) != 4:
+        raise ValueError("flags must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    eta_time, eta_freq = float(eta_time), float(eta_freq)
+    for name, eta in (("eta_time", eta_time), ("eta_freq", eta_freq)):
+        if not 0.0 <= eta < 1.0:              # also rejects NaN
+            raise ValueError("%s must lie in [0, 1), got %r" % (name, eta))
+    torch = _require_gpu()
+    from_numpy = isinstance(flags, np.ndarray)
+    device = flags.device if (torch.is_tensor(flags) and flags.is_cuda) else \
+        torch.device("cuda", torch.cuda.current_device())
+    f8 = _flags_u8(torch, flags, device)
+    nbl, ncorr, ntime, nchan = (int(s) for s in shape)
+    n_win = nbl * ncorr
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            # the workspace holds per-segment aggregates of lines longer than one workgroup; batch the windows
+            # when even that does not fit
+            batch = n_win
+            nbytes = lib.tri_sir_workspace_bytes(batch, ntime, nchan)
+            if nbytes > 0:
+                budget = _workspace_budget(torch, device)
+                while batch > 1 and lib.tri_sir_workspace_bytes(batch, ntime, nchan) > budget:
+                    batch = (batch + 1) // 2
+                nbytes = lib.tri_sir_workspace_bytes(batch, ntime, nchan)
+            ws = _workspace(torch, device, nbytes) if nbytes > 0 else None
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_scale_invariant_rank(
+                    f8.data_ptr() + w0 * per, out.data_ptr() + w0 * per, b, ntime, nchan,
+                    eta_time, eta_freq, ws.data_ptr() if ws is not None else None,
+                    ws.numel() if ws is not None else 0, stream))
+    return _like_flags(torch, out, flags, from_numpy)

@@ -25,7 +25,8 @@ log = logging.getLogger(__name__)
 _tls = threading.local()
 
 VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with_input_flags", "unflag",
-               "flag_nans_zeros", "apply_static_mask")          # strat_executor.py:36-83
+               "flag_nans_zeros", "apply_static_mask",          # strat_executor.py:36-83
+               "scale_invariant_rank_operator")                 # beyond the reference: flagging.scale_invariant_rank_operator
 
 
 # ---------------------------------------------------------------------------

@@ -34,6 +34,9 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
             flag_windows = flag_windows * 0 if not torch.is_tensor(flag_windows) else torch.zeros_like(flag_windows)
         elif task == "flag_nans_zeros":
             flag_windows = flagging.flag_nans_and_zeros(vis_windows, flag_windows)   # :63
+        elif task == "scale_invariant_rank_operator":
+            new_flags = flagging.scale_invariant_rank_operator(flag_windows, **kw)
+            flag_windows = lor(new_flags, flag_windows)
         elif task == "apply_static_mask":
             new_flags = flagging.apply_static_mask(flag_windows, ubl, ant_pos, masked_channels,
                                                    chan_freq, chan_width, **kw)
