@@ -300,6 +300,10 @@ k_boxt_spec(const float* __restrict__ srcData, const uint8_t* __restrict__ srcFl
 //     w = W / d^4, o = O / d^4, bg = (w == 0) ? NaN : o / w      (flagging.py:419, 506-513)
 //     MODE 1: dstO = |data - bg|                                  (rejection loop, :563-566)
 //     MODE 2: dstO = bg, dstW = data - bg, nanflag[line] = 1 on a NaN   (:576-578, :962)
+//             dstP (optional): data - bg once more, as the column panels [n / 64][C][64] that k_transpose<float, true>
+//             would make of dstW (host: n % 64 == 0).  A lane holds PF / 2 consecutive positions of its line: they
+//             leave as 16-byte stores after the block's quotients are final, position by position only where a
+//             group of four straddles a panel or the block touches a line end.
 // The filtered images are never written.  Buffer addressing throughout (host: images and
 // outputs below 2^31 bytes per window).
 // grid (ceil(C / 32), W), block 64, dynamic LDS 4 * d * 64 + 2 * PF * 34 floats
@@ -317,14 +321,20 @@ __host__ __device__ constexpr int boxf_nsub(int ks) { return (BOXF_DOUBLE_STAGE 
 #ifndef BOXF_STREAM_AUX
 #define BOXF_STREAM_AUX 0
 #endif
+// Instantiations that take the panel output (MODE 2, dstP): it keeps PF / 2 residuals alive until the block's quotients
+// are final, eight more registers.  The 8-slot forms and the 16-slot form without an LDS part have them (245 of 256 for
+// <16, false> at two waves per SIMD); <16, true> and the 32 / 80-slot forms would spill, so they never take dstP (host:
+// launch_boxf_ks() asks here) and their code is what it was.
+__host__ __device__ constexpr bool boxf_panel_ok(int ks, bool hasl) { return ks <= 8 || (ks == 16 && !hasl); }
 template <int KS, bool HASL, int MODE, int WPS = boxr_waves_f(KS)>   // WPS: waves per SIMD the registers are budgeted for
 __global__ void __launch_bounds__(64, WPS)
 k_boxf(const float* __restrict__ srcW, unsigned img_gap,
        float* __restrict__ dstW, float* __restrict__ dstO, const float* __restrict__ data,
        int n, int C, int ld, int r, BoxDenom denom, size_t sws_img, size_t dws, size_t ws_data,
-       uint8_t* __restrict__ nanflag) {
+       uint8_t* __restrict__ nanflag, float* __restrict__ dstP, size_t pws) {
     extern __shared__ float cf_ring[];
     constexpr int PF = boxr_pf_f(KS);
+    static_assert(MODE != 2 || (PF / 2) % 4 == 0, "panel output: groups of four positions per lane");
     // Staging granularity: NSUB blocks of PF positions per load.  With PF = 16 a staging instruction takes 64 of a
     // line's 128 bytes and the other half is fetched again a block later -- 60 % of the time from HBM (traffic 1.30 x
     // algorithmic, profiles/r03_fetch_calibration.txt); NSUB = 2 stages whole 128-byte lines every second block.
@@ -356,6 +366,9 @@ k_boxf(const float* __restrict__ srcW, unsigned img_gap,
         (void*)(dstO + win * dws), 0, (int)((unsigned)n * rowb), 0x00020000);
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(dstW + win * dws), 0, (int)((unsigned)n * rowb), 0x00020000);
+    const bool panel = MODE == 2 && boxf_panel_ok(KS, HASL) && dstP != nullptr;
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(panel ? dstP + win * pws : dstW), 0, panel ? (int)((unsigned)n * rowb) : 0, 0x00020000);
 
     // staging: element e = j * 32 + hl of this half's [32 lines][PF positions] patch: line = e / PF,
     // position = e % PF -> PF consecutive lanes read PF * 4 contiguous bytes of one row.
@@ -469,6 +482,7 @@ k_boxf(const float* __restrict__ srcW, unsigned img_gap,
                     wave_sync();                                 // both halves' outputs in the tiles
                     const int i0 = m0 - 3 - 4 * r;
                     unsigned long long okmask = ~0ull, active = 0;
+                    float res[MODE == 2 ? PF / 2 : 1];
                     auto finish = [&](auto ieee_tag) {
                         constexpr bool IEEE = decltype(ieee_tag)::value;
 #pragma unroll
@@ -487,7 +501,8 @@ k_boxf(const float* __restrict__ srcW, unsigned img_gap,
                                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fabsf(dpre[k] - bg)), ors, vo, so, BOXF_STREAM_AUX);
                                 } else {
                                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, bg), ors, vo, so, BOXF_STREAM_AUX);
-                                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dpre[k] - bg), wrs, vo, so, BOXF_STREAM_AUX);
+                                    res[MODE == 2 ? k : 0] = dpre[k] - bg;
+                                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, res[MODE == 2 ? k : 0]), wrs, vo, so, BOXF_STREAM_AUX);
                                     line_nan |= isnan(bg);
                                 }
                             }
@@ -497,6 +512,26 @@ k_boxf(const float* __restrict__ srcW, unsigned img_gap,
                     finish(std::false_type{});
                     // some quotient fell outside the reciprocal scheme's proven range: redo the block (rare)
                     if ((okmask & active) != active) finish(std::true_type{});
+                    if (MODE == 2 && panel && colok) {
+                        // element (position i, line c) of the panel image: ((i >> 6) * C + c) * 64 + (i & 63)
+                        auto paddr = [&](int i) { return (int)((((unsigned)(i >> 6) * (unsigned)C + (unsigned)c) << 8) + ((unsigned)(i & 63) << 2)); };
+#pragma unroll
+                        for (int g = 0; g < PF / 8; g++) {
+                            const int ig = i0 + hrow + 4 * g;
+                            if (fast && (ig & 63) <= 60) {
+                                typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                                u4 y;
+#pragma unroll
+                                for (int e = 0; e < 4; e++) y[e] = __builtin_bit_cast(unsigned, res[MODE == 2 ? 4 * g + e : 0]);
+                                __builtin_amdgcn_raw_buffer_store_b128(y, prs, paddr(ig), 0, BOXF_STREAM_AUX);
+                            } else {
+#pragma unroll
+                                for (int e = 0; e < 4; e++)
+                                    if (fast || (ig + e >= 0 && ig + e < n))
+                                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, res[MODE == 2 ? 4 * g + e : 0]), prs, paddr(ig + e), 0, BOXF_STREAM_AUX);
+                            }
+                        }
+                    }
                 }
             }
         }

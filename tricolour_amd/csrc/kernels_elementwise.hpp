@@ -241,11 +241,13 @@ __global__ void k_reject(const float* __restrict__ resid, uint8_t* __restrict__ 
 // K6  _linearly_interpolate_nans1d (flagging.py:307-344) along the line axis
 // of [L][C], one thread per column.  numba typing: grad = (f32 - f32) / int64
 // -> float64; value = f32(f32 + int64 * f64) evaluated in float64.
+// `panel` (with `resid`, L % 64 == 0): a second copy of the residual kept as column panels [L / 64][C][64] (see
+// k_transpose<T, true>), window stride ws_panel -- it receives the redone values too.
 // grid (ceil(C/256), W)
 // ---------------------------------------------------------------------------
 __global__ void k_colinterp(float* __restrict__ a, int L, int C, size_t ws,
                             const uint8_t* __restrict__ nanflag, const float* __restrict__ data,
-                            size_t ws_data, float* __restrict__ resid) {
+                            size_t ws_data, float* __restrict__ resid, float* __restrict__ panel, size_t ws_panel) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     if (nanflag && !nanflag[(size_t)blockIdx.y * C + c]) return;   // no NaN in this line
@@ -299,6 +301,10 @@ __global__ void k_colinterp(float* __restrict__ a, int L, int C, size_t ws,
             for (int u = 0; u < PFI; u++) rr[(size_t)(j + u) * Cs] = dv[u] - xv[u];
         }
         for (; j < L; j++) rr[(size_t)j * Cs] = d[(size_t)j * Cs] - x[(size_t)j * Cs];
+        if (panel) {
+            float* pp = panel + (size_t)blockIdx.y * ws_panel + (size_t)c * 64;
+            for (j = 0; j < L; j++) pp[(size_t)(j >> 6) * Cs * 64 + (j & 63)] = rr[(size_t)j * Cs];
+        }
     }
 }
 
@@ -345,7 +351,8 @@ __global__ void k_interp_scan(const float* __restrict__ a, int L, int C, size_t 
 }
 
 __global__ void k_interp_fix(float* __restrict__ a, int L, int C, size_t ws, const int* __restrict__ tab,
-                             const float* __restrict__ data, size_t ws_data, float* __restrict__ resid) {
+                             const float* __restrict__ data, size_t ws_data, float* __restrict__ resid,
+                             float* __restrict__ panel, size_t ws_panel) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C) return;
     const int seg = blockIdx.y, nseg = gridDim.y;
@@ -355,10 +362,15 @@ __global__ void k_interp_fix(float* __restrict__ a, int L, int C, size_t ws, con
     float* x = a + (size_t)blockIdx.z * ws + c;
     const float* d = resid ? data + (size_t)blockIdx.z * ws_data + c : nullptr;
     float* rr = resid ? resid + (size_t)blockIdx.z * ws + c : nullptr;
+    float* pp = (resid && panel) ? panel + (size_t)blockIdx.z * ws_panel + (size_t)c * 64 : nullptr;
     const size_t Cs = (size_t)C;
     auto put = [&](int j, float v) {
         x[(size_t)j * Cs] = v;
-        if (resid) rr[(size_t)j * Cs] = d[(size_t)j * Cs] - v;
+        if (resid) {
+            const float dr = d[(size_t)j * Cs] - v;
+            rr[(size_t)j * Cs] = dr;
+            if (pp) pp[(size_t)(j >> 6) * Cs * 64 + (j & 63)] = dr;
+        }
     };
     // positions [lo, hi) between the valid samples (last, lastv) and (i, v); last < 0: none before
     auto fill = [&](int lo, int hi, int last, float lastv, int i, float v) {

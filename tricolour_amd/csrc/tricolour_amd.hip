@@ -173,6 +173,10 @@ struct Ws {
     // per-window images
     float *dataTF, *dataFT, *Aw, *Ao, *Bw, *Bo;
     uint8_t *iter, *flagsTF, *flagsFT, *bgfTF, *bgfFT, *tflTF, *fflFT, *fflTF, *comb, *dil;
+    // Time-major residual as column panels, written by the final frequency stage (window stride T * Fa).  No memory of
+    // its own: it lies over bgfTF | bgfFT | comb | dil, four byte images that are dead from the final pass's frequency
+    // stage until the combine / dilate pass on the route that uses it.
+    float* residP;
     int *rowcnt, *colcnt;
     double* med;      // medians: max(Fa, T*G) per window
     // spectrum layout [Fa][Wb]
@@ -221,13 +225,15 @@ static void carve(const Plan& pl, int64_t Wb, void* base, size_t cap, bool dry, 
     ws->Bo = b.get<float>(W * (size_t)pl.PF * T);
     ws->flagsTF = b.get<uint8_t>(W * N);
     ws->flagsFT = b.get<uint8_t>(W * N);
-    ws->bgfTF = b.get<uint8_t>(W * N);
-    ws->bgfFT = b.get<uint8_t>(W * N);
     ws->tflTF = b.get<uint8_t>(W * N);
     ws->fflFT = b.get<uint8_t>(W * N);
     ws->fflTF = b.get<uint8_t>(W * N);
+    // (these four next to each other: together they hold ws->residP, T * F >= N)
+    ws->bgfTF = b.get<uint8_t>(W * N);
+    ws->bgfFT = b.get<uint8_t>(W * N);
     ws->comb = b.get<uint8_t>(W * N);
     ws->dil = b.get<uint8_t>(W * T * F);
+    ws->residP = dry ? nullptr : reinterpret_cast<float*>(ws->bgfTF);
     ws->rowcnt = b.get<int>(W * T);
     ws->colcnt = b.get<int>(W * F);
     ws->nanmask = b.get<uint16_t>(W * N / 16 + 8);
@@ -1009,15 +1015,15 @@ int launch_colst(const Run& r, const StWin& sw, const float* data, const double*
 
 // _linearly_interpolate_nans1d along the line axis of [L][C] images (K6 / K6p)
 int launch_interp(const Run& r, float* a, int L, int C, size_t ws, int64_t W, const uint8_t* nanflag,
-                  const float* data, size_t ws_data, float* resid) {
+                  const float* data, size_t ws_data, float* resid, float* panel = nullptr, size_t ws_panel = 0) {
     static const bool one_pass = [] { const char* e = getenv("TRI_INTERP_ONE_PASS"); return e && e[0] == '1'; }();
     const int nseg = (int)cdiv(L, INTERP_SEG);
     if (one_pass || nseg < 2 || nseg > 65535) {
-        hipLaunchKernelGGL(k_colinterp, dim3((unsigned)cdiv(C, 256), (unsigned)W), dim3(256), 0, r.st, a, L, C, ws, nanflag, data, ws_data, resid);
+        hipLaunchKernelGGL(k_colinterp, dim3((unsigned)cdiv(C, 256), (unsigned)W), dim3(256), 0, r.st, a, L, C, ws, nanflag, data, ws_data, resid, panel, ws_panel);
     } else {
         dim3 grid((unsigned)cdiv(C, 64), (unsigned)nseg, (unsigned)W);
         hipLaunchKernelGGL(k_interp_scan, grid, dim3(64), 0, r.st, (const float*)a, L, C, ws, nanflag, r.ws.itab);
-        hipLaunchKernelGGL(k_interp_fix, grid, dim3(64), 0, r.st, a, L, C, ws, (const int*)r.ws.itab, data, ws_data, resid);
+        hipLaunchKernelGGL(k_interp_fix, grid, dim3(64), 0, r.st, a, L, C, ws, (const int*)r.ws.itab, data, ws_data, resid, panel, ws_panel);
     }
     LAUNCHCHK();
     return TRI_OK;
@@ -1140,9 +1146,13 @@ int launch_colfilter_tf(const Run& r, const float* srcW, const float* srcO, floa
 // Register-ring form of the fused stage (K4r, k_boxf): any radius boxr_pick_ks() accepts.
 template <int KS, int MODE>
 int launch_boxf_ks(const Run& r, const float* srcW, const float* srcO, float* dstW, float* dstO, const float* data,
-                   int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag) {
+                   int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag,
+                   float* dstP, size_t pws, bool* wroteP) {
     const BoxDenom denom = box_reciprocal(box_denominator(rad));
     const int d = 2 * rad - KS;
+    // (the panel output only where the kernel has the registers for it: see boxf_panel_ok())
+    if (!(MODE == 2 && boxf_panel_ok(KS, d > 0))) dstP = nullptr;
+    if (dstP && wroteP) *wroteP = true;
     const size_t lds = ((size_t)4 * d * 64 + (size_t)2 * boxr_pf_f(KS) * boxf_nsub(KS) * boxf_ts(boxr_pf_f(KS) * boxf_nsub(KS))) * sizeof(float);
     // one descriptor per window spans both images: the data image must follow the weight image closely
     if (srcO <= srcW || ((uint64_t)(srcO - srcW) + (uint64_t)C * ld) * 4u >= (1ull << 31))
@@ -1161,17 +1171,17 @@ int launch_boxf_ks(const Run& r, const float* srcW, const float* srcO, float* ds
                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             HIPCHK(attr1);
             hipLaunchKernelGGL((k_boxf<KS, true, MODE, 1>), grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
-                               denom, sws_img, dws, ws_data, nanflag);
+                               denom, sws_img, dws, ws_data, nanflag, dstP, pws);
             one_wave = true;
         }
     }
     if (one_wave) {
     } else if (d > 0)
         hipLaunchKernelGGL((k_boxf<KS, true, MODE>), grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
-                           denom, sws_img, dws, ws_data, nanflag);
+                           denom, sws_img, dws, ws_data, nanflag, dstP, pws);
     else
         hipLaunchKernelGGL((k_boxf<KS, false, MODE>), grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
-                           denom, sws_img, dws, ws_data, nanflag);
+                           denom, sws_img, dws, ws_data, nanflag, dstP, pws);
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -1208,7 +1218,11 @@ int launch_boxqf_ks(const Run& r, const float* srcW, unsigned gap, float* dstW, 
 
 template <int MODE>
 int launch_boxf(const Run& r, int ks, const float* srcW, const float* srcO, float* dstW, float* dstO, const float* data,
-                int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag) {
+                int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag,
+                float* dstP = nullptr, size_t pws = 0, bool* wroteP = nullptr) {
+    // MODE 2, dstP: the register-ring kernel (K4r) also writes the residual as column panels [n / 64][C][64] where it has
+    // the registers for it, and says so in *wroteP; the stage pipeline (K4qf) has no such output and leaves *wroteP alone
+    if (MODE != 2 || n % 64 != 0) dstP = nullptr;
     {
         static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_PIPE_F"); return e && e[0] == '1'; }();
         const int kq = boxq_pick_ks(rad);
@@ -1255,11 +1269,11 @@ int launch_boxf(const Run& r, int ks, const float* srcW, const float* srcO, floa
         }
     }
     switch (ks) {
-        case 8: return launch_boxf_ks<8, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-        case 16: return launch_boxf_ks<16, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-        case 32: return launch_boxf_ks<32, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-        case 64: return launch_boxf_ks<64, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-        case 80: return launch_boxf_ks<80, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
+        case 8: return launch_boxf_ks<8, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
+        case 16: return launch_boxf_ks<16, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
+        case 32: return launch_boxf_ks<32, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
+        case 64: return launch_boxf_ks<64, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
+        case 80: return launch_boxf_ks<80, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
     }
     return set_err(TRI_EINVAL, "no register-ring kernel for %d slots", ks);
 }
@@ -1466,7 +1480,9 @@ static bool bg_flags_packed(int T, size_t N) {
     return !no_pack && (T % 4 == 0) && (N % 4 == 0);
 }
 
-int background2d(const Run& r, bool flagsFT_current) {
+// residP (optional): where the final frequency stage may leave the residual a second time, as column panels
+// [Fa / 64][T][64] with window stride N; *wroteP tells whether it did (only the register-ring kernel K4r can).
+int background2d(const Run& r, bool flagsFT_current, float* residP = nullptr, bool* wroteP = nullptr) {
     const Plan& pl = r.pl;
     const Ws& ws = r.ws;
     int T = (int)pl.T, Fa = (int)pl.Fa, G = (int)pl.G;
@@ -1479,27 +1495,55 @@ int background2d(const Run& r, bool flagsFT_current) {
     // ("TF4": [T/4][Fa] uint32) -- which is exactly the 32-bit transpose of the
     // FT byte image viewed as [Fa][T/4] words.
     const bool packed = bg_flags_packed(T, N);
-    int rc = flagsFT_current ? launch_u8<0>(r, ws.flagsFT, ws.bgfFT, N, N, N, W)
+    // The routes of the loop below that depend on the plan alone, picked once.
+    // fused frequency stage (register ring) and exact row filter of a frequency radius (see the loop)
+    auto ksf_of = [&](int r1) { return ((uint64_t)N * 4u < (1ull << 31) && ((uint64_t)(ws.Ao - ws.Aw) + N) * 4u < (1ull << 31)) ? boxr_pick_ks_f(r1) : 0; };
+    auto xl_of = [&](int r1) { return (r1 > 0 && (!ksf_of(r1) || r1 >= BOXX_MIN_R) && (!r.ampl_cached || r.data_mask)) ? boxx_pick_l(r1, Fa) : 0; };
+    static const bool no_fuse = [] { const char* e = getenv("TRI_NO_FUSED_REJECT"); return e && e[0] == '1'; }();
+    static const bool no_tile = [] { const char* e = getenv("TRI_NO_TILE_MEDREJ"); return e && e[0] == '1'; }();
+    static const bool no_medrej = [] { const char* e = getenv("TRI_FUSED_MEDREJ"); return !(e && e[0] == '1'); }();
+    static const int medrej_fallback = [] { const char* e = getenv("TRI_MEDREJ_FORCE_FALLBACK"); return e ? atoi(e) : 0; }();
+    // K3t (tile-parallel median + rejection, see the loop): scratch sizes and whether the rejection iterations take it
+    const size_t mr_nb = (size_t)pl.maxchunk * T;                  // samples of the largest block
+    const size_t ccap = (mr_nb / 4) & ~(size_t)3, ucap = (mr_nb / 8) & ~(size_t)3;
+    int ytiles = 0;
+    for (int g = 0; g < G; g++) ytiles += (int)cdiv(r.p->chunk_ends[g + 1] - r.p->chunk_ends[g], 64);
+    // (blocks too small to predict from -- fewer than 65536 samples -- would all take the redo path: the two-kernel route)
+    const bool tile_route = r.pl.vec && wsB % 4 == 0 && wsA % 4 == 0 && packed && !no_fuse && !no_tile && no_medrej && G <= 65535 &&
+                            mrt_scratch_words(G, ccap, ucap) <= wsA && (medrej_fallback || (pl.maxchunk - 1) * (int64_t)T >= 65536) &&
+                            ytiles > 0 && ytiles <= 65535;
+    // K3t never modifies the flags it reads (cur_ft in, alt_ft out, then the two swap), so its first iteration can read
+    // ws.flagsFT where it lies and the copy into ws.bgfFT is not needed.  Only when every rejection iteration is sure to
+    // take that route: the FT-native rejections (k_reject4_t, k_reject4, k_reject) and the rebuild after rows-only
+    // iterations (bgf_ft_stale, K4x) write into cur_ft.  TRI_BG_COPY_FLAGS=1 restores the copy (A/B runs).
+    static const bool copy_flags = [] { const char* e = getenv("TRI_BG_COPY_FLAGS"); return e && e[0] == '1'; }();
+    bool flags_in_place = flagsFT_current && !copy_flags && packed && tile_route;
+    for (int ext = pl.nit; ext >= 1 && flags_in_place; ext--)
+        if (xl_of((int)box_radius((double)ext * r.p->spike_width_freq)) > 0) flags_in_place = false;
+    int rc = TRI_OK;
+    if (!flags_in_place)
+        rc = flagsFT_current ? launch_u8<0>(r, ws.flagsFT, ws.bgfFT, N, N, N, W)
                              : launch_transpose<uint8_t>(r, ws.flagsTF, ws.bgfFT, T, Fa, N, N, W);
     if (rc) return rc;
     if (packed) {
-        rc = launch_transpose<float>(r, reinterpret_cast<const float*>(ws.bgfFT), reinterpret_cast<float*>(ws.bgfTF), Fa, T / 4, N / 4, N / 4, W);
+        rc = launch_transpose<float>(r, reinterpret_cast<const float*>(flags_in_place ? ws.flagsFT : ws.bgfFT), reinterpret_cast<float*>(ws.bgfTF), Fa, T / 4, N / 4, N / 4, W);
         if (rc) return rc;
     } else {
         rc = launch_u8<0>(r, ws.flagsTF, ws.bgfTF, N, N, N, W);
         if (rc) return rc;
     }
     double rej = TRI_MAD_NORMAL * r.p->background_reject;
+    bool wrote_panel = false;            // the final frequency stage left the residual in residP as well
     bool bgf_ft_stale = false;           // the FT flag bytes lag behind the TF4 words (rows-only rejection iterations)
     // K3r (round 4): block median + rejection in ONE pass over |data - background| (kernels_reject.hpp).  It writes the updated FT
     // flags to a SECOND image (its fallback redoes a block from the input flags), so the FT flag image alternates between
     // ws.bgfFT and ws.fflFT (free until the frequency-axis SumThreshold writes it).  TRI_FUSED_MEDREJ=1 switches it on.
     // (opt-in for now, TRI_FUSED_MEDREJ=1: one workgroup per block does not stream fast enough -- 3.7 against 3.0 ms per 252
     //  windows for the two kernels, scripts/ubench/medrej_dev.hip)
-    static const bool no_medrej = [] { const char* e = getenv("TRI_FUSED_MEDREJ"); return !(e && e[0] == '1'); }();
-    static const int medrej_fallback = [] { const char* e = getenv("TRI_MEDREJ_FORCE_FALLBACK"); return e ? atoi(e) : 0; }();
-    uint8_t* cur_ft = ws.bgfFT;
-    uint8_t* alt_ft = ws.fflFT;
+    // (read in place, ws.flagsFT stays as it is -- the time medians of the residual read it: the first iteration writes
+    //  ws.bgfFT, and from then on ws.bgfFT and ws.fflFT alternate)
+    uint8_t* cur_ft = flags_in_place ? ws.flagsFT : ws.bgfFT;
+    uint8_t* alt_ft = flags_in_place ? ws.bgfFT : ws.fflFT;
     for (int ext = pl.nit; ext >= 0; ext--) {
         bool final_pass = ext == 0;
         double e = (double)(final_pass ? 1 : ext);
@@ -1514,9 +1558,9 @@ int background2d(const Run& r, bool flagsFT_current) {
         bool direct_ft = false;
         // frequency stage able to read the time stage's TF images itself (no transposes)
         // register-ring fused frequency stage (signed 32-bit buffer offsets: window below 2^31 bytes)
-        const int ksf = ((uint64_t)N * 4u < (1ull << 31) && ((uint64_t)(ws.Ao - ws.Aw) + N) * 4u < (1ull << 31)) ? boxr_pick_ks_f(r1) : 0;
+        const int ksf = ksf_of(r1);
         // exact row filter (K4x) where the stage pipelines end: rows of the time stage's TF images in, rows out
-        const int xl = (r1 > 0 && (!ksf || r1 >= BOXX_MIN_R) && (!r.ampl_cached || r.data_mask)) ? boxx_pick_l(r1, Fa) : 0;
+        const int xl = xl_of(r1);
         // ... whose rejection iterations then stay in the row layout altogether (TRI_FILTER_NO_TF_REJECT=1: transposes + FT kernels)
         static const bool no_tfr = [] { const char* e = getenv("TRI_FILTER_NO_TF_REJECT"); return e && e[0] == '1'; }();
         const bool tf_native = xl > 0 && !final_pass && packed && !no_tfr && G <= 65535 && (uint64_t)T * Fa * 4u < (1ull << 31);
@@ -1619,7 +1663,8 @@ int background2d(const Run& r, bool flagsFT_current) {
         } else if (fused_div) {
             if (final_pass) {
                 HIPCHK(hipMemsetAsync(ws.rowcnt, 0, (size_t)W * T, r.st));
-                if (ksf) rc = launch_boxf<2>(r, ksf, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, reinterpret_cast<uint8_t*>(ws.rowcnt));
+                if (ksf) rc = launch_boxf<2>(r, ksf, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, reinterpret_cast<uint8_t*>(ws.rowcnt),
+                                             residP, N, &wrote_panel);
                 else rc = launch_colfilter_tf<2>(r, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, reinterpret_cast<uint8_t*>(ws.rowcnt));
             } else {
                 if (ksf) rc = launch_boxf<1>(r, ksf, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, nullptr);
@@ -1654,18 +1699,11 @@ int background2d(const Run& r, bool flagsFT_current) {
                 rc = launch_masked_div<1>(r, ws.Bw, ws.Bo, ws.dataFT, N, wsB, N, W, den_f);
                 if (rc) return rc;
             }
-            static const bool no_fuse = [] { const char* e = getenv("TRI_NO_FUSED_REJECT"); return e && e[0] == '1'; }();
-            static const bool no_tile = [] { const char* e = getenv("TRI_NO_TILE_MEDREJ"); return e && e[0] == '1'; }();
-            if (r.pl.vec && wsB % 4 == 0 && wsA % 4 == 0 && packed && !no_fuse && !no_tile && no_medrej && G <= 65535) {
+            {
                 // K3t: median + rejection + TF4 re-pack in one pass over |data - background|, tile-parallel (kernels_reject_tile.hpp):
                 // predict (per block) -> pass (per 64 x 64-word tile) -> finish (per block) -> redo of the blocks that failed a check.
                 // Scratch: the dead time-stage images of the window.
-                const size_t nb = (size_t)pl.maxchunk * T;                 // samples of the largest block
-                const size_t ccap = (nb / 4) & ~(size_t)3, ucap = (nb / 8) & ~(size_t)3;
-                int ytiles = 0;
-                for (int g = 0; g < G; g++) ytiles += (int)cdiv(r.p->chunk_ends[g + 1] - r.p->chunk_ends[g], 64);
-                // (blocks too small to predict from -- fewer than 65536 samples -- would all take the redo path: the two kernels below)
-                if (mrt_scratch_words(G, ccap, ucap) <= wsA && (medrej_fallback || (pl.maxchunk - 1) * (int64_t)T >= 65536) && ytiles > 0 && ytiles <= 65535) {
+                if (tile_route) {
                     unsigned* sc = reinterpret_cast<unsigned*>(ws.Aw);
                     hipLaunchKernelGGL(k_mr_predict, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)cur_ft,
                                        ws.d_chunk_ends, rej, T / 4, G, wsB, N, sc, wsA, ccap, ucap, medrej_fallback);
@@ -1680,9 +1718,11 @@ int background2d(const Run& r, bool flagsFT_current) {
                                        (const unsigned*)sc, wsA, (int)MRT_PARW, 11);
                     LAUNCHCHK();
                     std::swap(cur_ft, alt_ft);
+                    if (alt_ft == ws.flagsFT) alt_ft = ws.fflFT;
                     continue;
                 }
             }
+            if (flags_in_place) return set_err(TRI_EUNSUPPORTED, "internal: background flags read in place on a route that rewrites them");
             {
                 // one pass: median + rejection + TF4 re-pack (K3r).  Scratch per (window, chunk) block: the dead time-stage
                 // images, half for the window's keys, half for the undecided samples' indices
@@ -1727,7 +1767,10 @@ int background2d(const Run& r, bool flagsFT_current) {
             if (rc) return rc;
         }
     }
-    return launch_interp(r, ws.Bo, Fa, T, wsB, W, reinterpret_cast<const uint8_t*>(ws.rowcnt), (const float*)ws.dataFT, N, ws.Bw);
+    if (wroteP) *wroteP = wrote_panel;
+    // (a repaired line's residual is redone: in the panel image too)
+    return launch_interp(r, ws.Bo, Fa, T, wsB, W, reinterpret_cast<const uint8_t*>(ws.rowcnt), (const float*)ws.dataFT, N, ws.Bw,
+                         wrote_panel ? residP : nullptr, N);
 }
 
 // One major iteration (_get_flags_impl, flagging.py:745-781) for a batch.
@@ -1824,15 +1867,6 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     // (K4x masks rows of the unmasked TF amplitudes with the iteration's input flags: same layout when nothing is averaged)
     r.data_mask = (r.ampl_cached && Fa == F) ? iter_flags : nullptr;
     r.data_mask_ws = N;
-    rc = background2d(r, ft_current);
-    if (rc) return rc;
-    if (tap && r.dbg) {
-        HIPCHK(hipMemcpyAsync(r.dbg->f32 + Fa, ws.Bo, N * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-    }
-    // the residual data - background was written by the final masked division
-    // (and redone by the interpolation pass on repaired lines) into ws.Bw
-    float* residFT = ws.Bw;   // window stride wsB
-    float* residTF = ws.Aw;   // window stride N (the time-axis scratch is free again)
     // Column panels for the time-axis SumThreshold (round 4): the TF residual and the time flags as [Fa / 64][T][64], so the
     // column kernel's row walk is one linear stream.  Who else touches the two images reads panels too: the frequency-axis MAD
     // (wave medians over row segments: an aligned group of four channels is contiguous either way) and the fused combine /
@@ -1842,8 +1876,27 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     const bool panel_t = !st_no_panel() && defer_tf && !no_fused_or_p && !no_fdil_p && Fa % 64 == 0 && Fa == F &&
                          median_takes_extra_flags(pl.maxchunk + 3) && st_use_fused(pl.swT) && st_use_mask(T, Fa) &&
                          [&] { int64_t e = p->freq_extend; int64_t h = e >= 0 ? e / 2 : -((-e + 1) / 2); return -h == -1 && -h + e == 2; }();
-    rc = launch_transpose<float>(r, residFT, residTF, Fa, T, wsB, N, W, 0.0f, panel_t);
+    // The final frequency stage of the background holds every residual value in a register: where it is the register-ring
+    // kernel (K4r) it writes the panel image itself and the transpose below is not run.  The image lies over byte images that
+    // are dead by then (ws.residP, see carve()): this route never reads ws.comb, and ws.dil is written after the last reader.
+    // Measured on the 252-baseline slab the third store stream costs that kernel as much as the transpose it saves (DESIGN.md
+    // section 4), so the transpose stays the default route: TRI_NO_FUSED_RESID_TF=0 switches the fused write on, unset or 1
+    // keeps the transpose (A/B runs, tests).
+    static const bool no_fused_resid = [] { const char* e = getenv("TRI_NO_FUSED_RESID_TF"); return !(e && e[0] == '0'); }();
+    bool wrote_panel = false;
+    rc = background2d(r, ft_current, (panel_t && !no_fused_resid) ? ws.residP : nullptr, &wrote_panel);
     if (rc) return rc;
+    if (tap && r.dbg) {
+        HIPCHK(hipMemcpyAsync(r.dbg->f32 + Fa, ws.Bo, N * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+    }
+    // the residual data - background was written by the final masked division
+    // (and redone by the interpolation pass on repaired lines) into ws.Bw
+    float* residFT = ws.Bw;   // window stride wsB
+    float* residTF = wrote_panel ? ws.residP : ws.Aw;   // window stride N (ws.Aw: the time-axis scratch is free again)
+    if (!wrote_panel) {
+        rc = launch_transpose<float>(r, residFT, residTF, Fa, T, wsB, N, W, 0.0f, panel_t);
+        if (rc) return rc;
+    }
 
     // flagging.py:964  SumThreshold along time.  MAD per channel over time =
     // contiguous rows of the FT layout; flags = input | spectral flags.
