@@ -324,6 +324,47 @@ int tri_scale_invariant_rank(const uint8_t *flags, uint8_t *out_flags,
                              double eta_time, double eta_freq,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Line-RMS statistics of (n_win, ntime, nchan) windows and the thresholding
+ * of whole timesteps and whole channels on them (beyond the reference; the
+ * model is AOFlagger's threshold_timestep_rms / threshold_channel_rms, the
+ * definition is this library's own).  Per window, visibilities v (complex64,
+ * or float32 amplitudes) and uint8 flags f (nonzero = flagged):
+ *   p    = (double)re * (double)re + (double)im * (double)im   (a * a for
+ *          amplitudes); a sample counts if f == 0 and p is not NaN
+ *   rms  = sqrt(sum p / n) in float64 over the n counting samples of a time
+ *          row (over channels) or of a channel (over times); NaN when n == 0.
+ *          The order of the sum is fixed by the shape alone: no atomics, the
+ *          same bits on every run and for every split of the windows.
+ *   per axis: usable lines are those with a finite rms; med = their median
+ *          (even count: (a + b) / 2), sigma = 1.4826 * median(|rms - med|).
+ *          A usable line is bad if |rms - med| > nsigma * sigma (flag_low
+ *          nonzero) or rms - med > nsigma * sigma (flag_low zero) -- unless
+ *          the axis is inert: nsigma == 0, fewer than 3 usable lines, or
+ *          sigma > 1e-9 * med does not hold.  A non-empty line whose rms is
+ *          not finite is bad whenever nsigma > 0.
+ *   out_flags = f | bad_time[t] | bad_chan[c]   (0/1; both axes read f)
+ * tri_line_rms writes the statistics only: rms_time (n_win, ntime) and
+ * rms_chan (n_win, nchan) float64, and the counts n as int32 where count_time
+ * / count_chan are not NULL.  TRI_EINVAL for NULL pointers (other than the
+ * counts), negative shapes, nsigma negative or NaN, out_flags overlapping
+ * flags; TRI_EUNSUPPORTED for other dtypes and for more lines than one launch
+ * holds (pass fewer windows per call); TRI_EWORKSPACE when workspace_bytes <
+ * tri_line_rms_workspace_bytes().  Empty shapes return TRI_OK without a
+ * launch.
+ */
+size_t tri_line_rms_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan);
+int tri_line_rms(const void *vis, int vis_dtype, const uint8_t *flags,
+                 int64_t n_win, int64_t ntime, int64_t nchan,
+                 double *rms_time, double *rms_chan,
+                 int32_t *count_time, int32_t *count_chan,
+                 void *workspace, size_t workspace_bytes, void *stream);
+int tri_line_rms_threshold(const void *vis, int vis_dtype, const uint8_t *flags,
+                           uint8_t *out_flags, int64_t n_win, int64_t ntime,
+                           int64_t nchan, double nsigma_time, double nsigma_freq,
+                           int flag_low, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

@@ -727,3 +727,97 @@ def scale_invariant_rank_operator(flags, eta_time=0.2, eta_freq=0.2):
                     eta_time, eta_freq, ws.data_ptr() if ws is not None else None,
                     ws.numel() if ws is not None else 0, stream))
     return _like_flags(torch, out, flags, from_numpy)
+
+
+def _line_rms_inputs(name, vis, flags):
+    """Shape checks (before any device work) and device inputs of the line-RMS calls."""
+    shape = tuple(vis.shape)
+    if len(shape) != 4:
+        raise ValueError("vis must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    if tuple(flags.shape) != shape:
+        raise ValueError("vis and flags must have the same shape, got %s and %s" % (shape, tuple(flags.shape)))
+    torch = _require_gpu()
+    v, _, code, from_numpy, device = _as_device_inputs(torch, vis, flags)
+    if code not in (_lib.TRI_VIS_C64, _lib.TRI_VIS_F32):
+        raise TypeError("tricolour_amd.%s: visibilities must be complex64 or float32" % name)
+    return torch, v, _flags_u8(torch, flags, device), code, from_numpy, device
+
+
+def _line_rms_batch(torch, lib, device, n_win, ntime, nchan, max_windows=None):
+    """Windows per call: as many as the workspace budget and one launch hold (a launch holds 2^24 blocks: one per
+    time row in the apply pass, one per 64 x 1024 tile in the power pass)."""
+    tiles = -(-ntime // 64) * -(-nchan // 1024)
+    batch = max(1, min(n_win, ((1 << 24) - 1) // max(ntime, tiles), ((1 << 31) - 1) // (ntime + nchan)))
+    if max_windows:
+        batch = max(1, min(batch, int(max_windows)))
+    budget = _workspace_budget(torch, device)
+    while batch > 1 and lib.tri_line_rms_workspace_bytes(batch, ntime, nchan) > budget:
+        batch = (batch + 1) // 2
+    return batch, lib.tri_line_rms_workspace_bytes(batch, ntime, nchan)
+
+
+def line_rms(vis, flags, _max_windows=None):
+    """RMS of every time row (over channels) and of every channel (over times)
+    of (bl, corr, time, chan) windows, over the unflagged, non-NaN samples:
+    ``sqrt(sum |v|^2 / n)`` in float64 (float32 input: amplitudes).  Returns
+    ``(rms_time (bl, corr, time), rms_chan (bl, corr, chan))``, NaN for lines
+    without a counting sample -- numpy arrays for numpy input, tensors on the
+    device otherwise.  The sums run in a fixed order: the same bits on every
+    run and for every batch size.  Inputs are not modified."""
+    torch, v, f8, code, from_numpy, device = _line_rms_inputs("line_rms", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    rms_t = torch.empty((nbl, ncorr, ntime), dtype=torch.float64, device=device)
+    rms_c = torch.empty((nbl, ncorr, nchan), dtype=torch.float64, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, nbytes = _line_rms_batch(torch, lib, device, n_win, ntime, nchan, _max_windows)
+            ws = _workspace(torch, device, nbytes)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_line_rms(
+                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
+                    rms_t.data_ptr() + w0 * ntime * 8, rms_c.data_ptr() + w0 * nchan * 8, None, None,
+                    ws.data_ptr(), ws.numel(), stream))
+    if from_numpy:
+        return rms_t.cpu().numpy(), rms_c.cpu().numpy()
+    return rms_t, rms_c
+
+
+def threshold_line_rms(vis, flags, nsigma_time=3.5, nsigma_freq=3.0, flag_low=True):
+    """Flags whole timesteps and whole channels of (bl, corr, time, chan)
+    windows on their RMS (after AOFlagger's ``threshold_timestep_rms`` /
+    ``threshold_channel_rms``).  Per window and axis the line RMS values of
+    :func:`line_rms` give ``med`` and ``sigma = 1.4826 * MAD``; a line is
+    flagged when ``|rms - med| > nsigma * sigma`` (``flag_low=False``: only
+    ``rms - med > nsigma * sigma``).  An axis with ``nsigma = 0``, with fewer
+    than 3 finite lines or with ``sigma <= 1e-9 * med`` flags nothing, except
+    that a line holding an unflagged infinite sample is always flagged when
+    ``nsigma > 0``.  Both axes read the input flags:
+    ``out = flags | bad_time | bad_chan``.  Returns a new array in the
+    container / dtype of ``flags``; the inputs are not modified."""
+    nsigma_time, nsigma_freq = float(nsigma_time), float(nsigma_freq)
+    for name, ns in (("nsigma_time", nsigma_time), ("nsigma_freq", nsigma_freq)):
+        if not ns >= 0.0:                     # also rejects NaN
+            raise ValueError("%s must be >= 0, got %r" % (name, ns))
+    torch, v, f8, code, from_numpy, device = _line_rms_inputs("threshold_line_rms", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, nbytes = _line_rms_batch(torch, lib, device, n_win, ntime, nchan)
+            ws = _workspace(torch, device, nbytes)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_line_rms_threshold(
+                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per,
+                    out.data_ptr() + w0 * per, b, ntime, nchan, nsigma_time, nsigma_freq, 1 if flag_low else 0,
+                    ws.data_ptr(), ws.numel(), stream))
+    return _like_flags(torch, out, flags, from_numpy)

@@ -26,7 +26,8 @@ _tls = threading.local()
 
 VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with_input_flags", "unflag",
                "flag_nans_zeros", "apply_static_mask",          # strat_executor.py:36-83
-               "scale_invariant_rank_operator")                 # beyond the reference: flagging.scale_invariant_rank_operator
+               "scale_invariant_rank_operator",                 # beyond the reference: flagging.scale_invariant_rank_operator
+               "threshold_line_rms")                            # beyond the reference: flagging.threshold_line_rms
 
 
 # ---------------------------------------------------------------------------

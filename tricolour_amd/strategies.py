@@ -37,6 +37,9 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
         elif task == "scale_invariant_rank_operator":
             new_flags = flagging.scale_invariant_rank_operator(flag_windows, **kw)
             flag_windows = lor(new_flags, flag_windows)
+        elif task == "threshold_line_rms":
+            new_flags = flagging.threshold_line_rms(vis_windows, flag_windows, **kw)
+            flag_windows = lor(new_flags, flag_windows)
         elif task == "apply_static_mask":
             new_flags = flagging.apply_static_mask(flag_windows, ubl, ant_pos, masked_channels,
                                                    chan_freq, chan_width, **kw)
