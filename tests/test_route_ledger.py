@@ -1,0 +1,400 @@
+"""The ledger of route switches and kernels: which test runs each of them against a reference.
+
+SWITCHES has one row per TRI_* name the library reads through getenv, KERNELS one row per __global__ kernel of
+tricolour_amd/csrc.  The tests of this module (no GPU needed) hold the two tables to the sources: a switch or kernel
+added, renamed or retired without a row fails here, and so does a script, test or document that sets a TRI_* name
+nobody reads.  tests/test_route_matrix_gpu.py imports the tables and proves every row on the device: each `route`
+switch changes the kernel log of its case as the row says and stays bit-equal to the oracle, and every `flagger`
+kernel is launched by at least one oracle-checked call.
+
+Row of SWITCHES
+    cls      "route"      the switch replaces kernels: `legs` lists what must happen
+             "geometry"   same kernel symbols, other launch geometry or arguments: the leg's case must launch `shapes`
+             "schedule" / "print-only" / "elsewhere"   not in the matrix; `why` or `test` says where it is covered
+    legs     [dict(env=..., base=..., cases={case: dict(gone=[...], new=[...], present=[...])})]
+             env: the variables set (one child process per distinct env), base: the env the log is compared with
+             (default: none set), gone: launched under base, not under env; new: the other way round; present:
+             launched under env whatever base does.
+A kernel-name fragment without '<' names a kernel whatever its template arguments ("k_reject4" is not "k_reject4_t");
+with '<' it is a prefix of the instantiation ("k_median2<true, false, 16>").
+"""
+import glob
+import os
+import re
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "tricolour_amd", "csrc")
+
+
+def _leg(env, cases, base=None):
+    return dict(env=dict(env), base=dict(base or {}), cases=cases)
+
+
+def _route(*legs):
+    return dict(cls="route", legs=list(legs))
+
+
+def _one(name, value, case, gone=(), new=(), present=()):
+    return _route(_leg({name: value}, {case: dict(gone=list(gone), new=list(new), present=list(present))}))
+
+
+_TILE_KERNELS = ["k_mr_predict", "k_mr_pass", "k_mr_finish"]
+
+SWITCHES = {
+    # ---- rejection of the 2-D background (background2d) ----
+    "TRI_NO_TILE_MEDREJ": _route(_leg({"TRI_NO_TILE_MEDREJ": "1"}, {
+        # K3t off where it is the default: the two-kernel route, and the flag copy its in-place read had made unnecessary
+        "tile": dict(gone=_TILE_KERNELS + ["k_median_reject"], new=["k_median2", "k_reject4_t", "k_u8_op16<0>"], present=[]),
+        # one block of 2^20 samples, four blocks in all: the sixteen-groups-in-flight form of the two-pass select
+        "long_block": dict(gone=_TILE_KERNELS, new=["k_median2<true, false, 16>", "k_reject4_t"], present=[]),
+    })),
+    "TRI_FUSED_MEDREJ": _route(_leg({"TRI_FUSED_MEDREJ": "1"}, {
+        # (the default tile route launches k_median_reject too, as its redo kernel: `present`, not `new`)
+        "tile": dict(gone=_TILE_KERNELS, new=[], present=["k_median_reject"]),
+        "blocks": dict(gone=["k_median2", "k_reject4_t"], new=["k_median_reject"], present=[]),
+    })),
+    "TRI_NO_FUSED_REJECT": _route(
+        _leg({"TRI_NO_FUSED_REJECT": "1"}, {
+            "tile": dict(gone=_TILE_KERNELS + ["k_median_reject"], new=["k_median2", "k_reject4"], present=[]),
+            "blocks": dict(gone=["k_reject4_t"], new=["k_reject4"], present=["k_median2"]),
+        }),
+        _leg({"TRI_NO_FUSED_REJECT": "1", "TRI_NO_TILE_MEDREJ": "1"}, {
+            "tile": dict(gone=_TILE_KERNELS + ["k_median_reject"], new=["k_median2", "k_reject4"], present=[]),
+        }),
+        _leg({"TRI_NO_FUSED_REJECT": "1", "TRI_FUSED_MEDREJ": "1"}, {
+            "tile": dict(gone=_TILE_KERNELS + ["k_median_reject"], new=["k_median2", "k_reject4"], present=[]),
+        })),
+    "TRI_MEDREJ_FORCE_FALLBACK": _route(_leg({"TRI_MEDREJ_FORCE_FALLBACK": "1"}, {
+        # blocks of 16384 samples: the switch alone turns the tile route on (every block then takes the redo kernel)
+        "blocks": dict(gone=["k_median2", "k_reject4_t", "k_u8_op16<0>"], new=_TILE_KERNELS + ["k_median_reject"], present=[]),
+        # (on the tile case the kernels are the same: the forced redo shows in tri_medrej_stats, see the GPU module)
+    })),
+    "TRI_MEDIAN_3PASS": _one("TRI_MEDIAN_3PASS", "1", "blocks", gone=["k_median2"], new=["k_median"]),
+    "TRI_MEDIAN_NO_PREDICT": dict(cls="geometry", why="the same k_median2 instantiation, launched without its candidate scratch (arguments only)",
+                                  legs=[_leg({"TRI_MEDIAN_NO_PREDICT": "1"}, {"blocks": dict(shapes=["k_median2"])})]),
+    "TRI_MEDIAN_WAVE_OLD": _one("TRI_MEDIAN_WAVE_OLD", "1", "blocks", gone=["k_median_wave<8, true, 8>"], new=["k_median_wave<8, true, 1>"]),
+    "TRI_BG_COPY_FLAGS": dict(cls="elsewhere", test="test_final_pass_routes_gpu.py::test_slab_final_pass_writes_the_panel_residual"),
+    "TRI_NO_PACKED_FLAGS": _one("TRI_NO_PACKED_FLAGS", "1", "blocks", gone=["k_boxt", "k_boxw", "k_reject4_t", "k_colst_mask<1, 2, 4, 8, true>"],
+                                new=["k_build_wo4", "k_reject4", "k_colfilter_lane4<1", "k_or_spec16"]),
+    # ---- box filters ----
+    "TRI_TIME_PREBUILD": _one("TRI_TIME_PREBUILD", "0", "unpacked", gone=["k_build_wo4"], new=["k_colfilter_lds<0"]),
+    "TRI_FILTER_DIRECT_FT": _route(_leg({"TRI_NO_PACKED_FLAGS": "1", "TRI_FILTER_DIRECT_FT": "1"}, {
+        # acts on unpacked flags with T % 4 == 0 only, which is TRI_NO_PACKED_FLAGS=1 (T % 4 == 0 packs otherwise): compared with that leg
+        "blocks": dict(gone=["k_colfilter_lane4<1, true>", "k_boxqf"], new=["k_colfilter_lds<1, true, true>", "k_masked_div4<2>"], present=[]),
+    }, base={"TRI_NO_PACKED_FLAGS": "1"})),
+    "TRI_FILTER_MULTIPASS": _one("TRI_FILTER_MULTIPASS", "1", "blocks", gone=["k_boxt", "k_boxw"], new=["k_colfilter<0>"]),
+    "TRI_FILTER_NO_LANE4": _one("TRI_FILTER_NO_LANE4", "1", "unpacked", gone=["k_colfilter_lane4"], present=["k_colfilter_lds<1"]),
+    "TRI_FILTER_NO_REGRING": _one("TRI_FILTER_NO_REGRING", "1", "blocks", gone=["k_boxt", "k_boxw", "k_boxqf"],
+                                  new=["k_colfilter_lane4<2", "k_colfilter_lds<2", "k_colfilter_lane4<3", "k_colfilter_lds_tf"]),
+    "TRI_FILTER_NO_REGRING_F": _one("TRI_FILTER_NO_REGRING_F", "1", "blocks", gone=["k_boxqf"], new=["k_colfilter_lane4<3", "k_colfilter_lds_tf"],
+                                    present=["k_boxt"]),
+    "TRI_FILTER_NO_BOXW": _one("TRI_FILTER_NO_BOXW", "1", "blocks", gone=["k_boxw"], new=["k_boxt<32, true, 0>", "k_boxt<20, false, 0>"]),
+    "TRI_SPEC_NO_PIPE": _one("TRI_SPEC_NO_PIPE", "1", "blocks", gone=["k_boxp_spec"], new=["k_boxt_spec"]),
+    "TRI_FILTER_NO_PIPE_T": _one("TRI_FILTER_NO_PIPE_T", "1", "filters", gone=["k_boxq", "k_boxq_deep"], new=["k_boxt<80", "k_boxt<32"]),
+    "TRI_FILTER_PIPE_T_B8": _one("TRI_FILTER_PIPE_T_B8", "0", "filters", gone=["k_boxq_deep", "k_boxq<56, 1, 8>"],
+                                 new=["k_boxq<80, 1, 16>", "k_boxq<48, 1, 16>"]),
+    "TRI_FILTER_NO_PIPE_F": _one("TRI_FILTER_NO_PIPE_F", "1", "filters", gone=["k_boxqf"], new=["k_boxf"]),
+    "TRI_FILTER_PIPE_F_B8": _one("TRI_FILTER_PIPE_F_B8", "0", "filters", gone=["k_boxqf<56, 1, 8>", "k_boxqf<24, 2, 8>"],
+                                 new=["k_boxqf<48, 1, 16>", "k_boxqf<16, 2, 16>"], present=["k_boxqf<80, 1, 16>"]),
+    "TRI_FILTER_NO_TIN": _one("TRI_FILTER_NO_TIN", "1", "tiny", gone=["k_colfilter_lds_tf"], new=["k_colfilter_lds<1", "k_masked_div4<2>"]),
+    "TRI_FILTER_NO_FUSED_DIV": _one("TRI_FILTER_NO_FUSED_DIV", "1", "tiny", gone=["k_colfilter_lds_tf"], new=["k_colfilter_lds_t", "k_masked_div4<2>"]),
+    "TRI_FILTER_NO_EXACT": _one("TRI_FILTER_NO_EXACT", "1", "exact", gone=["k_boxx", "k_reject_tf"], new=["k_colfilter_lane4<3"]),
+    "TRI_FILTER_NO_TF_REJECT": _one("TRI_FILTER_NO_TF_REJECT", "1", "exact", gone=["k_reject_tf", "k_median2<false, true"], new=["k_reject4_t"],
+                                    present=["k_boxx"]),
+    "TRI_BOXX_NTI": dict(cls="geometry", why="k_boxx with 256 instead of 128 threads per image (shorter chunks per lane)",
+                         legs=[_leg({"TRI_BOXX_NTI": "256"}, {"exact": dict(shapes=["k_boxx"])})]),
+    "TRI_BOXX_STATS": dict(cls="print-only", why="tri_bench_boxfilter prints the exact row filter's pass counts to stderr"),
+    "TRI_INTERP_ONE_PASS": _one("TRI_INTERP_ONE_PASS", "1", "blocks", gone=["k_interp_scan", "k_interp_fix"], new=["k_colinterp"]),
+    # ---- SumThreshold and the passes around it ----
+    "TRI_ST_GENERIC": _one("TRI_ST_GENERIC", "1", "blocks", gone=["k_colst_mask"], new=["k_colst_pipe"]),
+    "TRI_ST_REGISTER": _one("TRI_ST_REGISTER", "1", "blocks", gone=["k_colst_mask"], new=["k_colst_fused"]),
+    "TRI_ST_NO_PIPE": _one("TRI_ST_NO_PIPE", "1", "st_pipe", gone=["k_colst_pipe"], new=["k_colst_dyn"]),
+    "TRI_ST_NO_PANEL": _one("TRI_ST_NO_PANEL", "1", "blocks", gone=["k_colst_mask<1, 2, 4, 8, true>", "k_combine_dilate16<true>", "k_transpose<float, true>", "k_unpanel"],
+                            # (the row form of k_colst_mask also serves the frequency axis and the spectra: launched either way)
+                            new=["k_combine_dilate16<false>"], present=["k_colst_mask<1, 2, 4, 8, false>"]),
+    "TRI_ST_BLK": dict(cls="geometry", why="the SumThreshold kernels with 64 instead of 256 columns per workgroup",
+                       legs=[_leg({"TRI_ST_BLK": "64"}, {"blocks": dict(shapes=["k_colst_mask"])})]),
+    "TRI_NO_FUSED_OR": _one("TRI_NO_FUSED_OR", "1", "blocks", gone=["k_colst_mask<1, 2, 4, 8, true>"], new=["k_or_spec_more16"],
+                            present=["k_colst_mask<1, 2, 4, 8, false>"]),
+    "TRI_NO_FUSED_DILATE": _one("TRI_NO_FUSED_DILATE", "1", "blocks", gone=["k_combine_dilate16"], new=["k_combine16", "k_unaverage16"]),
+    "TRI_NO_FUSED_RESID_TF": dict(cls="elsewhere", test="test_final_pass_routes_gpu.py::test_slab_final_pass_writes_the_panel_residual"),
+    "TRI_NO_FUSED_BEGIN": _one("TRI_NO_FUSED_BEGIN", "1", "blocks", gone=["k_transpose_u8w<true, true>"], new=["k_zero_flagged4"]),
+    "TRI_NO_FT_SPEC_OR": _one("TRI_NO_FT_SPEC_OR", "1", "blocks", gone=["k_or_spec_ft16"], new=["k_or_spec16"]),
+    "TRI_NO_AMPL_CACHE": _one("TRI_NO_AMPL_CACHE", "1", "blocks", gone=["k_amplitude4", "k_transpose_u8w<true, true>"], new=["k_prepare4"]),
+    # ---- not in the matrix ----
+    "TRI_SUBSTREAMS": dict(cls="schedule", why="two internal streams, the same kernels", test="test_gpu_parity.py::test_two_stream_schedule_vs_oracle"),
+    "TRI_UV_SCALAR": dict(cls="elsewhere", test="test_uvcontsub.py::test_gpu_uvcontsub_vector_kernels_match_scalar"),
+}
+
+NOT_IN_MATRIX = {"TRI_SUBSTREAMS", "TRI_BOXX_STATS", "TRI_NO_FUSED_RESID_TF", "TRI_BG_COPY_FLAGS", "TRI_UV_SCALAR"}
+
+_PARITY = "test_gpu_parity.py::"
+_SCAN = "test_scan_gpu.py::"
+_ROWS = "test_scan_stream_gpu.py::"
+_UV = "test_uvcontsub.py::test_gpu_uvcontsub_agreement"
+_LRMS = "test_line_rms.py::test_gpu_small_and_odd_shapes"
+_MEDBIG = _PARITY + "test_median_kernels"
+
+# "flagger": launched by sum_threshold_flagger on some route -- test_route_matrix_gpu.py must see it in an oracle-checked log
+KERNELS = {
+    # kernels_boxexact / boxfilter / boxline / boxpipe / boxweight
+    "k_boxx": "flagger", "k_colfilter": "flagger", "k_colfilter_lds": "flagger", "k_colfilter_lds_t": "flagger",
+    "k_colfilter_lds_tf": "flagger", "k_colfilter_lane4": "flagger", "k_boxt": "flagger", "k_boxt_spec": "flagger",
+    "k_boxf": "flagger", "k_boxp_spec": "flagger", "k_boxq": "flagger", "k_boxq_deep": "flagger", "k_boxqf": "flagger",
+    "k_boxw": "flagger",
+    # kernels_elementwise: the flagger's passes
+    "k_prepare": "flagger", "k_transpose": "flagger", "k_unpanel": "flagger", "k_transpose_u8w": "flagger",
+    "k_build_wo": "flagger", "k_build_wo4": "flagger", "k_masked_div": "flagger", "k_reject": "flagger",
+    "k_colinterp": "flagger", "k_interp_scan": "flagger", "k_interp_fix": "flagger", "k_sub": "flagger", "k_or": "flagger",
+    "k_copy_u8": "flagger", "k_or_spec": "flagger", "k_combine": "flagger", "k_unaverage": "flagger", "k_final": "flagger",
+    "k_prepare4": "flagger", "k_amplitude4": "flagger", "k_zero_flagged4": "flagger", "k_u8_op16": "flagger",
+    "k_spec_rows": "flagger", "k_or_spec16": "flagger", "k_or_spec_more16": "flagger", "k_or_spec_ft16": "flagger",
+    "k_combine16": "flagger", "k_combine_dilate16": "flagger", "k_unaverage16": "flagger", "k_colcount": "flagger",
+    "k_final16": "flagger", "k_masked_div4": "flagger", "k_sub4": "flagger", "k_reject4_t": "flagger",
+    "k_reject_tf": "flagger", "k_reject4": "flagger",
+    # ... and the kernels of the other entry points
+    "k_abs_c64": _PARITY + "test_hypotf_kat",
+    "k_panelize": _PARITY + "test_fused_sumthreshold_kernel_vs_generic_and_oracle",
+    "k_unpanel_w": _PARITY + "test_fused_sumthreshold_kernel_vs_generic_and_oracle",
+    "k_fill_windows": "test_packing.py::test_gpu_pack_flag_unpack",
+    "k_pack": "test_packing.py::test_gpu_pack_flag_unpack", "k_pack_v": "test_packing.py::test_gpu_pack_flag_unpack",
+    "k_unpack_v": "test_packing.py::test_gpu_pack_flag_unpack", "k_unpack": "test_packing.py::test_gpu_pack_flag_unpack",
+    "k_flag_nans_zeros": "test_strategy_steps.py::test_gpu_strategy_steps",
+    "k_apply_bl_chan_mask": "test_strategy_steps.py::test_gpu_strategy_steps",
+    "k_uv_count": "unlaunched", "k_uv_diff": "unlaunched",
+    "k_uv_mean": _UV, "k_uv_lowpass": _UV, "k_uv_resid": _UV, "k_uv_resid4": _UV, "k_uv_apply": _UV, "k_uv_apply4": _UV,
+    "k_window_counts": "test_window_statistics.py::test_gpu_window_counts",
+    "k_stokes_intensity": "test_stokes.py::test_gpu_intensities",
+    # kernels_linerms
+    "k_lrms_power": _LRMS, "k_lrms_combine": _LRMS, "k_lrms_decide": _LRMS, "k_lrms_apply": _LRMS,
+    # kernels_median
+    "k_median": "flagger", "k_median2": "flagger", "k_median_wave": "flagger", "k_spec_from_med": "flagger",
+    "k_medbig_range": _MEDBIG, "k_medbig_hist": _MEDBIG, "k_medbig_pick": _MEDBIG, "k_medbig_compact": _MEDBIG,
+    "k_medbig_select": _MEDBIG,
+    # kernels_reject / reject_tile
+    "k_median_reject": "flagger", "k_mr_predict": "flagger", "k_mr_pass": "flagger", "k_mr_finish": "flagger",
+    # kernels_scan
+    "k_pack_scan_v": _SCAN + "test_gpu_pack_scan_matches_unfused_kernels", "k_pack_scan": _SCAN + "test_gpu_pack_scan_matches_unfused_kernels",
+    "k_unpack_scan": _SCAN + "test_gpu_unpack_scan_matches_numpy",
+    "k_pack_scan_rows_v": _ROWS + "test_gpu_pack_scan_rows_matches_pack_scan", "k_pack_scan_rows": _ROWS + "test_gpu_pack_scan_rows_matches_pack_scan",
+    "k_unpack_scan_rows": _ROWS + "test_gpu_unpack_scan_rows_matches_unpack_scan",
+    # kernels_sir
+    "k_sir": "test_sir.py::test_gpu_sir_small_and_odd_shapes",
+    # kernels_sumthreshold
+    "k_colst_dyn": "flagger", "k_colst_pipe": "flagger", "k_colst_fused": "flagger", "k_colst_mask": "flagger",
+    # tricolour_amd.hip
+    "k_tables": "flagger", "k_gather_col_f32": "flagger", "k_gather_col_u8": "flagger", "k_normalise_flags": "flagger",
+    "k_check_box_divide": _PARITY + "test_division_by_box_denominator",
+}
+
+
+def matches(fragment, name):
+    """Whether the demangled kernel name `name` (template arguments included) is the kernel `fragment` speaks of."""
+    if "<" in fragment:
+        return name.startswith(fragment)
+    return name == fragment or name.startswith(fragment + "<")
+
+
+def launches(log, fragment):
+    return sum(n for name, n in log.items() if matches(fragment, name))
+
+
+def base_name(name):
+    return name.split("<", 1)[0]
+
+
+def switch_legs(name):
+    return SWITCHES[name].get("legs", [])
+
+
+# ---- the scans ----
+
+def _sources(directory=CSRC):
+    out = {}
+    for path in sorted(glob.glob(os.path.join(directory, "*"))):
+        if os.path.isfile(path):
+            with open(path, encoding="utf-8") as fh:
+                out[path] = fh.read()
+    return out
+
+
+def scan_getenv(directory=CSRC):
+    found = set()
+    for text in _sources(directory).values():
+        found.update(re.findall(r'getenv\(\s*"(TRI_[A-Z0-9_]+)"', text))
+    return found
+
+
+def scan_kernels(directory=CSRC):
+    found = set()
+    for text in _sources(directory).values():
+        found.update(re.findall(r"__global__[\s\S]{0,200}?\b(k_\w+)\s*\(", text))
+    return found
+
+
+def names_read_by_python():
+    """TRI_* names bench.py and the package read from the environment themselves."""
+    found = set()
+    for path in [os.path.join(ROOT, "bench.py")] + sorted(glob.glob(os.path.join(ROOT, "tricolour_amd", "*.py"))):
+        with open(path, encoding="utf-8") as fh:
+            for line in fh:
+                if "environ" in line or "getenv" in line or re.search(r"\benv\[", line):
+                    found.update(re.findall(r"""["'](TRI_[A-Z0-9_]+)["']""", line))
+    return found
+
+
+_COMMAND = r"(?:python[\w.]*|pytest|bash|sh|env|rocprofv3|hipcc|make|\./\S+|scripts/\S+|\$\w+|\$\{\w+\})"
+
+
+def assigned_names(path, text):
+    """TRI_* names `text` puts into an environment: NAME=value before a command (shell, documents), a `for` list
+    whose variable is then set with $var=..., env[...] / os.environ[...] stores, dict(os.environ, NAME=...) and
+    switch names kept as whole strings ("NAME" or "NAME=value") in Python."""
+    found = set()
+    ext = os.path.splitext(path)[1]
+    if ext == ".py":
+        found.update(re.findall(r"(?<![\w$])(TRI_[A-Z0-9_]+)=", text))                        # dict(os.environ, NAME="1"), "NAME=1"
+        found.update(re.findall(r"""(?:env|environ)\[\s*["'](TRI_[A-Z0-9_]+)["']\s*\]\s*=[^=]""", text))
+        found.update(re.findall(r"""["'](TRI_[A-Z0-9_]+)(?:=\w*)?["']""", text))
+        found.update(re.findall(r"""["'](TRI_[A-Z0-9_]+)["']\s*:""", text))
+    elif ext in (".md", ".rst", ".txt"):
+        for m in re.finditer(r"(?<![\w$])((?:[A-Z_][A-Z0-9_]*=\S*\s+)+)" + _COMMAND, text):
+            found.update(re.findall(r"(?<![\w$])(TRI_[A-Z0-9_]+)=", m.group(1)))
+    else:
+        found.update(re.findall(r"(?<![\w$])(TRI_[A-Z0-9_]+)=", text))
+        for m in re.finditer(r"\bfor\s+(\w+)\s+in\s+([^;\n]*)", text):
+            var, words = m.group(1), m.group(2)
+            if re.search(r"\$\{?%s\}?=" % re.escape(var), text):
+                found.update(re.findall(r"(?<![\w$])(TRI_[A-Z0-9_]+)\b", words))
+    return found
+
+
+def files_that_set_switches():
+    paths = [os.path.join(ROOT, "bench.py")] + sorted(glob.glob(os.path.join(ROOT, "*.md")))
+    for sub in ("scripts", "tests"):
+        for d, _, names in os.walk(os.path.join(ROOT, sub)):
+            if "golden" in d or "__pycache__" in d:
+                continue
+            paths += [os.path.join(d, n) for n in sorted(names) if os.path.splitext(n)[1] in (".py", ".sh", ".md", ".txt")]
+    # (this file's own rows are held to the getenv scan; its scan tests spell made-up names)
+    return [p for p in paths if os.path.abspath(p) != os.path.abspath(__file__)]
+
+
+# error codes, dtype codes and limits of the C ABI: TRI_* tokens that are not environment variables
+ABI_CONSTANTS = re.compile(r"^TRI_(OK|EINVAL|EUNSUPPORTED|EWORKSPACE|EHIP|VIS_\w+|MAX_\w+|MAD_NORMAL)$")
+
+
+# ---- the tests ----
+
+def test_every_getenv_name_has_a_row():
+    found = scan_getenv()
+    assert found == set(SWITCHES), "not in SWITCHES: %s; rows without a getenv: %s" % (sorted(found - set(SWITCHES)), sorted(set(SWITCHES) - found))
+
+
+def test_every_kernel_has_a_row():
+    found = scan_kernels()
+    assert found == set(KERNELS), "not in KERNELS: %s; rows without a kernel: %s" % (sorted(found - set(KERNELS)), sorted(set(KERNELS) - found))
+
+
+def test_the_scans_notice_a_change(tmp_path):
+    """A renamed getenv string or an added kernel in a copy of the sources changes what the scans find."""
+    for path, text in _sources().items():
+        text = text.replace('getenv("TRI_ST_NO_PIPE")', 'getenv("TRI_ST_NOPIPE")')
+        if path.endswith("kernels_sir.hpp"):
+            text += "\ntemplate <int N>\n__global__ void __launch_bounds__(64, f(N))\nk_added_later(const float* a) {}\n"
+        (tmp_path / os.path.basename(path)).write_text(text, encoding="utf-8")
+    assert scan_getenv(str(tmp_path)) ^ set(SWITCHES) == {"TRI_ST_NO_PIPE", "TRI_ST_NOPIPE"}
+    assert scan_kernels(str(tmp_path)) - set(KERNELS) == {"k_added_later"}
+
+
+def test_rows_are_well_formed():
+    for name, row in SWITCHES.items():
+        cls = row["cls"]
+        assert cls in ("route", "geometry", "schedule", "print-only", "elsewhere", "unreachable"), name
+        if cls in ("route", "geometry"):
+            assert name not in NOT_IN_MATRIX and row["legs"], name
+            for leg in row["legs"]:
+                assert name in leg["env"] and leg["cases"], name
+                assert all(leg["env"].get(k) == v for k, v in leg["base"].items()) and name not in leg["base"], name
+                for case, what in leg["cases"].items():
+                    if cls == "route":
+                        assert what["gone"] or what["new"], (name, case)
+                    else:
+                        assert what["shapes"] and row["why"], (name, case)
+        elif cls == "unreachable":
+            assert row["why"], name
+        else:
+            # nothing but these five may stay out of the matrix
+            assert name in NOT_IN_MATRIX, name
+            assert row.get("test") or row.get("why"), name
+    assert {n for n, r in SWITCHES.items() if r["cls"] not in ("route", "geometry", "unreachable")} == NOT_IN_MATRIX
+    assert {n for n, r in SWITCHES.items() if r["cls"] == "elsewhere"} == {"TRI_NO_FUSED_RESID_TF", "TRI_BG_COPY_FLAGS", "TRI_UV_SCALAR"}
+    for kernel, where in KERNELS.items():
+        assert where in ("flagger", "unlaunched") or "::" in where, kernel
+
+
+def _function_exists(ref):
+    fname, func = ref.split("::")
+    with open(os.path.join(HERE, fname), encoding="utf-8") as fh:
+        return re.search(r"^def %s\(" % re.escape(func), fh.read(), re.M) is not None
+
+
+def test_named_tests_exist():
+    refs = {w for w in KERNELS.values() if "::" in w} | {r["test"] for r in SWITCHES.values() if r.get("test")}
+    missing = sorted(r for r in refs if not _function_exists(r))
+    assert not missing, missing
+
+
+def test_unlaunched_kernels_have_no_launch_site():
+    with open(os.path.join(CSRC, "tricolour_amd.hip"), encoding="utf-8") as fh:
+        hip = fh.read()
+    for kernel, where in KERNELS.items():
+        used = re.search(r"\b%s\b" % kernel, re.sub(r"//[^\n]*", "", hip)) is not None
+        defined_there = re.search(r"__global__[\s\S]{0,200}?\b%s\s*\(" % kernel, hip) is not None
+        if where == "unlaunched":
+            assert not used, "%s has a launch site" % kernel
+        elif not defined_there:
+            assert used, "%s is never launched: mark it unlaunched" % kernel
+
+
+def test_the_elsewhere_tests_assert_a_kernel_log():
+    for name, row in SWITCHES.items():
+        if row["cls"] != "elsewhere":
+            continue
+        with open(os.path.join(HERE, row["test"].split("::")[0]), encoding="utf-8") as fh:
+            text = fh.read()
+        assert name in text and "kernel_log_begin" in text, name
+
+
+def test_no_file_sets_a_name_nobody_reads():
+    known = set(SWITCHES) | names_read_by_python()
+    bad = []
+    for path in files_that_set_switches():
+        with open(path, encoding="utf-8") as fh:
+            text = fh.read()
+        for name in sorted(assigned_names(path, text)):
+            if name not in known and not ABI_CONSTANTS.match(name):
+                bad.append("%s sets %s" % (os.path.relpath(path, ROOT), name))
+    assert not bad, "; ".join(bad)
+
+
+def test_the_assignment_scan_sees_each_form():
+    assert assigned_names("x.sh", "for k in NONE TRI_A TRI_B; do\n  env $k=1 python x.py\ndone\n") == {"TRI_A", "TRI_B"}
+    assert assigned_names("x.sh", "TRI_C=1 TRI_D=0 python x.py\nexport TRI_E=1\n") == {"TRI_C", "TRI_D", "TRI_E"}
+    assert assigned_names("x.md", "run `TRI_F=1 python bench.py`; the loop sets TRI_G=1, a variable nobody reads") == {"TRI_F"}
+    assert assigned_names("x.py", 'env["TRI_H"] = "1"\nos.environ["TRI_I"] = "1"\ne = dict(os.environ, TRI_J="1")\nK = ("TRI_K=256", "TRI_L")\n') == \
+        {"TRI_H", "TRI_I", "TRI_J", "TRI_K", "TRI_L"}
+
+
+def test_alternate_kernel_paths_names_are_switches():
+    with open(os.path.join(HERE, "test_gpu_parity.py"), encoding="utf-8") as fh:
+        text = fh.read()
+    m = re.search(r'parametrize\("knob",\s*\[(.*?)\]\)\s*\ndef test_alternate_kernel_paths', text, re.S)
+    assert m, "test_alternate_kernel_paths not found"
+    names = set()
+    for knob in re.findall(r'"([^"]+)"', m.group(1)):
+        for one in knob.split(";"):
+            names.add(one.partition("=")[0])
+    names.discard("DEFAULT_ROUTES")
+    assert len(names) > 30 and names <= set(SWITCHES), sorted(names - set(SWITCHES))

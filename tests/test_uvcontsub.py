@@ -145,7 +145,7 @@ UV_AB_SCRIPT = r'''
 import sys, hashlib
 sys.path.insert(0, %r)
 import numpy as np
-from tricolour_amd import flagging
+from tricolour_amd import flagging, _lib
 rs = np.random.RandomState(8)
 shape = (3, 2, 64, 512)
 x = np.linspace(0, 1, shape[3])
@@ -156,24 +156,30 @@ vis[2, 0, 10] += 3
 vis[0, 1, 5, 7] = np.nan
 flags = rs.uniform(size=shape) < 0.02
 flags[1, 1] = True
+_lib.kernel_log_begin()
 out = flagging.uvcontsub_flagger(vis, flags, major_cycles=5, or_original_from_cycle=1, taylor_degrees=20, sigma=10.0)
+log = _lib.kernel_log_end()
 print("DIGEST", hashlib.sha1(np.packbits(out).tobytes()).hexdigest(), int(out.sum()))
+print("KERNELS", " ".join(sorted(k for k in log if k.startswith("k_uv_"))))
 '''
 
 
 @pytest.mark.gpu
 def test_gpu_uvcontsub_vector_kernels_match_scalar(gpu):
     """The four-samples-per-thread residual / apply kernels and the scalar ones (TRI_UV_SCALAR=1, read once per
-    process) give the same flags bit for bit."""
+    process) give the same flags bit for bit, and the kernel log shows that each leg ran its own pair."""
     import os
     import subprocess
     import sys
     from conftest import ROOT
-    digests = []
+    digests, kernels = [], []
     for scalar in ("0", "1"):
         env = dict(os.environ)
         env["TRI_UV_SCALAR"] = scalar
         p = subprocess.run([sys.executable, "-c", UV_AB_SCRIPT % ROOT], capture_output=True, text=True, env=env, timeout=600)
         assert p.returncode == 0, p.stdout + p.stderr
         digests.append([l for l in p.stdout.splitlines() if l.startswith("DIGEST")][0])
+        kernels.append([l for l in p.stdout.splitlines() if l.startswith("KERNELS")][0].split()[1:])
     assert digests[0] == digests[1], digests
+    assert "k_uv_resid4" in kernels[0] and "k_uv_apply4" in kernels[0] and "k_uv_resid" not in kernels[0] and "k_uv_apply" not in kernels[0], kernels
+    assert "k_uv_resid" in kernels[1] and "k_uv_apply" in kernels[1] and "k_uv_resid4" not in kernels[1] and "k_uv_apply4" not in kernels[1], kernels
