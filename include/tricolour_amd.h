@@ -427,6 +427,7 @@ int tri_bench_sumthreshold(const float *data, const double *mad, uint8_t *out,
  *            float32(2 r + 1) ** 4.
  * `variant`: 0 = the flagger's default route for this radius, 1 = LDS delay
  * lines only (K4b / K4c / multi-pass), 2 = register delay lines (K4r).
+ * (Stage 1, radius >= 56: the flagger takes the exact row filter, variant 0 the stage pipeline; variant 4 is K4x.)
  * For stage 2: 0 = default route, 1 = register delay lines (K4r), 2 / 3 = the
  * stage pipeline across four waves (K4p) with blocks of 16 / 8 positions
  * (TRI_EUNSUPPORTED when that block length does not apply to the shape).

@@ -49,6 +49,17 @@ static hipError_t lds_optin(const void* fn, hipFuncAttribute attr, int value) {
     return e;
 }
 
+// a switch of the environment is on when its value starts with '1'
+static inline bool is1(const char* e) { return e && e[0] == '1'; }
+
+// ... for several kernels: stops at the first failure
+template <class... K>
+static hipError_t lds_optin_all(int bytes, K... kernels) {
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : lds_optin(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)), ...);
+    return e;
+}
+
 struct Bump {
     char* base;
     size_t cap, off;
@@ -399,10 +410,7 @@ struct Run {
 // The register cascade covers windows exactly (1,2,4,8) in that order; the
 // environment variable TRI_ST_GENERIC=1 forces the generic kernel (tests).
 bool st_use_fused(const StWin& sw) {
-    static const bool force_generic = [] {
-        const char* e = getenv("TRI_ST_GENERIC");
-        return e && e[0] == '1';
-    }();
+    static const bool force_generic = is1(getenv("TRI_ST_GENERIC"));
     if (force_generic) return false;
     return sw.nw == 4 && sw.w[0] == 1 && sw.w[1] == 2 && sw.w[2] == 4 && sw.w[3] == 8;
 }
@@ -411,12 +419,12 @@ bool st_use_fused(const StWin& sw) {
 // offsets (windows below 2 GiB of float32); larger windows and TRI_ST_REGISTER=1 (tests) take the register
 // cascade (K7b).
 bool st_use_mask(int L, int C) {
-    static const bool force_register = [] {
-        const char* e = getenv("TRI_ST_REGISTER");
-        return e && e[0] == '1';
-    }();
+    static const bool force_register = is1(getenv("TRI_ST_REGISTER"));
     return !force_register && (uint64_t)L * (uint64_t)C * 4u < (1ull << 31);   // signed 32-bit scalar offsets
 }
+
+// TRI_MEDIAN_NO_PREDICT=1: the two-pass medians read their segments twice, without the predicted-window candidates (A/B runs, tests)
+static bool median_no_predict() { static const bool v = is1(getenv("TRI_MEDIAN_NO_PREDICT")); return v; }
 
 // launch_median() can OR a second flag image and per-column flags into the flags it reads when the segments fit the wave kernels
 static bool median_takes_extra_flags(int64_t max_len) { return max_len <= 64 * MW_K; }
@@ -503,7 +511,7 @@ int launch_median(const Run& r, MedianJob j) {
     if (j.panel_rows > 0 && !row4) return set_err(TRI_EUNSUPPORTED, "panel images of 4 GB or more per window");
     const int64_t slack = j.segs_aligned ? 0 : 3;   // misaligned segment starts cost up to 3 masked slots
     // wave medians: MW_SPW rows of a segment per wave, the next row's loads in flight (round 4; TRI_MEDIAN_WAVE_OLD=1: one segment per wave)
-    static const bool wave_old = [] { const char* e = getenv("TRI_MEDIAN_WAVE_OLD"); return e && e[0] == '1'; }();
+    static const bool wave_old = is1(getenv("TRI_MEDIAN_WAVE_OLD"));
     MedianKernel k;
     if (max_len + slack <= 64 * 8 && row4) k = MedianKernel::Wave8Vec;
     else if (max_len <= 64 * 8 && j.panel_rows == 0) k = MedianKernel::Wave8;     // (panel images: the 16-byte kernels only)
@@ -511,12 +519,11 @@ int launch_median(const Run& r, MedianJob j) {
     else if (max_len <= 64 * MW_K) k = MedianKernel::Wave16;
     else {
         // long segments: two-pass select (K3c); TRI_MEDIAN_3PASS=1 keeps the three-pass kernel (A/B runs, tests)
-        static const bool three = [] { const char* e = getenv("TRI_MEDIAN_3PASS"); return e && e[0] == '1'; }();
+        static const bool three = is1(getenv("TRI_MEDIAN_3PASS"));
         if (three) k = j.vec_ok ? MedianKernel::SelectVec : MedianKernel::Select;
         else {
             // scratch for the predicted-window candidates (K3c): one read of the segment instead of two
-            static const bool no_predict = [] { const char* e = getenv("TRI_MEDIAN_NO_PREDICT"); return e && e[0] == '1'; }();
-            if (no_predict || j.cand_cap < max_len || j.cand_ws % 4 != 0 || j.cand_cap % 4 != 0 || ((uintptr_t)j.gcand % 16 != 0)) {
+            if (median_no_predict() || j.cand_cap < max_len || j.cand_ws % 4 != 0 || j.cand_cap % 4 != 0 || ((uintptr_t)j.gcand % 16 != 0)) {
                 j.gcand = nullptr; j.cand_ws = 0; j.cand_cap = 0;
             }
             // few, long segments (fewer workgroups than the machine holds at six per CU): sixteen 16-byte groups in flight per thread
@@ -544,17 +551,11 @@ int launch_median(const Run& r, MedianJob j) {
 #ifndef LANE4_R_MAX
 #define LANE4_R_MAX 160
 #endif
+static bool filter_no_lane4() { static const bool v = is1(getenv("TRI_FILTER_NO_LANE4")); return v; }
 int colfilter_lds_block(int rad, int C) {
-    static const bool disabled = [] {
-        const char* e = getenv("TRI_FILTER_MULTIPASS");
-        return e && e[0] == '1';
-    }();
-    static const bool no_lane4 = [] {
-        const char* e = getenv("TRI_FILTER_NO_LANE4");
-        return e && e[0] == '1';
-    }();
+    static const bool disabled = is1(getenv("TRI_FILTER_MULTIPASS"));
     if (disabled || rad <= 0) return 0;
-    if (no_lane4) {
+    if (filter_no_lane4()) {
         int bt = rad <= 10 ? 256 : (rad <= 20 ? 128 : (rad <= 40 ? 64 : 0));   // K4b alone (TRI_FILTER_NO_LANE4)
         while (bt > 64 && bt / 2 >= C) bt /= 2;
         return bt;
@@ -566,23 +567,8 @@ int colfilter_lds_block(int rad, int C) {
     }
     return rad <= LANE4_R_MAX ? 64 : 0;
 }
-inline bool colfilter_use_lane4(int rad) {
-    static const bool no_lane4 = [] {
-        const char* e = getenv("TRI_FILTER_NO_LANE4");
-        return e && e[0] == '1';
-    }();
-    return !no_lane4 && rad > LDS_R_MAX && rad <= LANE4_R_MAX;
-}
+inline bool colfilter_use_lane4(int rad) { return !filter_no_lane4() && rad > LDS_R_MAX && rad <= LANE4_R_MAX; }
 
-// One axis of masked_gaussian_filter's two box filters (weight image and
-// data image) on a column-layout image pair.
-//   srcmode 0: images are built on the fly from (srcData, srcFlags) [n][C]
-//   srcmode 1: images are float arrays; for the multi-pass kernel they sit in
-//              rows [4r, 4r+n) of bufW / bufO, for the LDS kernel in rows [0,n)
-// Output: rows [0,n) of dstW / dstO.
-// `deferred_denom` (optional): when the single-sweep kernel is used the final
-// division by float32(d)**4 is left to the consumer (transpose / masked_div) and
-// *deferred_denom receives the denominator; otherwise it is set to 0.
 // Register-ring single sweep (K4r, kernels_boxline.hpp): KS register slots per stage, the
 // rest of the 2r-deep delay line in LDS.  Returns 0 when the radius is outside its range.
 // TRI_FILTER_NO_REGRING=1 keeps the LDS-ring kernels (A/B runs, tests).
@@ -591,7 +577,7 @@ inline bool colfilter_use_lane4(int rad) {
 #endif
 thread_local int g_boxr_override = -1;     // measurement hook: 0 = LDS-ring kernels, 1 = register-ring kernels
 int boxr_pick_ks(int rad) {
-    static const bool env_off = [] { const char* e = getenv("TRI_FILTER_NO_REGRING"); return e && e[0] == '1'; }();
+    static const bool env_off = is1(getenv("TRI_FILTER_NO_REGRING"));
     const bool off = g_boxr_override >= 0 ? g_boxr_override == 0 : env_off;
     if (off || rad < 4 || rad > 107) return 0;
     const int ks = 2 * rad >= 80 ? 80 : (2 * rad >= 64 ? 64 : (2 * rad >= 32 ? 32 : (2 * rad >= 16 ? 16 : 8)));
@@ -612,7 +598,7 @@ int boxr_pick_ks_t(int rad) {
     return 2 * rad >= BOXT_MIN_2R ? boxr_pick_ks(rad) : 0;
 }
 int boxr_pick_ks_f(int rad) {
-    static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_REGRING_F"); return e && e[0] == '1'; }();
+    static const bool off = is1(getenv("TRI_FILTER_NO_REGRING_F"));
     return off ? 0 : boxr_pick_ks(rad);
 }
 
@@ -621,7 +607,7 @@ int boxr_pick_ks_f(int rad) {
 // not apply; the caller's kernels then filter both images as before.  TRI_FILTER_NO_BOXW=1 switches it off (A/B runs, tests).
 thread_local int g_boxw_override = -1;     // tests / benches: 0 = off
 static bool boxw_usable(int rad, int n, int C) {
-    static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_BOXW"); return e && e[0] == '1'; }();
+    static const bool off = is1(getenv("TRI_FILTER_NO_BOXW"));
     if (g_boxw_override == 0 || (off && g_boxw_override < 0)) return false;
     return 2 * rad >= 20 && 2 * rad <= 110 && n % 4 == 0 && (uint64_t)n * (uint64_t)C * 4u < (1ull << 31);
 }
@@ -650,12 +636,7 @@ int launch_boxt_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, 
     const int d = 2 * rad - KS;
     const size_t lds = (size_t)4 * d * 64 * sizeof(float);
     dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
-    const hipError_t attr = [] {
-        hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_boxt<KS, true, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_boxt<KS, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return e;
-    }();
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_boxt<KS, true, 0>, &k_boxt<KS, true, 1>));
     // one launch per image: a compute unit then runs (mostly) one of the two long loop bodies at a time
     // (the weight image through the integer kernel K4w where it applies)
     const bool wk = boxw_usable(rad, n, C);
@@ -678,9 +659,7 @@ int launch_boxt_spec_ks(const Run& r, const float* srcData, const uint8_t* srcFl
     const int d = 2 * rad - KS;
     const size_t lds = (size_t)4 * d * 64 * sizeof(float);
     dim3 grid((unsigned)cdiv(C, 64), 2);
-    const hipError_t attr = lds_optin(reinterpret_cast<const void*>(&k_boxt_spec<KS, true>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_boxt_spec<KS, true>));
     if (d > 0) hipLaunchKernelGGL((k_boxt_spec<KS, true>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
     else hipLaunchKernelGGL((k_boxt_spec<KS, false>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
     LAUNCHCHK();
@@ -703,7 +682,7 @@ int launch_boxt_spec(const Run& r, int ks, const float* srcData, const uint8_t* 
 // (2r >= B, four stage buffers within the CU's 160 KB of LDS).  TRI_SPEC_NO_PIPE=1 keeps the register rings.
 static thread_local int g_boxp_override = -1;   // tests / benches: 0 = off, 8 / 16 = only that block length
 static int boxp_pick_block(int rad, int C) {
-    static const bool off = [] { const char* e = getenv("TRI_SPEC_NO_PIPE"); return e && e[0] == '1'; }();
+    static const bool off = is1(getenv("TRI_SPEC_NO_PIPE"));
     if (g_boxp_override == 0 || (off && g_boxp_override < 0)) return 0;
     if (g_boxp_override != 8 && 2 * rad >= 16 && C % 4 == 0 && boxp_lds_bytes(rad, 16) <= 160 * 1024) return 16;
     if (g_boxp_override == 16) return 0;
@@ -714,9 +693,7 @@ static int boxp_pick_block(int rad, int C) {
 template <int B, int P>
 int launch_boxp_spec_b(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
                        int n, int C, int rad, float denom) {
-    const hipError_t attr = lds_optin(reinterpret_cast<const void*>(&k_boxp_spec<B, P>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_boxp_spec<B, P>));
     dim3 grid((unsigned)cdiv(C, 64), 2);
     hipLaunchKernelGGL((k_boxp_spec<B, P>), grid, dim3(256), boxp_lds_bytes(rad, B), r.st, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
     LAUNCHCHK();
@@ -730,7 +707,7 @@ int launch_boxp_spec_b(const Run& r, const float* srcData, const uint8_t* srcFla
 #endif
 thread_local int g_boxq_override = -1;   // tests / benches: 0 = off, 1 = on wherever it applies
 static int boxq_pick_ks(int rad) {
-    static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_PIPE_T"); return e && e[0] == '1'; }();
+    static const bool off = is1(getenv("TRI_FILTER_NO_PIPE_T"));
     if (g_boxq_override == 0 || (off && g_boxq_override < 0)) return 0;
     const int ks = 2 * rad / 16 * 16;
     return (ks >= 16 && ks <= 96) ? ks : 0;
@@ -739,12 +716,7 @@ static int boxq_pick_ks(int rad) {
 template <int KS, int B = 16>
 int launch_boxq_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
                    int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-    const hipError_t attr = [] {
-        hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_boxq<KS, 0, B>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_boxq<KS, 1, B>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return e;
-    }();
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_boxq<KS, 0, B>, &k_boxq<KS, 1, B>));
     dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
     const BoxDenom dn = box_reciprocal(denom);
     if (boxw_usable(rad, n, C)) { const int rc = launch_boxw(r, srcFlags, dstW, n, C, rad, denom, sws, dws, W); if (rc) return rc; }
@@ -772,12 +744,7 @@ static int boxq_pick_ks8(int rad) {
 template <int KS>
 int launch_boxq_deep(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
                      int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-    const hipError_t attr = [] {
-        hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_boxq_deep<KS, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_boxq_deep<KS, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return e;
-    }();
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_boxq_deep<KS, 0>, &k_boxq_deep<KS, 1>));
     dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
     const BoxDenom dn = box_reciprocal(denom);
     if (boxw_usable(rad, n, C)) { const int rc = launch_boxw(r, srcFlags, dstW, n, C, rad, denom, sws, dws, W); if (rc) return rc; }
@@ -828,129 +795,102 @@ int launch_boxt(const Run& r, int ks, const float* srcData, const uint8_t* srcFl
     return set_err(TRI_EINVAL, "no register-ring kernel for %d slots", ks);
 }
 
-int launch_colfilter(const Run& r, int srcmode, float* bufW, float* bufO, const float* srcData,
+// Where launch_colfilter() takes the two images from
+enum class ColSrc {
+    ByteFlags,     // built on the fly from (srcData, srcFlags) [n][C], one flag byte per sample
+    Images,        // float arrays: for the multi-pass kernel in rows [4r, 4r+n) of bufW / bufO, for the LDS kernels in rows [0,n)
+    PackedFlags    // built on the fly from (srcData, srcFlags), four line positions of a column per flag word (n % 4 == 0)
+};
+enum ColFlag : unsigned {
+    COL_TRANSPOSED_OUT = 1,   // write [C][n] (LDS-ring kernel, float images only)
+    COL_WEIGHTS_01 = 2        // the weights are 0 / 1: integer arithmetic where it is exact
+};
+enum class ColFamily { SpecPipe, SpecRing, StagePipe, RegRing, Lane4, LdsRing, MultiPass };   // K4p, K4r (spectrum), K4q, K4r, K4c, K4b, K4
+
+// One axis of masked_gaussian_filter's two box filters (weight image and data image) on a column-layout image pair.
+// Output: rows [0,n) of dstW / dstO.  deferred_denom (optional): where the kernel can, the division by float32(d)**4 is left
+// to the consumer (transpose / masked_div) and *deferred_denom receives the denominator; otherwise it is set to 0.
+int launch_colfilter(const Run& r, ColSrc src, float* bufW, float* bufO, const float* srcData,
                      const uint8_t* srcFlags, float* dstW, float* dstO, int n, int C, int rad,
-                     size_t bws, size_t sws, size_t dws, int64_t W, float* deferred_denom = nullptr,
-                     bool transposed_out = false, bool weights_are_01 = false) {
-    float denom = box_denominator(rad);
+                     size_t bws, size_t sws, size_t dws, int64_t W, unsigned flags = 0, float* deferred_denom = nullptr) {
+    const bool transposed_out = flags & COL_TRANSPOSED_OUT, weights_are_01 = flags & COL_WEIGHTS_01;
+    const float denom = box_denominator(rad);
     // integer arithmetic for the weight image is exact while (2r+1)^4 <= 2^24
     const int intw = (weights_are_01 && rad <= 31) ? 1 : 0;
     int bt = colfilter_lds_block(rad, C);
     if (deferred_denom) *deferred_denom = 0.0f;
-    // spectrum path (one "window" of byte flags + data, both images): register-ring kernel from r = 4 on
-    if (srcmode == 0 && !deferred_denom && !transposed_out && weights_are_01 && W == 1 && boxp_pick_block(rad, C) > 0 && rad <= 107 &&
-        (uint64_t)n * (uint64_t)C * 4u < (1ull << 31) && ((uintptr_t)srcData % 16 == 0) && ((uintptr_t)srcFlags % 4 == 0) &&
-        ((uintptr_t)dstW % 16 == 0) && ((uintptr_t)dstO % 16 == 0)) {
-        if (boxp_pick_block(rad, C) == 16) return launch_boxp_spec_b<16, 16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-        return launch_boxp_spec_b<8, 16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
+    // --- which kernel family ---
+    // the register-ring and stage-pipeline kernels build 0 / 1 weights themselves, divide themselves, write [n][C] and address
+    // a window through signed 32-bit buffer offsets
+    const bool regs_ok = !deferred_denom && !transposed_out && weights_are_01 && (uint64_t)n * (uint64_t)C * 4u < (1ull << 31);
+    const bool spectrum = regs_ok && src == ColSrc::ByteFlags && W == 1;    // one "window" of byte flags + data, both images per launch
+    const bool packed = regs_ok && src == ColSrc::PackedFlags && n % 4 == 0;
+    ColFamily fam;
+    if (spectrum && boxp_pick_block(rad, C) > 0 && rad <= 107 && ((uintptr_t)srcData % 16 == 0) && ((uintptr_t)srcFlags % 4 == 0) &&
+        ((uintptr_t)dstW % 16 == 0) && ((uintptr_t)dstO % 16 == 0))
+        fam = ColFamily::SpecPipe;
+    else if (spectrum && boxr_pick_ks(rad) > 0) fam = ColFamily::SpecRing;     // from r = 4 on
+    // measured (1008 windows, both images): K4r 13.4 / 13.5 / 14.6 / 15.9 / 19.2 / 21.9 / 19.9 / 23.0 / 23.7 ms at
+    // r = 17 / 21 / 27 / 28 / 32 / 35 / 40 / 43 / 54; K4q with blocks of 8 (four waves per SIMD, r <= 43)
+    // 15.3 / 15.8 / 16.0 / 15.9 / 16.1 / 16.3 / 17.2 / 17.3, with blocks of 16 19.3 ... 20.8
+    else if (packed && boxq_pick_ks(rad) > 0 && rad <= 107 && (g_boxq_override == 1 || 2 * rad >= BOXQ_MIN_2R)) fam = ColFamily::StagePipe;
+    else if (packed && boxr_pick_ks_t(rad) > 0) fam = ColFamily::RegRing;
+    else if (bt > 0 && colfilter_use_lane4(rad) && !transposed_out && src != ColSrc::ByteFlags) fam = ColFamily::Lane4;
+    else {
+        if (bt > 0 && colfilter_use_lane4(rad) && src == ColSrc::ByteFlags) {
+            // byte flags with a medium radius (no lane-per-stage kernel for them): 4-ring kernel with a small block if it fits
+            bt = rad <= 20 ? 128 : (rad <= 40 ? 64 : 0);
+            while (bt > 64 && bt / 2 >= C) bt /= 2;
+        }
+        fam = bt > 0 ? ColFamily::LdsRing : ColFamily::MultiPass;
     }
-    if (srcmode == 0 && !deferred_denom && !transposed_out && weights_are_01 && W == 1 && boxr_pick_ks(rad) > 0 &&
-        (uint64_t)n * (uint64_t)C * 4u < (1ull << 31))
-        return launch_boxt_spec(r, boxr_pick_ks(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-    if (srcmode == 2 && !deferred_denom && !transposed_out && weights_are_01 && boxq_pick_ks(rad) > 0 && rad <= 107 &&
-        // measured (1008 windows, both images): K4r 13.4 / 13.5 / 14.6 / 15.9 / 19.2 / 21.9 / 19.9 / 23.0 / 23.7 ms at
-        // r = 17 / 21 / 27 / 28 / 32 / 35 / 40 / 43 / 54; K4q with blocks of 8 (four waves per SIMD, r <= 43)
-        // 15.3 / 15.8 / 16.0 / 15.9 / 16.1 / 16.3 / 17.2 / 17.3, with blocks of 16 19.3 ... 20.8
-        (g_boxq_override == 1 || 2 * rad >= BOXQ_MIN_2R) &&
-        n % 4 == 0 && (uint64_t)n * (uint64_t)C * 4u < (1ull << 31))
-        return launch_boxq(r, boxq_pick_ks(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-    if (srcmode == 2 && !deferred_denom && !transposed_out && weights_are_01 && boxr_pick_ks_t(rad) > 0 &&
-        n % 4 == 0 && (uint64_t)n * (uint64_t)C * 4u < (1ull << 31))   // signed 32-bit buffer offsets
-        return launch_boxt(r, boxr_pick_ks_t(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-    if (bt > 0 && colfilter_use_lane4(rad) && !transposed_out) {
-        size_t lds = (size_t)lane4_ring_capacity(rad) * 64 * sizeof(float);
-        dim3 grid((unsigned)cdiv(C, 16), (unsigned)W, 2);
-        // thread-safe one-time setup (C++11 static initialisation)
-        const hipError_t attr4 = [] {
-            hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lane4<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lane4<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lane4<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lane4<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lane4<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            return e;
-        }();
-        HIPCHK(attr4);
-        if (srcmode == 0) {
-            // byte flags + data (spectrum path): build-free variant is not provided;
-            // fall through to the 4-ring kernel below when it fits, else multi-pass
-        } else if (srcmode == 2) {
-            if (deferred_denom) {
-                *deferred_denom = denom;
-                hipLaunchKernelGGL((k_colfilter_lane4<2, false>), grid, dim3(64), lds, r.st, (const float*)nullptr, (const float*)nullptr,
-                                   srcData, srcFlags, dstW, dstO, n, C, rad, denom, (size_t)0, sws, dws);
-            } else {
-                hipLaunchKernelGGL((k_colfilter_lane4<2, true>), grid, dim3(64), lds, r.st, (const float*)nullptr, (const float*)nullptr,
-                                   srcData, srcFlags, dstW, dstO, n, C, rad, denom, (size_t)0, sws, dws);
-            }
-            LAUNCHCHK();
-            return TRI_OK;
-        } else if (deferred_denom) {
-            *deferred_denom = denom;
-            hipLaunchKernelGGL((k_colfilter_lane4<1, false>), grid, dim3(64), lds, r.st, (const float*)bufW, (const float*)bufO,
-                               srcData, srcFlags, dstW, dstO, n, C, rad, denom, bws, sws, dws);
-            LAUNCHCHK();
-            return TRI_OK;
-        } else {
-            hipLaunchKernelGGL((k_colfilter_lane4<1, true>), grid, dim3(64), lds, r.st, (const float*)bufW, (const float*)bufO,
-                               srcData, srcFlags, dstW, dstO, n, C, rad, denom, bws, sws, dws);
-            LAUNCHCHK();
-            return TRI_OK;
+    // --- launch ---
+    // (kernels that build their images ignore bufW / bufO)
+    const bool built = src != ColSrc::Images, divide = !deferred_denom;
+    const float *const inW = built ? nullptr : bufW, *const inO = built ? nullptr : bufO;
+    const size_t in_ws = built ? 0 : bws;
+    switch (fam) {
+        case ColFamily::SpecPipe:
+            if (boxp_pick_block(rad, C) == 16) return launch_boxp_spec_b<16, 16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
+            return launch_boxp_spec_b<8, 16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
+        case ColFamily::SpecRing:
+            return launch_boxt_spec(r, boxr_pick_ks(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom);
+        case ColFamily::StagePipe:
+            return launch_boxq(r, boxq_pick_ks(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
+        case ColFamily::RegRing:
+            return launch_boxt(r, boxr_pick_ks_t(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
+        case ColFamily::Lane4: {
+            HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lane4<0, true>, &k_colfilter_lane4<1, true>, &k_colfilter_lane4<1, false>,
+                                 &k_colfilter_lane4<2, false>, &k_colfilter_lane4<2, true>));
+            const auto k = src == ColSrc::PackedFlags ? (divide ? &k_colfilter_lane4<2, true> : &k_colfilter_lane4<2, false>)
+                                                      : (divide ? &k_colfilter_lane4<1, true> : &k_colfilter_lane4<1, false>);
+            if (!divide) *deferred_denom = denom;
+            hipLaunchKernelGGL(k, dim3((unsigned)cdiv(C, 16), (unsigned)W, 2), dim3(64), (size_t)lane4_ring_capacity(rad) * 64 * sizeof(float), r.st,
+                               inW, inO, srcData, srcFlags, dstW, dstO, n, C, rad, denom, in_ws, sws, dws);
+            break;
+        }
+        case ColFamily::LdsRing: {
+            HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lds<0, true, false>, &k_colfilter_lds<1, true, false>, &k_colfilter_lds<1, false, false>,
+                                 &k_colfilter_lds<1, true, true>, &k_colfilter_lds<2, false, false>, &k_colfilter_lds<2, true, false>));
+            // (the division is deferred for float images and packed flags only, the transposed output exists for float images only)
+            auto k = &k_colfilter_lds<0, true, false>;
+            bool div = true;
+            if (src == ColSrc::PackedFlags) { div = divide; k = div ? &k_colfilter_lds<2, true, false> : &k_colfilter_lds<2, false, false>; }
+            else if (transposed_out) k = &k_colfilter_lds<1, true, true>;
+            else if (src == ColSrc::Images) { div = divide; k = div ? &k_colfilter_lds<1, true, false> : &k_colfilter_lds<1, false, false>; }
+            if (!div) *deferred_denom = denom;
+            hipLaunchKernelGGL(k, dim3((unsigned)cdiv(C, bt), (unsigned)W, 2), dim3(bt), (size_t)4 * 2 * rad * bt * sizeof(float), r.st,
+                               inW, inO, srcData, srcFlags, dstW, dstO, n, C, rad, denom, in_ws, sws, dws, intw);
+            break;
+        }
+        case ColFamily::MultiPass: {
+            const int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
+            const auto k = src == ColSrc::ByteFlags ? &k_colfilter<0> : &k_colfilter<1>;
+            hipLaunchKernelGGL(k, dim3((unsigned)cdiv(C, blk), (unsigned)W, 2), dim3(blk), 0, r.st, bufW, bufO, srcData, srcFlags,
+                               dstW, dstO, n, C, rad, denom, bws, sws, dws);
+            break;
         }
     }
-    if (bt > 0 && colfilter_use_lane4(rad) && srcmode == 0) {
-        // spectrum path with a medium radius: 4-ring kernel with a small block if it fits
-        bt = rad <= 20 ? 128 : (rad <= 40 ? 64 : 0);
-        while (bt > 64 && bt / 2 >= C) bt /= 2;
-    }
-    if (bt > 0) {
-        size_t lds = (size_t)4 * 2 * rad * bt * sizeof(float);
-        dim3 grid((unsigned)cdiv(C, bt), (unsigned)W, 2);
-        const hipError_t attr_set = [] {
-            hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds<0, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds<1, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds<1, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds<1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds<2, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds<2, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            return e;
-        }();
-        HIPCHK(attr_set);
-        if (srcmode == 2) {
-            if (deferred_denom) {
-                *deferred_denom = denom;
-                hipLaunchKernelGGL((k_colfilter_lds<2, false, false>), grid, dim3(bt), lds, r.st, (const float*)nullptr, (const float*)nullptr,
-                                   srcData, srcFlags, dstW, dstO, n, C, rad, denom, (size_t)0, sws, dws, intw);
-            } else {
-                hipLaunchKernelGGL((k_colfilter_lds<2, true, false>), grid, dim3(bt), lds, r.st, (const float*)nullptr, (const float*)nullptr,
-                                   srcData, srcFlags, dstW, dstO, n, C, rad, denom, (size_t)0, sws, dws, intw);
-            }
-            LAUNCHCHK();
-            return TRI_OK;
-        }
-        if (transposed_out)
-            hipLaunchKernelGGL((k_colfilter_lds<1, true, true>), grid, dim3(bt), lds, r.st, (const float*)bufW, (const float*)bufO,
-                               srcData, srcFlags, dstW, dstO, n, C, rad, denom, bws, sws, dws, intw);
-        else if (srcmode == 0)
-            hipLaunchKernelGGL((k_colfilter_lds<0, true, false>), grid, dim3(bt), lds, r.st, (const float*)nullptr, (const float*)nullptr,
-                               srcData, srcFlags, dstW, dstO, n, C, rad, denom, (size_t)0, sws, dws, intw);
-        else if (deferred_denom) {
-            *deferred_denom = denom;
-            hipLaunchKernelGGL((k_colfilter_lds<1, false, false>), grid, dim3(bt), lds, r.st, (const float*)bufW, (const float*)bufO,
-                               srcData, srcFlags, dstW, dstO, n, C, rad, denom, bws, sws, dws, intw);
-        } else
-            hipLaunchKernelGGL((k_colfilter_lds<1, true, false>), grid, dim3(bt), lds, r.st, (const float*)bufW, (const float*)bufO,
-                               srcData, srcFlags, dstW, dstO, n, C, rad, denom, bws, sws, dws, intw);
-        LAUNCHCHK();
-        return TRI_OK;
-    }
-    int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-    dim3 grid((unsigned)cdiv(C, blk), (unsigned)W, 2);
-    if (srcmode == 0)
-        hipLaunchKernelGGL(k_colfilter<0>, grid, dim3(blk), 0, r.st, bufW, bufO, srcData, srcFlags,
-                           dstW, dstO, n, C, rad, denom, bws, sws, dws);
-    else
-        hipLaunchKernelGGL(k_colfilter<1>, grid, dim3(blk), 0, r.st, bufW, bufO, srcData, srcFlags,
-                           dstW, dstO, n, C, rad, denom, bws, sws, dws);
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -958,16 +898,12 @@ int launch_colfilter(const Run& r, int srcmode, float* bufW, float* bufO, const 
 // K7p applies: up to eight windows whose flag-byte ring fits the CU's LDS (there are no prefix rings any more)
 // (TRI_ST_NO_PIPE=1 keeps the global-scratch kernel)
 bool st_use_pipe(const StWin& sw) {
-    static const bool off = [] { const char* e = getenv("TRI_ST_NO_PIPE"); return e && e[0] == '1'; }();
+    static const bool off = is1(getenv("TRI_ST_NO_PIPE"));
     return !off && sw.nw >= 1 && sw.nw <= 8 && stp_lds_bytes(sw) <= 160 * 1024;
 }
 
 // TRI_ST_NO_PANEL=1: the time-axis SumThreshold and whoever shares its images read plain rows, never column panels (A/B runs)
-static bool st_no_panel() { static const bool off = [] { const char* e = getenv("TRI_ST_NO_PANEL"); return e && e[0] == '1'; }(); return off; }
-
-static hipError_t st_pipe_optin() {
-    return lds_optin(reinterpret_cast<const void*>(&k_colst_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
+static bool st_no_panel() { static const bool off = is1(getenv("TRI_ST_NO_PANEL")); return off; }
 
 // The SumThreshold kernels (kernels_sumthreshold.hpp): k_colst_dyn (any windows), k_colst_fused (register cascade),
 // k_colst_mask (lane-mask cascade) on rows or on 64-column panels, k_colst_pipe (up to eight windows, K7p)
@@ -990,7 +926,7 @@ int st_launch(hipStream_t st, StKernel k, const StWin& sw, const float* data, co
     else if (k == StKernel::Fused)
         hipLaunchKernelGGL((k_colst_fused<1, 2, 4, 8>), grid, dim3(blk), 0, st, data, med, out, d_chunk_ends, fa, thr_scale, L, C, G, ws_data, ws_out);
     else if (k == StKernel::Pipe) {
-        HIPCHK(st_pipe_optin());
+        HIPCHK(lds_optin_all(160 * 1024, &k_colst_pipe));
         hipLaunchKernelGGL(k_colst_pipe, dim3((unsigned)cdiv(C, 64), (unsigned)G, (unsigned)W), dim3(64 * sw.nw), stp_lds_bytes(sw), st,
                            data, med, out, d_chunk_ends, sw, stp_plan(sw), thr_scale, L, C, G, ws_data, ws_out);
     } else
@@ -1019,7 +955,7 @@ int launch_colst(const Run& r, const StWin& sw, const float* data, const double*
 // _linearly_interpolate_nans1d along the line axis of [L][C] images (K6 / K6p)
 int launch_interp(const Run& r, float* a, int L, int C, size_t ws, int64_t W, const uint8_t* nanflag,
                   const float* data, size_t ws_data, float* resid, float* panel = nullptr, size_t ws_panel = 0) {
-    static const bool one_pass = [] { const char* e = getenv("TRI_INTERP_ONE_PASS"); return e && e[0] == '1'; }();
+    static const bool one_pass = is1(getenv("TRI_INTERP_ONE_PASS"));
     const int nseg = (int)cdiv(L, INTERP_SEG);
     if (one_pass || nseg < 2 || nseg > 65535) {
         hipLaunchKernelGGL(k_colinterp, dim3((unsigned)cdiv(C, 256), (unsigned)W), dim3(256), 0, r.st, a, L, C, ws, nanflag, data, ws_data, resid, panel, ws_panel);
@@ -1096,28 +1032,18 @@ int launch_sub(const Run& r, const float* a, const float* b, float* out, size_t 
 
 // Frequency-axis stage reading the time-axis stage's TF images directly
 // (k_colfilter_lds_t).  Usable for radii whose four rings fit LDS at 128 threads.
-bool colfilter_t_usable(int rad) {
-    static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_TIN"); return e && e[0] == '1'; }();
-    return !off && rad > 0 && rad <= 16;
-}
+static bool filter_no_tin() { static const bool v = is1(getenv("TRI_FILTER_NO_TIN")); return v; }
+bool colfilter_t_usable(int rad) { return !filter_no_tin() && rad > 0 && rad <= 16; }
 
 int launch_colfilter_t(const Run& r, const float* srcW, const float* srcO, float* dstW, float* dstO,
                        int n, int C, int ld, int rad, size_t sws_img, size_t dws, int64_t W, float* deferred_denom) {
     float denom = box_denominator(rad);
     size_t lds = ((size_t)4 * 2 * rad * CFT_BT + (size_t)CFT_PF * (CFT_BT + 1)) * sizeof(float);
-    const hipError_t attr = [] {
-        hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return e;
-    }();
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lds_t<false>, &k_colfilter_lds_t<true>));
     dim3 grid((unsigned)cdiv(C, CFT_BT), (unsigned)W, 2);
-    if (deferred_denom) {
-        *deferred_denom = denom;
-        hipLaunchKernelGGL(k_colfilter_lds_t<false>, grid, dim3(CFT_BT), lds, r.st, srcW, srcO, dstW, dstO, n, C, ld, rad, denom, sws_img, dws);
-    } else {
-        hipLaunchKernelGGL(k_colfilter_lds_t<true>, grid, dim3(CFT_BT), lds, r.st, srcW, srcO, dstW, dstO, n, C, ld, rad, denom, sws_img, dws);
-    }
+    if (deferred_denom) *deferred_denom = denom;
+    const auto k = deferred_denom ? &k_colfilter_lds_t<false> : &k_colfilter_lds_t<true>;
+    hipLaunchKernelGGL(k, grid, dim3(CFT_BT), lds, r.st, srcW, srcO, dstW, dstO, n, C, ld, rad, denom, sws_img, dws);
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -1127,7 +1053,7 @@ int launch_colfilter_t(const Run& r, const float* srcW, const float* srcO, float
 // residual in dstW and the per-line NaN markers.  TRI_FILTER_NO_FUSED_DIV=1 keeps the
 // separate kernels (A/B runs).
 bool colfilter_tf_usable(int rad) {
-    static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_FUSED_DIV"); return e && e[0] == '1'; }();
+    static const bool off = is1(getenv("TRI_FILTER_NO_FUSED_DIV"));
     return !off && colfilter_t_usable(rad);
 }
 
@@ -1136,9 +1062,7 @@ int launch_colfilter_tf(const Run& r, const float* srcW, const float* srcO, floa
                         int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag) {
     float denom = box_denominator(rad);
     size_t lds = (size_t)2 * ((size_t)4 * 2 * rad * CFF_BT + (size_t)CFT_PF * (CFF_BT + 1)) * sizeof(float);
-    const hipError_t attr = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lds_tf<MODE>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lds_tf<MODE>));
     dim3 grid((unsigned)cdiv(C, CFF_BT), (unsigned)W);
     hipLaunchKernelGGL(k_colfilter_lds_tf<MODE>, grid, dim3(2 * CFF_BT), lds, r.st, srcW, srcO, dstW, dstO, data, n, C, ld, rad,
                        denom, sws_img, dws, ws_data, nanflag);
@@ -1161,37 +1085,19 @@ int launch_boxf_ks(const Run& r, const float* srcW, const float* srcO, float* ds
     if (srcO <= srcW || ((uint64_t)(srcO - srcW) + (uint64_t)C * ld) * 4u >= (1ull << 31))
         return set_err(TRI_EUNSUPPORTED, "fused frequency stage: the data image must follow the weight image within 2^31 bytes");
     const unsigned gap = (unsigned)(srcO - srcW);
-    const hipError_t attr = lds_optin(reinterpret_cast<const void*>(&k_boxf<KS, true, MODE>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_boxf<KS, true, MODE>));
     dim3 grid((unsigned)cdiv(C, 32), (unsigned)W);
     // 32 register slots: two waves per SIMD only pay while the LDS part leaves room for them (measured: r = 30,
     // 28 LDS slots: 10.0 ms per 252 windows at two waves per SIMD, 7.0 ms with the one-wave register budget)
-    bool one_wave = false;
+    auto k = d > 0 ? &k_boxf<KS, true, MODE> : &k_boxf<KS, false, MODE>;
     if constexpr (KS == 32) {
-        if (d > 14) {
-            const hipError_t attr1 = lds_optin(reinterpret_cast<const void*>(&k_boxf<KS, true, MODE, 1>),
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            HIPCHK(attr1);
-            hipLaunchKernelGGL((k_boxf<KS, true, MODE, 1>), grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
-                               denom, sws_img, dws, ws_data, nanflag, dstP, pws);
-            one_wave = true;
-        }
+        if (d > 14) { k = &k_boxf<KS, true, MODE, 1>; HIPCHK(lds_optin_all(160 * 1024, k)); }
     }
-    if (one_wave) {
-    } else if (d > 0)
-        hipLaunchKernelGGL((k_boxf<KS, true, MODE>), grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
-                           denom, sws_img, dws, ws_data, nanflag, dstP, pws);
-    else
-        hipLaunchKernelGGL((k_boxf<KS, false, MODE>), grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
-                           denom, sws_img, dws, ws_data, nanflag, dstP, pws);
+    hipLaunchKernelGGL(k, grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad, denom, sws_img, dws, ws_data, nanflag, dstP, pws);
     LAUNCHCHK();
     return TRI_OK;
 }
 
-static int boxq_pick_ks(int rad);
-extern thread_local int g_boxq_override;
-extern thread_local int g_boxq_b8_override;
 // K4qf: the fused frequency stage as an eight-wave stage pipeline (kernels_boxpipe.hpp)
 #ifndef BOXQF_MIN_2R
 #define BOXQF_MIN_2R 34
@@ -1208,9 +1114,7 @@ extern thread_local int g_boxq_b8_override;
 template <int KS, int MODE, int B = 16>
 int launch_boxqf_ks(const Run& r, const float* srcW, unsigned gap, float* dstW, float* dstO, const float* data,
                     int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag) {
-    const hipError_t attr = lds_optin(reinterpret_cast<const void*>(&k_boxqf<KS, MODE, B>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_boxqf<KS, MODE, B>));
     const BoxDenom denom = box_reciprocal(box_denominator(rad));
     dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
     hipLaunchKernelGGL((k_boxqf<KS, MODE, B>), grid, dim3(512), boxqf_lds_bytes(B, boxqf_dbl(KS, B)), r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
@@ -1227,7 +1131,7 @@ int launch_boxf(const Run& r, int ks, const float* srcW, const float* srcO, floa
     // the registers for it, and says so in *wroteP; the stage pipeline (K4qf) has no such output and leaves *wroteP alone
     if (MODE != 2 || n % 64 != 0) dstP = nullptr;
     {
-        static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_PIPE_F"); return e && e[0] == '1'; }();
+        static const bool off = is1(getenv("TRI_FILTER_NO_PIPE_F"));
         const int kq = boxq_pick_ks(rad);
         // Few, long lines (an SKA slab: 64 windows of 512 lines x 65536 channels): the one-wave-per-32-lines kernels (K4r) fill
         // half the machine at best; the stage pipeline (a workgroup of eight waves per 64 lines) then takes the small radii too.
@@ -1294,7 +1198,7 @@ thread_local unsigned long long g_boxx_last_stats[2] = {0, 0};
 // Long chunks on 128 threads per image where the line fits them (fewer instructions per line: see the kernel);
 // TRI_BOXX_NTI=256 forces the short chunks (A/B runs).
 int boxx_pick_l(int rad, int n) {
-    static const bool env_off = [] { const char* e = getenv("TRI_FILTER_NO_EXACT"); return e && e[0] == '1'; }();
+    static const bool env_off = is1(getenv("TRI_FILTER_NO_EXACT"));
     static const int force_nti = [] { const char* e = getenv("TRI_BOXX_NTI"); return e ? atoi(e) : 0; }();
     if (g_boxx_override == 0 || (g_boxx_override < 0 && (env_off || rad < BOXX_MIN_R))) return 0;
     if (rad < 1 || n % 4 != 0) return 0;
@@ -1321,15 +1225,10 @@ int launch_boxx_l(const Run& r, const float* srcW, unsigned gap, const float* da
     const size_t lds = boxx_lds_bytes(NTI, L, rad);
     dim3 grid((unsigned)C, (unsigned)W);
     // (the kernel also has a few static LDS bytes -- __syncthreads_or -- so 160 KB of dynamic LDS is refused: ask for 159)
-    if (boxx_recip_ok(rad)) {
-        HIPCHK(lds_optin(reinterpret_cast<const void*>(&k_boxx<NTI, L, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-        hipLaunchKernelGGL((k_boxx<NTI, L, MODE, true>), grid, dim3(2 * NTI), lds, r.st, srcW, gap, data, mask, outA, outB, n, ld, rad, denom, sws_img,
-                           ws_data, ws_mask, ws_outA, ws_outB, nanflag, stats);
-    } else {
-        HIPCHK(lds_optin(reinterpret_cast<const void*>(&k_boxx<NTI, L, MODE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-        hipLaunchKernelGGL((k_boxx<NTI, L, MODE, false>), grid, dim3(2 * NTI), lds, r.st, srcW, gap, data, mask, outA, outB, n, ld, rad, denom, sws_img,
-                           ws_data, ws_mask, ws_outA, ws_outB, nanflag, stats);
-    }
+    const auto k = boxx_recip_ok(rad) ? &k_boxx<NTI, L, MODE, true> : &k_boxx<NTI, L, MODE, false>;
+    HIPCHK(lds_optin_all(159 * 1024, k));
+    hipLaunchKernelGGL(k, grid, dim3(2 * NTI), lds, r.st, srcW, gap, data, mask, outA, outB, n, ld, rad, denom, sws_img,
+                       ws_data, ws_mask, ws_outA, ws_outB, nanflag, stats);
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -1355,30 +1254,18 @@ int launch_boxx(const Run& r, int L, const float* srcW, const float* srcO, const
 }
 
 // Lane-per-stage variant of the same (radii 17..LANE4_R_MAX): k_colfilter_lane4<3, *>.
-bool colfilter_t4_usable(int rad) {
-    static const bool off = [] { const char* e = getenv("TRI_FILTER_NO_TIN"); return e && e[0] == '1'; }();
-    return !off && colfilter_use_lane4(rad);
-}
+bool colfilter_t4_usable(int rad) { return !filter_no_tin() && colfilter_use_lane4(rad); }
 
 int launch_colfilter_t4(const Run& r, const float* srcW, const float* srcO, float* dstW, float* dstO,
                         int n, int C, int ld, int rad, size_t sws_img, size_t dws, int64_t W, float* deferred_denom) {
     float denom = box_denominator(rad);
     size_t lds = ((size_t)lane4_ring_capacity(rad) * 64 + 32 * 17) * sizeof(float);
-    const hipError_t attr = [] {
-        hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lane4<3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = lds_optin(reinterpret_cast<const void*>(&k_colfilter_lane4<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return e;
-    }();
-    HIPCHK(attr);
+    HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lane4<3, false>, &k_colfilter_lane4<3, true>));
     dim3 grid((unsigned)cdiv(C, 16), (unsigned)W, 2);
-    if (deferred_denom) {
-        *deferred_denom = denom;
-        hipLaunchKernelGGL((k_colfilter_lane4<3, false>), grid, dim3(64), lds, r.st, srcW, srcO, (const float*)nullptr, (const uint8_t*)nullptr,
-                           dstW, dstO, n, C, rad, denom, sws_img, (size_t)ld, dws);
-    } else {
-        hipLaunchKernelGGL((k_colfilter_lane4<3, true>), grid, dim3(64), lds, r.st, srcW, srcO, (const float*)nullptr, (const uint8_t*)nullptr,
-                           dstW, dstO, n, C, rad, denom, sws_img, (size_t)ld, dws);
-    }
+    if (deferred_denom) *deferred_denom = denom;
+    const auto k = deferred_denom ? &k_colfilter_lane4<3, false> : &k_colfilter_lane4<3, true>;
+    hipLaunchKernelGGL(k, grid, dim3(64), lds, r.st, srcW, srcO, (const float*)nullptr, (const uint8_t*)nullptr,
+                       dstW, dstO, n, C, rad, denom, sws_img, (size_t)ld, dws);
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -1453,7 +1340,7 @@ int spectrum_background(const Run& r) {
             continue;
         }
         if (rad > 0) {
-            int rc = launch_colfilter(r, 0, ws.sw, ws.so, ws.sdata, ws.sbgf, ws.sw, ws.so, Fa, Wn, rad, 0, 0, 0, 1, nullptr, false, true);
+            int rc = launch_colfilter(r, ColSrc::ByteFlags, ws.sw, ws.so, ws.sdata, ws.sbgf, ws.sw, ws.so, Fa, Wn, rad, 0, 0, 0, 1, COL_WEIGHTS_01);
             if (rc) return rc;
         } else {
             hipLaunchKernelGGL(k_build_wo, grid1(nS, 1), dim3(256), 0, r.st, ws.sdata, ws.sbgf, ws.sw, ws.so, nS, (size_t)0, (size_t)0);
@@ -1479,8 +1366,347 @@ int spectrum_background(const Run& r) {
 // background in FT layout in rows [0,Fa) of ws.Bo and the residual
 // data - background in rows [0,Fa) of ws.Bw (window stride PF*T).
 static bool bg_flags_packed(int T, size_t N) {
-    static const bool no_pack = [] { const char* e = getenv("TRI_NO_PACKED_FLAGS"); return e && e[0] == '1'; }();
+    static const bool no_pack = is1(getenv("TRI_NO_PACKED_FLAGS"));
     return !no_pack && (T % 4 == 0) && (N % 4 == 0);
+}
+
+// ---- the routes of one background iteration, picked once (pick_bg_step) and then only switched on -------------------------
+
+enum class TimeStage {
+    BuildOnly,        // r0 == 0: the weight / data images themselves
+    PackedSweep,      // single sweep straight from (data, TF4 flag words): no image build
+    Prebuilt,         // images built first, float images through the single sweep (faster than byte loads in its loop)
+    PrebuiltDirectFT, // ... which writes the FT layout itself (TRI_FILTER_DIRECT_FT=1; measured no faster than two transposes)
+    ByteFlags         // built on the fly from byte flags (multi-pass kernel of the large radii: 11.4 vs 16.8 ms per call with a build)
+};
+enum class FreqStage {
+    ExactRows,        // K4x: rows of the time stage's TF images in, rows out, then to FT
+    FusedRing,        // K4r / K4qf + masked division in one kernel (launch_boxf)
+    FusedLds,         // four LDS rings + masked division in one kernel (launch_colfilter_tf)
+    LdsDiv,           // four LDS rings from the TF images, then the division (launch_colfilter_t)
+    Lane4Div,         // lane per stage from the TF images, then the division (launch_colfilter_t4)
+    Transposed        // two transposes, launch_colfilter on the FT images (none at r = 0), then the division
+};
+enum class Reject {
+    None,             // final pass
+    InRows,           // K4x iterations: block medians and rejection where the rows lie (TF4 flag words)
+    Tile,             // K3t: median + rejection + TF4 re-pack, tile-parallel
+    OnePass,          // K3r: the same, one workgroup per block
+    MedianReject4T,   // block medians, then rejection + TF4 re-pack in one pass
+    MedianReject4,    // block medians, then the vector rejection and a transpose of the flags
+    MedianReject      // block medians, then the scalar rejection and a transpose of the flags
+};
+
+// The frequency stage of one radius: lines of n positions, C of them per window, the data image `gap` floats behind the
+// weight image.  Shared by the flagger and tri_bench_boxfilter.
+struct FreqPick {
+    FreqStage route;
+    int ks;           // FusedRing: register slots of K4r
+    int xl;           // ExactRows: chunk code of K4x
+    size_t off;       // Transposed: first element of the FT images (rows [4r, 4r + n) of the padded buffers for the in-place
+                      // multi-pass filter, rows [0, n) for the single-sweep one)
+};
+static FreqPick pick_freq_unfused(int rad, int C) {
+    return {FreqStage::Transposed, 0, 0, colfilter_lds_block(rad, C) > 0 ? 0 : (size_t)4 * rad * C};
+}
+static FreqPick pick_freq_stage(int rad, int n, int C, size_t gap, bool exact_rows) {
+    // register-ring fused stage: signed 32-bit buffer offsets, one descriptor over both images of a window
+    const int ks = ((uint64_t)gap + (uint64_t)n * C) * 4u < (1ull << 31) ? boxr_pick_ks_f(rad) : 0;
+    // exact row filter where the stage pipelines end
+    const int xl = (rad > 0 && (!ks || rad >= BOXX_MIN_R) && exact_rows) ? boxx_pick_l(rad, n) : 0;
+    if (xl > 0) return {FreqStage::ExactRows, 0, xl, 0};
+    if (ks > 0) return {FreqStage::FusedRing, ks, 0, 0};
+    if (colfilter_tf_usable(rad)) return {FreqStage::FusedLds, 0, 0, 0};
+    if (colfilter_t_usable(rad)) return {FreqStage::LdsDiv, 0, 0, 0};
+    if (colfilter_t4_usable(rad)) return {FreqStage::Lane4Div, 0, 0, 0};
+    return pick_freq_unfused(rad, C);
+}
+
+// K3t (tile-parallel median + rejection): scratch sizes and whether the rejection iterations take it
+struct TileRoute { bool use; size_t ccap, ucap; int ytiles; };
+static int medrej_force_fallback() { static const int v = [] { const char* e = getenv("TRI_MEDREJ_FORCE_FALLBACK"); return e ? atoi(e) : 0; }(); return v; }
+static bool no_fused_reject() { static const bool v = is1(getenv("TRI_NO_FUSED_REJECT")); return v; }
+// K3r is opt-in (TRI_FUSED_MEDREJ=1): one workgroup per block does not stream fast enough -- 3.7 against 3.0 ms per 252
+// windows for the two kernels, scripts/ubench/medrej_dev.hip
+static bool fused_medrej() { static const bool v = is1(getenv("TRI_FUSED_MEDREJ")); return v; }
+static TileRoute pick_tile_route(const Run& r, bool packed) {
+    const Plan& pl = r.pl;
+    static const bool no_tile = is1(getenv("TRI_NO_TILE_MEDREJ"));
+    const int T = (int)pl.T, G = (int)pl.G;
+    const size_t wsA = 2 * (size_t)pl.PT * pl.Fa, wsB = (size_t)pl.PF * T;
+    const size_t mr_nb = (size_t)pl.maxchunk * T;                  // samples of the largest block
+    TileRoute t = {false, (mr_nb / 4) & ~(size_t)3, (mr_nb / 8) & ~(size_t)3, 0};
+    for (int g = 0; g < G; g++) t.ytiles += (int)cdiv(r.p->chunk_ends[g + 1] - r.p->chunk_ends[g], 64);
+    // (blocks too small to predict from -- fewer than 65536 samples -- would all take the redo path: the two-kernel route)
+    t.use = pl.vec && wsB % 4 == 0 && wsA % 4 == 0 && packed && !no_fused_reject() && !no_tile && !fused_medrej() && G <= 65535 &&
+            mrt_scratch_words(G, t.ccap, t.ucap) <= wsA && (medrej_force_fallback() || (pl.maxchunk - 1) * (int64_t)T >= 65536) &&
+            t.ytiles > 0 && t.ytiles <= 65535;
+    return t;
+}
+// K3r scratch per (window, chunk) block: the dead time-stage images, half for the window's keys, half for the undecided
+// samples' indices
+static unsigned medrej_capq(size_t wsA, int G) {
+    const size_t per_block = (wsA / (size_t)G) & ~(size_t)7;
+    return (unsigned)std::min<size_t>(per_block / 2, 0x3ffffffcu);
+}
+
+struct BgStep {
+    int r0, r1;
+    bool final_pass;
+    TimeStage time;
+    bool time_needs_bytes;   // the time stage reads a TF byte image of the flags, rebuilt into ws.comb while they are packed
+    bool time_defers;        // it leaves its division by float32(d)**4 to the transposes (else it divides itself)
+    FreqPick freq;
+    bool freq_transposes;    // Transposed: the FT images still have to be made (not after PrebuiltDirectFT)
+    Reject reject;
+    bool reads_ft_flags;     // the FT flag bytes are read: by the time stage's byte image, or by an FT-native median / rejection
+};
+
+// ext = background_iterations .. 1: rejection iterations; 0: the final pass.  packed: bg_flags_packed().
+static BgStep pick_bg_step(const Run& r, bool packed, bool tile_route, int ext) {
+    const Plan& pl = r.pl;
+    const int T = (int)pl.T, Fa = (int)pl.Fa, G = (int)pl.G;
+    const size_t wsA = 2 * (size_t)pl.PT * Fa, wsB = (size_t)pl.PF * T;
+    BgStep s;
+    s.final_pass = ext == 0;
+    const double e = (double)(s.final_pass ? 1 : ext);
+    s.r0 = (int)box_radius(e * r.p->spike_width_time);
+    s.r1 = (int)box_radius(e * r.p->spike_width_freq);
+
+    static const bool prebuild = [] { const char* e = getenv("TRI_TIME_PREBUILD"); return !(e && e[0] == '0'); }();
+    const bool sweep = s.r0 > 0 && colfilter_lds_block(s.r0, Fa) > 0;
+    if (s.r0 == 0) s.time = TimeStage::BuildOnly;
+    else if (sweep && packed) s.time = TimeStage::PackedSweep;
+    else if (sweep && prebuild) {
+        static const bool want_direct = is1(getenv("TRI_FILTER_DIRECT_FT"));
+        s.time = (want_direct && T % 4 == 0 && wsB % 4 == 0) ? TimeStage::PrebuiltDirectFT : TimeStage::Prebuilt;
+    } else s.time = TimeStage::ByteFlags;
+    s.time_needs_bytes = packed && (s.time == TimeStage::BuildOnly || s.time == TimeStage::ByteFlags);
+
+    // (K4x masks the unmasked cached amplitudes with the iteration's input flags: it needs them)
+    s.freq = s.time == TimeStage::PrebuiltDirectFT ? pick_freq_unfused(s.r1, T)
+                                                   : pick_freq_stage(s.r1, Fa, T, (size_t)(r.ws.Ao - r.ws.Aw), !r.ampl_cached || r.data_mask);
+    s.freq_transposes = s.time != TimeStage::PrebuiltDirectFT;
+    s.time_defers = s.freq.route == FreqStage::Transposed;
+
+    // K4x iterations stay in the row layout altogether (TRI_FILTER_NO_TF_REJECT=1: transposes + FT kernels)
+    static const bool no_tfr = is1(getenv("TRI_FILTER_NO_TF_REJECT"));
+    const bool vec4 = pl.vec && wsB % 4 == 0;
+    if (s.final_pass) s.reject = Reject::None;
+    else if (s.freq.route == FreqStage::ExactRows && packed && !no_tfr && G <= 65535 && (uint64_t)T * Fa * 4u < (1ull << 31))
+        s.reject = Reject::InRows;
+    else if (tile_route) s.reject = Reject::Tile;
+    else if (vec4 && wsA % 4 == 0 && packed && !no_fused_reject() && fused_medrej() && medrej_capq(wsA, G) >= 1024 && G <= 65535 &&
+             (uint64_t)T * Fa * 4u < (1ull << 32))
+        s.reject = Reject::OnePass;
+    else if (vec4 && packed && !no_fused_reject()) s.reject = Reject::MedianReject4T;
+    else s.reject = vec4 ? Reject::MedianReject4 : Reject::MedianReject;
+    s.reads_ft_flags = s.time_needs_bytes || (!s.final_pass && s.reject != Reject::InRows);
+    return s;
+}
+
+// The images the time and frequency stages work on: the flagger's workspace, or the arguments of tri_bench_boxfilter.
+// TF images are [T][Fa], FT images [Fa][T]; every stride is per window, in elements.
+struct BgImages {
+    int T, Fa;
+    int64_t W;
+    const float *dataTF, *dataFT;   // amplitudes (stride T * Fa)
+    const uint8_t* flagsTF;         // background flags of the time stage: bytes, or TF4 words when packed (stride T * Fa bytes)
+    uint8_t* comb;                  // room for their byte image while they are packed
+    float *Aw, *Ao; size_t wsA;     // TF weight / weight * data images: time stage out, frequency stage in
+    float *Bw, *Bo; size_t wsB;     // FT images: frequency stage out
+    float* rows; size_t ws_rows;    // ExactRows: where K4x leaves |data - background| / the background as rows
+    const uint8_t* mask; size_t ws_mask;   // ExactRows: byte mask of the data rows, or NULL
+    uint8_t* nanflag;               // final pass: per-line "background holds a NaN" markers, W * T ints
+    float* residP;                  // final pass, optional: the residual a second time, as column panels (stride T * Fa)
+    unsigned long long* xstats;     // ExactRows, optional: pass counters
+};
+
+// What survives from one iteration to the next
+struct BgState {
+    uint8_t *cur_ft, *alt_ft;   // FT flag bytes: current image, and the one K3t / K3r write (the two then swap)
+    bool bgf_ft_stale;          // the FT flag bytes lag behind the TF4 words (rows-only rejection iterations)
+    bool wrote_panel;           // the final frequency stage left the residual in residP as well
+};
+
+// --- time axis (TF layout: line = time, column = channel) ---
+// *den_t: the division the stage left to the transposes, or 0
+static int bg_time_stage(const Run& r, const BgStep& s, const BgImages& im, const BgState& st, float* den_t) {
+    const int T = im.T, Fa = im.Fa;
+    const size_t N = (size_t)T * Fa;
+    const int64_t W = im.W;
+    int rc = TRI_OK;
+    *den_t = 0.0f;
+    float* const defer = s.time_defers ? den_t : nullptr;
+    const uint8_t* fl = im.flagsTF;
+    if (s.time_needs_bytes) {
+        rc = launch_transpose<uint8_t>(r, st.cur_ft, im.comb, Fa, T, N, N, W);
+        if (rc) return rc;
+        fl = im.comb;
+    }
+    switch (s.time) {
+        case TimeStage::BuildOnly:
+            hipLaunchKernelGGL(k_build_wo, grid1(N, W), dim3(256), 0, r.st, im.dataTF, fl, im.Aw, im.Ao, N, N, im.wsA);
+            LAUNCHCHK();
+            return TRI_OK;
+        case TimeStage::PackedSweep:
+            return launch_colfilter(r, ColSrc::PackedFlags, im.Aw, im.Ao, im.dataTF, fl, im.Aw, im.Ao, T, Fa, s.r0, im.wsA, N, im.wsA, W, COL_WEIGHTS_01, defer);
+        case TimeStage::Prebuilt:
+        case TimeStage::PrebuiltDirectFT:
+            if (N % 4 == 0 && im.wsA % 4 == 0)
+                hipLaunchKernelGGL(k_build_wo4, grid1(N / 4, W), dim3(256), 0, r.st, im.dataTF, fl, im.Aw, im.Ao, N / 4, N, im.wsA);
+            else
+                hipLaunchKernelGGL(k_build_wo, grid1(N, W), dim3(256), 0, r.st, im.dataTF, fl, im.Aw, im.Ao, N, N, im.wsA);
+            LAUNCHCHK();
+            if (s.time == TimeStage::Prebuilt)
+                return launch_colfilter(r, ColSrc::Images, im.Aw, im.Ao, nullptr, nullptr, im.Aw, im.Ao, T, Fa, s.r0, im.wsA, 0, im.wsA, W, COL_WEIGHTS_01, defer);
+            return launch_colfilter(r, ColSrc::Images, im.Aw, im.Ao, nullptr, nullptr, im.Bw + s.freq.off, im.Bo + s.freq.off, T, Fa, s.r0, im.wsA, 0, im.wsB, W, COL_TRANSPOSED_OUT);
+        case TimeStage::ByteFlags:
+            return launch_colfilter(r, ColSrc::ByteFlags, im.Aw, im.Ao, im.dataTF, fl, im.Aw, im.Ao, T, Fa, s.r0, im.wsA, N, im.wsA, W);
+    }
+    return set_err(TRI_EINVAL, "internal: no such time stage");
+}
+
+// --- frequency axis (FT layout: line = channel, column = time) + masked division ---
+// Leaves |data - background| (final pass: the background) in im.Bo and, in the final pass, data - background in im.Bw;
+// with Reject::InRows |data - background| stays in im.rows.
+template <int MODE>
+static int bg_freq_stage_mode(const Run& r, const BgStep& s, const BgImages& im, BgState& st, float den_t) {
+    const int T = im.T, Fa = im.Fa, r1 = s.r1;
+    const size_t N = (size_t)T * Fa, wsA = im.wsA, wsB = im.wsB;
+    const int64_t W = im.W;
+    uint8_t* const nan = MODE == 2 ? im.nanflag : nullptr;
+    float den_f = 0.0f;   // division deferred to masked_div
+    int rc = TRI_OK;
+    // im.nanflag (W * T ints, idle until the end of the iteration) holds the per-line NaN markers
+    if (MODE == 2) HIPCHK(hipMemsetAsync(im.nanflag, 0, (size_t)W * T, r.st));
+    switch (s.freq.route) {
+        case FreqStage::ExactRows:
+            // (the flagger: im.rows == im.Ao, the rows are filtered in place; MODE 2: im.Aw <- data - background)
+            rc = launch_boxx<MODE>(r, s.freq.xl, im.Aw, im.Ao, im.dataTF, im.mask, im.rows, MODE == 2 ? im.Aw : nullptr, Fa, T, Fa, r1, wsA, N,
+                                   im.ws_mask, im.ws_rows, MODE == 2 ? wsA : 0, W, nan, im.xstats);
+            if (!rc && MODE == 2) rc = launch_transpose<float>(r, im.Aw, im.Bw, T, Fa, wsA, wsB, W);
+            if (rc || s.reject == Reject::InRows) return rc;
+            return launch_transpose<float>(r, im.rows, im.Bo, T, Fa, im.ws_rows, wsB, W);
+        case FreqStage::FusedRing:
+            return launch_boxf<MODE>(r, s.freq.ks, im.Aw, im.Ao, im.Bw, im.Bo, im.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, nan,
+                                     MODE == 2 ? im.residP : nullptr, MODE == 2 ? N : 0, &st.wrote_panel);
+        case FreqStage::FusedLds:
+            return launch_colfilter_tf<MODE>(r, im.Aw, im.Ao, im.Bw, im.Bo, im.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, nan);
+        case FreqStage::LdsDiv:
+            rc = launch_colfilter_t(r, im.Aw, im.Ao, im.Bw, im.Bo, Fa, T, Fa, r1, wsA, wsB, W, &den_f);
+            break;
+        case FreqStage::Lane4Div:
+            rc = launch_colfilter_t4(r, im.Aw, im.Ao, im.Bw, im.Bo, Fa, T, Fa, r1, wsA, wsB, W, &den_f);
+            break;
+        case FreqStage::Transposed:
+            if (s.freq_transposes) {
+                rc = launch_transpose<float>(r, im.Aw, im.Bw + s.freq.off, T, Fa, wsA, wsB, W, den_t);
+                if (!rc) rc = launch_transpose<float>(r, im.Ao, im.Bo + s.freq.off, T, Fa, wsA, wsB, W, den_t);
+            }
+            if (!rc && r1 > 0) rc = launch_colfilter(r, ColSrc::Images, im.Bw, im.Bo, nullptr, nullptr, im.Bw, im.Bo, Fa, T, r1, wsB, 0, wsB, W, 0, &den_f);
+            break;
+    }
+    if (rc) return rc;
+    return launch_masked_div<MODE>(r, im.Bw, im.Bo, im.dataFT, N, wsB, N, W, den_f, nan, MODE == 2 ? T : 1);
+}
+static int bg_freq_stage(const Run& r, const BgStep& s, const BgImages& im, BgState& st, float den_t) {
+    return s.final_pass ? bg_freq_stage_mode<2>(r, s, im, st, den_t) : bg_freq_stage_mode<1>(r, s, im, st, den_t);
+}
+
+// --- block medians of |data - background| and rejection of a non-final iteration; the flags end up in st.cur_ft (FT bytes,
+//     unless Reject::InRows) and in ws.bgfTF (the time stage's form) ---
+static int bg_reject_stage(const Run& r, const BgStep& s, const TileRoute& tile, bool packed, BgState& st) {
+    const Plan& pl = r.pl;
+    const Ws& ws = r.ws;
+    const int T = (int)pl.T, Fa = (int)pl.Fa, G = (int)pl.G;
+    const int64_t W = r.Wb;
+    const size_t N = (size_t)T * Fa, wsA = 2 * (size_t)pl.PT * Fa, wsB = (size_t)pl.PF * T;
+    const double rej = TRI_MAD_NORMAL * r.p->background_reject;
+    if (s.reject == Reject::None) return TRI_OK;
+    // (only K3t leaves the flags it reads alone: see flags_in_place in background2d)
+    if (s.reject != Reject::Tile && st.cur_ft == ws.flagsFT)
+        return set_err(TRI_EUNSUPPORTED, "internal: background flags read in place on a route that rewrites them");
+    switch (s.reject) {
+        case Reject::InRows: {
+            // block medians over (all times) x (chunk channels) of the row image with the TF4 flag words, rejection straight
+            // into those words -- no FT image of the residual or of the flags in this iteration (the FT flags are rebuilt
+            // when an iteration that reads them follows)
+            unsigned* gc = reinterpret_cast<unsigned*>(ws.Aw);          // the weight rows are dead: candidate scratch
+            unsigned cap = (unsigned)(std::min<size_t>((wsA / 2) / (size_t)G, 0x7fffffffu) & ~(size_t)3);
+            if (median_no_predict() || (int64_t)cap < pl.maxchunk * pl.T || wsA % 4 != 0) { gc = nullptr; cap = 0; }
+            // (not through launch_median_kernel: a block of rows with TF4 flag words, not row segments)
+            hipLaunchKernelGGL((k_median2<false, true>), dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Ao,
+                               (const uint8_t*)ws.bgfTF, ws.med, wsA, N, (size_t)0, (size_t)1, ws.segC_start, ws.segC_len, 1, G,
+                               gc, gc ? wsA : (size_t)0, cap, T / 4, Fa);
+            hipLaunchKernelGGL(k_reject_tf, dim3((unsigned)cdiv(Fa, 256), (unsigned)(T / 4), (unsigned)W), dim3(256), 0, r.st,
+                               (const float*)ws.Ao, reinterpret_cast<unsigned*>(ws.bgfTF), ws.med, ws.d_chunk_of, rej, T / 4, Fa, Fa, G,
+                               wsA, N / 4);
+            LAUNCHCHK();
+            st.bgf_ft_stale = true;
+            return TRI_OK;
+        }
+        case Reject::Tile: {
+            // K3t (kernels_reject_tile.hpp): predict (per block) -> pass (per 64 x 64-word tile) -> finish (per block) -> redo of
+            // the blocks that failed a check.  Scratch: the dead time-stage images of the window.  It never modifies the flags
+            // it reads: cur_ft in, alt_ft out, then the two swap.
+            unsigned* sc = reinterpret_cast<unsigned*>(ws.Aw);
+            hipLaunchKernelGGL(k_mr_predict, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)st.cur_ft,
+                               ws.d_chunk_ends, rej, T / 4, G, wsB, N, sc, wsA, tile.ccap, tile.ucap, medrej_force_fallback());
+            for (unsigned round = 1; round <= 2; round++) {        // (round 2: only the blocks whose median missed the predicted window)
+                hipLaunchKernelGGL(k_mr_pass, dim3((unsigned)cdiv(T / 4, 64), (unsigned)tile.ytiles, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo,
+                                   (const uint8_t*)st.cur_ft, st.alt_ft, ws.bgfTF, ws.d_chunk_ends, Fa, T / 4, G, wsB, N, sc, wsA, tile.ccap, tile.ucap, round);
+                hipLaunchKernelGGL(k_mr_finish, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)st.cur_ft, st.alt_ft,
+                                   ws.bgfTF, ws.med, ws.d_chunk_ends, rej, Fa, T / 4, G, wsB, N, sc, wsA, tile.ccap, tile.ucap, round);
+            }
+            hipLaunchKernelGGL(k_median_reject, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)st.cur_ft,
+                               st.alt_ft, ws.bgfTF, ws.med, ws.d_chunk_ends, rej, Fa, T / 4, G, wsB, N, sc, wsA, 0u, 0u, 1,
+                               (const unsigned*)sc, wsA, (int)MRT_PARW, 11);
+            LAUNCHCHK();
+            // (read in place, ws.flagsFT stays as it is -- the time medians of the residual read it: the first iteration
+            //  writes ws.bgfFT, and from then on ws.bgfFT and ws.fflFT alternate)
+            std::swap(st.cur_ft, st.alt_ft);
+            if (st.alt_ft == ws.flagsFT) st.alt_ft = ws.fflFT;
+            return TRI_OK;
+        }
+        case Reject::OnePass: {
+            // K3r (kernels_reject.hpp) writes the updated FT flags to a SECOND image (its fallback redoes a block from the
+            // input flags), so the FT flag image alternates between ws.bgfFT and ws.fflFT (free until the frequency-axis
+            // SumThreshold writes it)
+            const unsigned capq = medrej_capq(wsA, G);
+            hipLaunchKernelGGL(k_median_reject, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)st.cur_ft,
+                               st.alt_ft, ws.bgfTF, ws.med, ws.d_chunk_ends, rej, Fa, T / 4, G, wsB, N,
+                               reinterpret_cast<unsigned*>(ws.Aw), wsA, capq, capq, medrej_force_fallback());
+            LAUNCHCHK();
+            std::swap(st.cur_ft, st.alt_ft);
+            return TRI_OK;
+        }
+        default:   // the three median-then-reject routes: below
+            break;
+    }
+    // block medians over (all times) x (chunk channels): contiguous in FT
+    // (the time stage's images in ws.Aw / ws.Ao are dead here: candidate scratch, wsA / G keys per block)
+    MedianJob j;
+    j.data = ws.Bo; j.flags = st.cur_ft; j.med = ws.med; j.WSd = wsB; j.WSf = N;
+    j.seg_start = ws.segB_start; j.seg_len = ws.segB_len; j.R = 1; j.G = G; j.W = W; j.max_len = pl.maxchunk * pl.T;
+    j.vec_ok = T % 4 == 0 && wsB % 4 == 0 && N % 4 == 0;
+    j.gcand = reinterpret_cast<unsigned*>(ws.Aw); j.cand_ws = wsA;
+    j.cand_cap = (unsigned)(std::min<size_t>(wsA / (size_t)G, 0x7fffffffu) & ~(size_t)3);
+    const int rc = launch_median(r, j);
+    if (rc) return rc;
+    if (s.reject == Reject::MedianReject4T) {
+        hipLaunchKernelGGL(k_reject4_t, dim3((unsigned)cdiv(T / 4, 64), (unsigned)cdiv(Fa, 64), (unsigned)W), dim3(64, 4), 0, r.st,
+                           ws.Bo, st.cur_ft, ws.bgfTF, ws.med, ws.d_chunk_of, rej, Fa, T / 4, G, wsB, N);
+        LAUNCHCHK();
+        return TRI_OK;
+    }
+    if (s.reject == Reject::MedianReject4)
+        hipLaunchKernelGGL(k_reject4, grid1(N / 4, W), dim3(256), 0, r.st, ws.Bo, st.cur_ft, ws.med, ws.d_chunk_of, rej, T / 4, G, N / 4, wsB, N);
+    else
+        hipLaunchKernelGGL(k_reject<true>, grid1(N, W), dim3(256), 0, r.st, ws.Bo, st.cur_ft, ws.med, ws.d_chunk_of, rej, Fa, T, G, wsB, N);
+    LAUNCHCHK();
+    if (packed) return launch_transpose<float>(r, reinterpret_cast<const float*>(st.cur_ft), reinterpret_cast<float*>(ws.bgfTF), Fa, T / 4, N / 4, N / 4, W);
+    return launch_transpose<uint8_t>(r, st.cur_ft, ws.bgfTF, Fa, T, N, N, W);
 }
 
 // residP (optional): where the final frequency stage may leave the residual a second time, as column panels
@@ -1488,292 +1714,64 @@ static bool bg_flags_packed(int T, size_t N) {
 int background2d(const Run& r, bool flagsFT_current, float* residP = nullptr, bool* wroteP = nullptr) {
     const Plan& pl = r.pl;
     const Ws& ws = r.ws;
-    int T = (int)pl.T, Fa = (int)pl.Fa, G = (int)pl.G;
-    int64_t W = r.Wb;
-    size_t N = (size_t)T * Fa;
-    size_t wsA = 2 * (size_t)pl.PT * Fa, wsB = (size_t)pl.PF * T;   // Aw / Ao interleaved per window (carve)
+    const int T = (int)pl.T, Fa = (int)pl.Fa;
+    const int64_t W = r.Wb;
+    const size_t N = (size_t)T * Fa;
     // Background flags live in FT layout (ws.bgfFT).  For the time-axis stage
     // they are needed per (time, channel) column thread: either as a TF byte
     // image (general case) or, when T % 4 == 0, packed four times per word
     // ("TF4": [T/4][Fa] uint32) -- which is exactly the 32-bit transpose of the
     // FT byte image viewed as [Fa][T/4] words.
     const bool packed = bg_flags_packed(T, N);
-    // The routes of the loop below that depend on the plan alone, picked once.
-    // fused frequency stage (register ring) and exact row filter of a frequency radius (see the loop)
-    auto ksf_of = [&](int r1) { return ((uint64_t)N * 4u < (1ull << 31) && ((uint64_t)(ws.Ao - ws.Aw) + N) * 4u < (1ull << 31)) ? boxr_pick_ks_f(r1) : 0; };
-    auto xl_of = [&](int r1) { return (r1 > 0 && (!ksf_of(r1) || r1 >= BOXX_MIN_R) && (!r.ampl_cached || r.data_mask)) ? boxx_pick_l(r1, Fa) : 0; };
-    static const bool no_fuse = [] { const char* e = getenv("TRI_NO_FUSED_REJECT"); return e && e[0] == '1'; }();
-    static const bool no_tile = [] { const char* e = getenv("TRI_NO_TILE_MEDREJ"); return e && e[0] == '1'; }();
-    static const bool no_medrej = [] { const char* e = getenv("TRI_FUSED_MEDREJ"); return !(e && e[0] == '1'); }();
-    static const int medrej_fallback = [] { const char* e = getenv("TRI_MEDREJ_FORCE_FALLBACK"); return e ? atoi(e) : 0; }();
-    // K3t (tile-parallel median + rejection, see the loop): scratch sizes and whether the rejection iterations take it
-    const size_t mr_nb = (size_t)pl.maxchunk * T;                  // samples of the largest block
-    const size_t ccap = (mr_nb / 4) & ~(size_t)3, ucap = (mr_nb / 8) & ~(size_t)3;
-    int ytiles = 0;
-    for (int g = 0; g < G; g++) ytiles += (int)cdiv(r.p->chunk_ends[g + 1] - r.p->chunk_ends[g], 64);
-    // (blocks too small to predict from -- fewer than 65536 samples -- would all take the redo path: the two-kernel route)
-    const bool tile_route = r.pl.vec && wsB % 4 == 0 && wsA % 4 == 0 && packed && !no_fuse && !no_tile && no_medrej && G <= 65535 &&
-                            mrt_scratch_words(G, ccap, ucap) <= wsA && (medrej_fallback || (pl.maxchunk - 1) * (int64_t)T >= 65536) &&
-                            ytiles > 0 && ytiles <= 65535;
-    // K3t never modifies the flags it reads (cur_ft in, alt_ft out, then the two swap), so its first iteration can read
-    // ws.flagsFT where it lies and the copy into ws.bgfFT is not needed.  Only when every rejection iteration is sure to
-    // take that route: the FT-native rejections (k_reject4_t, k_reject4, k_reject) and the rebuild after rows-only
-    // iterations (bgf_ft_stale, K4x) write into cur_ft.  TRI_BG_COPY_FLAGS=1 restores the copy (A/B runs).
-    static const bool copy_flags = [] { const char* e = getenv("TRI_BG_COPY_FLAGS"); return e && e[0] == '1'; }();
-    bool flags_in_place = flagsFT_current && !copy_flags && packed && tile_route;
+    const TileRoute tile = pick_tile_route(r, packed);
+    // K3t never modifies the flags it reads, so its first iteration can read ws.flagsFT where it lies and the copy into
+    // ws.bgfFT is not needed.  Only when every rejection iteration is sure to take that route: the FT-native rejections
+    // (k_reject4_t, k_reject4, k_reject) and the rebuild after rows-only iterations (bgf_ft_stale, K4x) write into cur_ft.
+    // TRI_BG_COPY_FLAGS=1 restores the copy (A/B runs).
+    static const bool copy_flags = is1(getenv("TRI_BG_COPY_FLAGS"));
+    bool flags_in_place = flagsFT_current && !copy_flags && packed && tile.use;
     for (int ext = pl.nit; ext >= 1 && flags_in_place; ext--)
-        if (xl_of((int)box_radius((double)ext * r.p->spike_width_freq)) > 0) flags_in_place = false;
+        if (pick_bg_step(r, packed, tile.use, ext).freq.route == FreqStage::ExactRows) flags_in_place = false;
     int rc = TRI_OK;
     if (!flags_in_place)
         rc = flagsFT_current ? launch_u8<0>(r, ws.flagsFT, ws.bgfFT, N, N, N, W)
                              : launch_transpose<uint8_t>(r, ws.flagsTF, ws.bgfFT, T, Fa, N, N, W);
     if (rc) return rc;
-    if (packed) {
+    if (packed)
         rc = launch_transpose<float>(r, reinterpret_cast<const float*>(flags_in_place ? ws.flagsFT : ws.bgfFT), reinterpret_cast<float*>(ws.bgfTF), Fa, T / 4, N / 4, N / 4, W);
-        if (rc) return rc;
-    } else {
+    else
         rc = launch_u8<0>(r, ws.flagsTF, ws.bgfTF, N, N, N, W);
+    if (rc) return rc;
+
+    BgImages im;
+    im.T = T; im.Fa = Fa; im.W = W;
+    im.dataTF = ws.dataTF; im.dataFT = ws.dataFT;
+    im.flagsTF = ws.bgfTF; im.comb = ws.comb;
+    im.Aw = ws.Aw; im.Ao = ws.Ao; im.wsA = 2 * (size_t)pl.PT * Fa;   // Aw / Ao interleaved per window (carve)
+    im.Bw = ws.Bw; im.Bo = ws.Bo; im.wsB = (size_t)pl.PF * T;
+    im.rows = ws.Ao; im.ws_rows = im.wsA;
+    im.mask = r.ampl_cached ? r.data_mask : nullptr; im.ws_mask = r.data_mask_ws;
+    im.nanflag = reinterpret_cast<uint8_t*>(ws.rowcnt);
+    im.residP = residP; im.xstats = nullptr;
+    BgState st = {flags_in_place ? ws.flagsFT : ws.bgfFT, flags_in_place ? ws.bgfFT : ws.fflFT, false, false};
+    for (int ext = pl.nit; ext >= 0; ext--) {
+        const BgStep s = pick_bg_step(r, packed, tile.use, ext);
+        if (st.bgf_ft_stale && s.reads_ft_flags) {
+            // an iteration that reads the FT flag bytes follows rows-only ones: they are the 32-bit transpose of the TF4 words
+            rc = launch_transpose<float>(r, reinterpret_cast<const float*>(ws.bgfTF), reinterpret_cast<float*>(st.cur_ft), T / 4, Fa, N / 4, N / 4, W);
+            if (rc) return rc;
+            st.bgf_ft_stale = false;
+        }
+        float den_t = 0.0f;
+        rc = bg_time_stage(r, s, im, st, &den_t);
+        if (!rc) rc = bg_freq_stage(r, s, im, st, den_t);
+        if (!rc) rc = bg_reject_stage(r, s, tile, packed, st);
         if (rc) return rc;
     }
-    double rej = TRI_MAD_NORMAL * r.p->background_reject;
-    bool wrote_panel = false;            // the final frequency stage left the residual in residP as well
-    bool bgf_ft_stale = false;           // the FT flag bytes lag behind the TF4 words (rows-only rejection iterations)
-    // K3r (round 4): block median + rejection in ONE pass over |data - background| (kernels_reject.hpp).  It writes the updated FT
-    // flags to a SECOND image (its fallback redoes a block from the input flags), so the FT flag image alternates between
-    // ws.bgfFT and ws.fflFT (free until the frequency-axis SumThreshold writes it).  TRI_FUSED_MEDREJ=1 switches it on.
-    // (opt-in for now, TRI_FUSED_MEDREJ=1: one workgroup per block does not stream fast enough -- 3.7 against 3.0 ms per 252
-    //  windows for the two kernels, scripts/ubench/medrej_dev.hip)
-    // (read in place, ws.flagsFT stays as it is -- the time medians of the residual read it: the first iteration writes
-    //  ws.bgfFT, and from then on ws.bgfFT and ws.fflFT alternate)
-    uint8_t* cur_ft = flags_in_place ? ws.flagsFT : ws.bgfFT;
-    uint8_t* alt_ft = flags_in_place ? ws.bgfFT : ws.fflFT;
-    for (int ext = pl.nit; ext >= 0; ext--) {
-        bool final_pass = ext == 0;
-        double e = (double)(final_pass ? 1 : ext);
-        int r0 = (int)box_radius(e * r.p->spike_width_time);
-        int r1 = (int)box_radius(e * r.p->spike_width_freq);
-        // --- time axis (TF layout: line = time, column = channel) ---
-        // Building the weight / data images first (13 B/sample, vectorised) and
-        // streaming float images through the sequential kernel is faster than
-        // byte loads of the flags inside its per-line loop.
-        static const bool prebuild = [] { const char* e = getenv("TRI_TIME_PREBUILD"); return !(e && e[0] == '0'); }();
-        float den_t = 0.0f, den_f = 0.0f;   // divisions deferred to the transposes / masked_div
-        bool direct_ft = false;
-        // frequency stage able to read the time stage's TF images itself (no transposes)
-        // register-ring fused frequency stage (signed 32-bit buffer offsets: window below 2^31 bytes)
-        const int ksf = ksf_of(r1);
-        // exact row filter (K4x) where the stage pipelines end: rows of the time stage's TF images in, rows out
-        const int xl = xl_of(r1);
-        // ... whose rejection iterations then stay in the row layout altogether (TRI_FILTER_NO_TF_REJECT=1: transposes + FT kernels)
-        static const bool no_tfr = [] { const char* e = getenv("TRI_FILTER_NO_TF_REJECT"); return e && e[0] == '1'; }();
-        const bool tf_native = xl > 0 && !final_pass && packed && !no_tfr && G <= 65535 && (uint64_t)T * Fa * 4u < (1ull << 31);
-        // (who reads the FT bytes: a time stage that cannot take the TF4 words, and the median / rejection of an FT-native
-        //  iteration; the final pass has neither median nor rejection)
-        const bool time_from_tf4 = r0 > 0 && packed && colfilter_lds_block(r0, Fa) > 0;
-        if (bgf_ft_stale && (!time_from_tf4 || (!final_pass && !tf_native))) {
-            // an iteration that reads the FT flag bytes follows rows-only ones: they are the 32-bit transpose of the TF4 words
-            rc = launch_transpose<float>(r, reinterpret_cast<const float*>(ws.bgfTF), reinterpret_cast<float*>(cur_ft), T / 4, Fa, N / 4, N / 4, W);
-            if (rc) return rc;
-            bgf_ft_stale = false;
-        }
-        const bool tin4 = !xl && !ksf && !colfilter_t_usable(r1) && colfilter_t4_usable(r1);
-        const bool tin = xl > 0 || ksf > 0 || colfilter_t_usable(r1) || tin4;
-        float* den_t_ptr = tin ? nullptr : &den_t;
-        // (for the in-place multi-pass kernel, used at large radii, building on
-        //  the fly measured faster: 11.4 vs 16.8 ms per call at 128 windows)
-        if (r0 > 0 && packed && colfilter_lds_block(r0, Fa) > 0) {
-            // single sweep straight from (data, packed flags): no image build
-            rc = launch_colfilter(r, 2, ws.Aw, ws.Ao, ws.dataTF, ws.bgfTF, ws.Aw, ws.Ao, T, Fa, r0, wsA, N, wsA, W, den_t_ptr, false, true);
-            if (rc) return rc;
-        } else if (r0 > 0 && !packed && prebuild && colfilter_lds_block(r0, Fa) > 0) {
-            const bool lds_path = true;
-            const size_t boff = lds_path ? 0 : (size_t)4 * r0 * Fa;
-            if (N % 4 == 0 && wsA % 4 == 0)
-                hipLaunchKernelGGL(k_build_wo4, grid1(N / 4, W), dim3(256), 0, r.st, ws.dataTF, ws.bgfTF, ws.Aw + boff, ws.Ao + boff, N / 4, N, wsA);
-            else
-                hipLaunchKernelGGL(k_build_wo, grid1(N, W), dim3(256), 0, r.st, ws.dataTF, ws.bgfTF, ws.Aw + boff, ws.Ao + boff, N, N, wsA);
-            LAUNCHCHK();
-            // (TRI_FILTER_DIRECT_FT=1: write the filtered images straight into FT
-            //  layout; measured no faster than the two transposes it replaces)
-            static const bool want_direct = [] { const char* e = getenv("TRI_FILTER_DIRECT_FT"); return e && e[0] == '1'; }();
-            direct_ft = lds_path && want_direct && (T % 4 == 0) && (wsB % 4 == 0);
-            if (direct_ft) {
-                size_t off2 = colfilter_lds_block(r1, T) > 0 ? 0 : (size_t)4 * r1 * T;
-                rc = launch_colfilter(r, 1, ws.Aw, ws.Ao, nullptr, nullptr, ws.Bw + off2, ws.Bo + off2, T, Fa, r0, wsA, 0, wsB, W, nullptr, true);
-            } else {
-                rc = launch_colfilter(r, 1, ws.Aw, ws.Ao, nullptr, nullptr, ws.Aw, ws.Ao, T, Fa, r0, wsA, 0, wsA, W, den_t_ptr, false, true);
-            }
-            if (rc) return rc;
-        } else if (r0 > 0) {
-            const uint8_t* fl = ws.bgfTF;
-            if (packed) {   // byte image needed: rebuild it next to the packed one
-                rc = launch_transpose<uint8_t>(r, cur_ft, ws.comb, Fa, T, N, N, W);
-                if (rc) return rc;
-                fl = ws.comb;
-            }
-            rc = launch_colfilter(r, 0, ws.Aw, ws.Ao, ws.dataTF, fl, ws.Aw, ws.Ao, T, Fa, r0, wsA, N, wsA, W);
-            if (rc) return rc;
-        } else {
-            const uint8_t* fl = ws.bgfTF;
-            if (packed) {
-                rc = launch_transpose<uint8_t>(r, cur_ft, ws.comb, Fa, T, N, N, W);
-                if (rc) return rc;
-                fl = ws.comb;
-            }
-            hipLaunchKernelGGL(k_build_wo, grid1(N, W), dim3(256), 0, r.st, ws.dataTF, fl, ws.Aw, ws.Ao, N, N, wsA);
-            LAUNCHCHK();
-        }
-        // --- to FT layout: rows [4 r1, 4 r1 + Fa) of the padded buffers for the
-        //     in-place multi-pass filter, rows [0, Fa) for the single-sweep one ---
-        size_t off = colfilter_lds_block(r1, T) > 0 ? 0 : (size_t)4 * r1 * T;
-        // frequency stage + masked division in one kernel when the four-ring stage applies
-        const bool fused_div = tin && !tin4 && !direct_ft && (xl > 0 || ksf > 0 || colfilter_tf_usable(r1));
-        if (xl > 0 && !direct_ft) {
-            // rows are filtered in place (Ao <- |data - bg| or bg, Aw <- data - bg), then taken to the FT layout
-            const uint8_t* mk = r.ampl_cached ? r.data_mask : nullptr;
-            if (final_pass) {
-                HIPCHK(hipMemsetAsync(ws.rowcnt, 0, (size_t)W * T, r.st));
-                rc = launch_boxx<2>(r, xl, ws.Aw, ws.Ao, ws.dataTF, mk, ws.Ao, ws.Aw, Fa, T, Fa, r1, wsA, N, r.data_mask_ws, wsA, wsA, W,
-                                    reinterpret_cast<uint8_t*>(ws.rowcnt));
-                if (rc) return rc;
-                rc = launch_transpose<float>(r, ws.Aw, ws.Bw, T, Fa, wsA, wsB, W);
-            } else {
-                rc = launch_boxx<1>(r, xl, ws.Aw, ws.Ao, ws.dataTF, mk, ws.Ao, nullptr, Fa, T, Fa, r1, wsA, N, r.data_mask_ws, wsA, 0, W, nullptr);
-                if (rc) return rc;
-                if (tf_native) {
-                    // the rejection where the rows lie: block medians over (all times) x (chunk channels) of the row image
-                    // with the TF4 flag words, rejection straight into those words -- no FT image of the residual or of
-                    // the flags in this iteration (the FT flags are rebuilt when an FT-native iteration follows)
-                    static const bool no_predict = [] { const char* e = getenv("TRI_MEDIAN_NO_PREDICT"); return e && e[0] == '1'; }();
-                    unsigned* gc = reinterpret_cast<unsigned*>(ws.Aw);          // the weight rows are dead: candidate scratch
-                    unsigned cap = (unsigned)(std::min<size_t>((wsA / 2) / (size_t)G, 0x7fffffffu) & ~(size_t)3);
-                    if (no_predict || (int64_t)cap < pl.maxchunk * pl.T || wsA % 4 != 0) { gc = nullptr; cap = 0; }
-                    // (not through launch_median_kernel: a block of rows with TF4 flag words, not row segments)
-                    hipLaunchKernelGGL((k_median2<false, true>), dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Ao,
-                                       (const uint8_t*)ws.bgfTF, ws.med, wsA, N, (size_t)0, (size_t)1, ws.segC_start, ws.segC_len, 1, G,
-                                       gc, gc ? wsA : (size_t)0, cap, T / 4, Fa);
-                    hipLaunchKernelGGL(k_reject_tf, dim3((unsigned)cdiv(Fa, 256), (unsigned)(T / 4), (unsigned)W), dim3(256), 0, r.st,
-                                       (const float*)ws.Ao, reinterpret_cast<unsigned*>(ws.bgfTF), ws.med, ws.d_chunk_of, rej, T / 4, Fa, Fa, G,
-                                       wsA, N / 4);
-                    LAUNCHCHK();
-                    bgf_ft_stale = true;
-                    continue;
-                }
-            }
-            if (rc) return rc;
-            rc = launch_transpose<float>(r, ws.Ao, ws.Bo, T, Fa, wsA, wsB, W);
-            if (rc) return rc;
-        } else if (fused_div) {
-            if (final_pass) {
-                HIPCHK(hipMemsetAsync(ws.rowcnt, 0, (size_t)W * T, r.st));
-                if (ksf) rc = launch_boxf<2>(r, ksf, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, reinterpret_cast<uint8_t*>(ws.rowcnt),
-                                             residP, N, &wrote_panel);
-                else rc = launch_colfilter_tf<2>(r, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, reinterpret_cast<uint8_t*>(ws.rowcnt));
-            } else {
-                if (ksf) rc = launch_boxf<1>(r, ksf, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, nullptr);
-                else rc = launch_colfilter_tf<1>(r, ws.Aw, ws.Ao, ws.Bw, ws.Bo, ws.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, nullptr);
-            }
-            if (rc) return rc;
-        } else if (tin && !direct_ft) {
-            if (tin4) rc = launch_colfilter_t4(r, ws.Aw, ws.Ao, ws.Bw, ws.Bo, Fa, T, Fa, r1, wsA, wsB, W, &den_f);
-            else rc = launch_colfilter_t(r, ws.Aw, ws.Ao, ws.Bw, ws.Bo, Fa, T, Fa, r1, wsA, wsB, W, &den_f);
-            if (rc) return rc;
-        } else if (!direct_ft) {
-            rc = launch_transpose<float>(r, ws.Aw, ws.Bw + off, T, Fa, wsA, wsB, W, den_t);
-            if (rc) return rc;
-            rc = launch_transpose<float>(r, ws.Ao, ws.Bo + off, T, Fa, wsA, wsB, W, den_t);
-            if (rc) return rc;
-        }
-        // --- frequency axis (FT layout: line = channel, column = time) ---
-        if (r1 > 0 && !(tin && !direct_ft)) {
-            rc = launch_colfilter(r, 1, ws.Bw, ws.Bo, nullptr, nullptr, ws.Bw, ws.Bo, Fa, T, r1, wsB, 0, wsB, W, &den_f);
-            if (rc) return rc;
-        }
-        if (final_pass) {
-            // ws.rowcnt (W * T ints, idle until the end of the iteration) doubles as the
-            // per-line "background holds a NaN" marker
-            if (!fused_div) {
-                HIPCHK(hipMemsetAsync(ws.rowcnt, 0, (size_t)W * T, r.st));
-                rc = launch_masked_div<2>(r, ws.Bw, ws.Bo, ws.dataFT, N, wsB, N, W, den_f, reinterpret_cast<uint8_t*>(ws.rowcnt), T);
-                if (rc) return rc;
-            }
-        } else {
-            if (!fused_div) {
-                rc = launch_masked_div<1>(r, ws.Bw, ws.Bo, ws.dataFT, N, wsB, N, W, den_f);
-                if (rc) return rc;
-            }
-            {
-                // K3t: median + rejection + TF4 re-pack in one pass over |data - background|, tile-parallel (kernels_reject_tile.hpp):
-                // predict (per block) -> pass (per 64 x 64-word tile) -> finish (per block) -> redo of the blocks that failed a check.
-                // Scratch: the dead time-stage images of the window.
-                if (tile_route) {
-                    unsigned* sc = reinterpret_cast<unsigned*>(ws.Aw);
-                    hipLaunchKernelGGL(k_mr_predict, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)cur_ft,
-                                       ws.d_chunk_ends, rej, T / 4, G, wsB, N, sc, wsA, ccap, ucap, medrej_fallback);
-                    for (unsigned round = 1; round <= 2; round++) {        // (round 2: only the blocks whose median missed the predicted window)
-                        hipLaunchKernelGGL(k_mr_pass, dim3((unsigned)cdiv(T / 4, 64), (unsigned)ytiles, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo,
-                                           (const uint8_t*)cur_ft, alt_ft, ws.bgfTF, ws.d_chunk_ends, Fa, T / 4, G, wsB, N, sc, wsA, ccap, ucap, round);
-                        hipLaunchKernelGGL(k_mr_finish, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)cur_ft, alt_ft,
-                                           ws.bgfTF, ws.med, ws.d_chunk_ends, rej, Fa, T / 4, G, wsB, N, sc, wsA, ccap, ucap, round);
-                    }
-                    hipLaunchKernelGGL(k_median_reject, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)cur_ft,
-                                       alt_ft, ws.bgfTF, ws.med, ws.d_chunk_ends, rej, Fa, T / 4, G, wsB, N, sc, wsA, 0u, 0u, 1,
-                                       (const unsigned*)sc, wsA, (int)MRT_PARW, 11);
-                    LAUNCHCHK();
-                    std::swap(cur_ft, alt_ft);
-                    if (alt_ft == ws.flagsFT) alt_ft = ws.fflFT;
-                    continue;
-                }
-            }
-            if (flags_in_place) return set_err(TRI_EUNSUPPORTED, "internal: background flags read in place on a route that rewrites them");
-            {
-                // one pass: median + rejection + TF4 re-pack (K3r).  Scratch per (window, chunk) block: the dead time-stage
-                // images, half for the window's keys, half for the undecided samples' indices
-                const size_t per_block = (wsA / (size_t)G) & ~(size_t)7;
-                const unsigned capq = (unsigned)std::min<size_t>(per_block / 2, 0x3ffffffcu);
-                if (r.pl.vec && wsB % 4 == 0 && wsA % 4 == 0 && packed && !no_fuse && !no_medrej && capq >= 1024 && G <= 65535 &&
-                    (uint64_t)N * 4u < (1ull << 32)) {
-                    hipLaunchKernelGGL(k_median_reject, dim3((unsigned)G, (unsigned)W), dim3(256), 0, r.st, (const float*)ws.Bo, (const uint8_t*)cur_ft,
-                                       alt_ft, ws.bgfTF, ws.med, ws.d_chunk_ends, rej, Fa, T / 4, G, wsB, N,
-                                       reinterpret_cast<unsigned*>(ws.Aw), wsA, capq, capq, medrej_fallback);
-                    LAUNCHCHK();
-                    std::swap(cur_ft, alt_ft);
-                    continue;
-                }
-            }
-            // block medians over (all times) x (chunk channels): contiguous in FT
-            // (the time stage's images in ws.Aw / ws.Ao are dead here: candidate scratch, wsA / G keys per block)
-            MedianJob j;
-            j.data = ws.Bo; j.flags = cur_ft; j.med = ws.med; j.WSd = wsB; j.WSf = N;
-            j.seg_start = ws.segB_start; j.seg_len = ws.segB_len; j.R = 1; j.G = G; j.W = W; j.max_len = pl.maxchunk * pl.T;
-            j.vec_ok = T % 4 == 0 && wsB % 4 == 0 && N % 4 == 0;
-            j.gcand = reinterpret_cast<unsigned*>(ws.Aw); j.cand_ws = wsA;
-            j.cand_cap = (unsigned)(std::min<size_t>(wsA / (size_t)G, 0x7fffffffu) & ~(size_t)3);
-            rc = launch_median(r, j);
-            if (rc) return rc;
-            if (r.pl.vec && wsB % 4 == 0 && packed && !no_fuse) {
-                // rejection + TF4 re-pack of the flags in one pass
-                hipLaunchKernelGGL(k_reject4_t, dim3((unsigned)cdiv(T / 4, 64), (unsigned)cdiv(Fa, 64), (unsigned)W), dim3(64, 4), 0, r.st,
-                                   ws.Bo, cur_ft, ws.bgfTF, ws.med, ws.d_chunk_of, rej, Fa, T / 4, G, wsB, N);
-                LAUNCHCHK();
-                continue;
-            }
-            if (r.pl.vec && wsB % 4 == 0)
-                hipLaunchKernelGGL(k_reject4, grid1(N / 4, W), dim3(256), 0, r.st, ws.Bo, cur_ft, ws.med, ws.d_chunk_of, rej, T / 4, G, N / 4, wsB, N);
-            else
-                hipLaunchKernelGGL(k_reject<true>, grid1(N, W), dim3(256), 0, r.st, ws.Bo, cur_ft, ws.med, ws.d_chunk_of, rej, Fa, T, G, wsB, N);
-            LAUNCHCHK();
-            if (packed)
-                rc = launch_transpose<float>(r, reinterpret_cast<const float*>(cur_ft), reinterpret_cast<float*>(ws.bgfTF), Fa, T / 4, N / 4, N / 4, W);
-            else
-                rc = launch_transpose<uint8_t>(r, cur_ft, ws.bgfTF, Fa, T, N, N, W);
-            if (rc) return rc;
-        }
-    }
-    if (wroteP) *wroteP = wrote_panel;
+    if (wroteP) *wroteP = st.wrote_panel;
     // (a repaired line's residual is redone: in the panel image too)
-    return launch_interp(r, ws.Bo, Fa, T, wsB, W, reinterpret_cast<const uint8_t*>(ws.rowcnt), (const float*)ws.dataFT, N, ws.Bw,
-                         wrote_panel ? residP : nullptr, N);
+    return launch_interp(r, ws.Bo, Fa, T, im.wsB, W, reinterpret_cast<const uint8_t*>(ws.rowcnt), (const float*)ws.dataFT, N, ws.Bw,
+                         st.wrote_panel ? residP : nullptr, N);
 }
 
 // One major iteration (_get_flags_impl, flagging.py:745-781) for a batch.
@@ -1790,7 +1788,7 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     int rc;
 
     // flagging.py:756  _average_freq
-    static const bool no_fused_begin = [] { const char* e = getenv("TRI_NO_FUSED_BEGIN"); return e && e[0] == '1'; }();
+    static const bool no_fused_begin = is1(getenv("TRI_NO_FUSED_BEGIN"));
     const bool fused_begin = r.ampl_cached && !no_fused_begin && T % 4 == 0 && Fa % 4 == 0 && N % 4 == 0 &&
                              ((uintptr_t)iter_flags % 4 == 0);
     if (fused_begin) {
@@ -1850,7 +1848,7 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     // flagging.py:954  flags |= spec_flags
     // With whole 16-byte groups along time the FT copy of the flags is updated
     // in place (rows of flagged channels only) instead of being transposed again.
-    static const bool no_ft_or = [] { const char* e = getenv("TRI_NO_FT_SPEC_OR"); return e && e[0] == '1'; }();
+    static const bool no_ft_or = is1(getenv("TRI_NO_FT_SPEC_OR"));
     const bool ft_current = pl.vec && !no_ft_or && T % 16 == 0;
     // ... and when the background works from the FT image alone (packed flags), the TF image is
     // not read before the time flags are OR-ed in: both updates then share one pass.
@@ -1874,9 +1872,9 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     // column kernel's row walk is one linear stream.  Who else touches the two images reads panels too: the frequency-axis MAD
     // (wave medians over row segments: an aligned group of four channels is contiguous either way) and the fused combine /
     // dilate pass.  Only on the route where exactly those kernels run (TRI_ST_NO_PANEL=1: plain rows everywhere).
-    static const bool no_fused_or_p = [] { const char* e = getenv("TRI_NO_FUSED_OR"); return e && e[0] == '1'; }();
-    static const bool no_fdil_p = [] { const char* e = getenv("TRI_NO_FUSED_DILATE"); return e && e[0] == '1'; }();
-    const bool panel_t = !st_no_panel() && defer_tf && !no_fused_or_p && !no_fdil_p && Fa % 64 == 0 && Fa == F &&
+    static const bool no_fused_or = is1(getenv("TRI_NO_FUSED_OR"));
+    static const bool no_fused_dilate = is1(getenv("TRI_NO_FUSED_DILATE"));
+    const bool panel_t = !st_no_panel() && defer_tf && !no_fused_or && !no_fused_dilate && Fa % 64 == 0 && Fa == F &&
                          median_takes_extra_flags(pl.maxchunk + 3) && st_use_fused(pl.swT) && st_use_mask(T, Fa) &&
                          [&] { int64_t e = p->freq_extend; int64_t h = e >= 0 ? e / 2 : -((-e + 1) / 2); return -h == -1 && -h + e == 2; }();
     // The final frequency stage of the background holds every residual value in a register: where it is the register-ring
@@ -1916,7 +1914,6 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
     // MAD per (time, chunk) = contiguous row segments of the TF layout.
     // (the union is read by this MAD only -- the next major iteration rebuilds the TF flags -- so when the chunk medians are
     //  wave medians they take the three sources as they are and no pass writes the union; TRI_NO_FUSED_OR=1: the pass)
-    static const bool no_fused_or = [] { const char* e = getenv("TRI_NO_FUSED_OR"); return e && e[0] == '1'; }();
     MedianJob cj;
     cj.data = residTF; cj.flags = ws.flagsTF; cj.med = ws.med; cj.WSd = cj.WSf = N; cj.RS = (size_t)Fa;
     cj.seg_start = ws.segC_start; cj.seg_len = ws.segC_len; cj.R = T; cj.G = G; cj.W = W; cj.max_len = pl.maxchunk;
@@ -1966,9 +1963,8 @@ int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_fla
         int64_t ef = p->freq_extend;
         int64_t halff = ef >= 0 ? ef / 2 : -((-ef + 1) / 2);
         int flo = (int)-halff, fhi = (int)(-halff + ef);
-        static const bool no_fuse = [] { const char* e = getenv("TRI_NO_FUSED_DILATE"); return e && e[0] == '1'; }();
         HIPCHK(hipMemsetAsync(ws.rowcnt, 0, (size_t)W * T * sizeof(int), r.st));
-        if (pl.vec && flo == -1 && fhi == 2 && !no_fuse) {
+        if (pl.vec && flo == -1 && fhi == 2 && !no_fused_dilate) {
             // both smearings in one pass, no intermediate image
             dim3 grid((unsigned)cdiv(F / 16, 64), (unsigned)T, (unsigned)W);
             if (panel_t) hipLaunchKernelGGL(k_combine_dilate16<true>, grid, dim3(64), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.dil, ws.rowcnt, T, F / 16, lo, hi);
@@ -2048,7 +2044,7 @@ int process_windows(Run& r, const void* vis, int vis_dtype, const uint8_t* flags
         if (rc) return rc;
         // without channel averaging |vis| is the same in every major iteration:
         // compute it once, in both layouts (TRI_NO_AMPL_CACHE=1 recomputes it per iteration)
-        static const bool no_cache = [] { const char* e = getenv("TRI_NO_AMPL_CACHE"); return e && e[0] == '1'; }();
+        static const bool no_cache = is1(getenv("TRI_NO_AMPL_CACHE"));
         r.ampl_cached = r.pl.vec && !no_cache && p->num_major_iterations > 0;
         if (r.ampl_cached) {
             const size_t n4 = (size_t)r.Wb * NF / 4;
@@ -2535,7 +2531,7 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     if (variant == 0 && can_fuse) variant = st_use_mask(L, C) ? ((C % 64 == 0 && !st_no_panel()) ? 5 : 3) : 2;
     if (variant == 4) {
         if (sw.nw > 8 || stp_lds_bytes(sw) > 160 * 1024) return set_err(TRI_EUNSUPPORTED, "stage pipeline: more than eight windows, or the flag ring does not fit LDS");
-        HIPCHK(st_pipe_optin());
+        HIPCHK(lds_optin_all(160 * 1024, &k_colst_pipe));
     }
     DevBuf<double> ring;
     DevBuf<uint8_t> acc;
@@ -2631,6 +2627,25 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
         g_boxq_b8_override = variant == 5 ? 0 : -1;
     }
     int rc = TRI_OK;
+    // The stage as one step of the background loop on the hook's images: stage 0 the single sweep from packed flags into
+    // (out_w, out_o), stage 1 the frequency stage of a non-final iteration from the TF images in flags4 (n_win, 2, n_line,
+    // n_col: weight, weight * data) into (out_w, out_o)
+    BgStep s = {};
+    s.r0 = s.r1 = (int)radius;
+    s.time = TimeStage::PackedSweep;
+    BgImages im = {};
+    im.T = (int)n_line; im.Fa = (int)n_col; im.W = n_win;
+    BgState bst = {};
+    if (stage == 0) {
+        im.dataTF = data; im.flagsTF = flags4;
+        im.Aw = out_w; im.Ao = out_o; im.wsA = N;
+    } else if (stage == 1) {
+        im.Aw = const_cast<float*>(reinterpret_cast<const float*>(flags4));   // (read only in a non-final iteration)
+        im.Ao = im.Aw + N; im.wsA = 2 * N;
+        im.Bw = out_w; im.Bo = out_o; im.wsB = N;
+        im.dataFT = data;
+        s.freq = pick_freq_stage((int)radius, (int)n_col, (int)n_line, N, false);
+    }
     // stage 1, variant 4: K4x works on rows -- the amplitudes are taken to the TF layout once (untimed), the rows it
     // writes go back to FT inside the timed loop (as in the flagger); out_w doubles as the row buffer.
     // ms_per_launch then covers kernel + transpose; the counters in stats[] are printed with TRI_BOXX_STATS=1
@@ -2639,7 +2654,7 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     int xl = 0;
     if (stage == 1 && variant == 4) {
         g_boxx_override = 1;
-        xl = boxx_pick_l((int)radius, (int)n_col);
+        xl = boxx_pick_l((int)radius, (int)n_col);      // (forced: at any radius, not only where the flagger takes it)
         g_boxx_override = -1;
         if (!xl) return set_err(TRI_EUNSUPPORTED, "no exact row filter for radius %d on lines of %d", (int)radius, (int)n_col);
         HIPCHK(x_data_tf.alloc((size_t)n_win * N));
@@ -2647,40 +2662,22 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
         HIPCHK(hipMemsetAsync(x_stats.get(), 0, 2 * sizeof(unsigned long long), r.st));
         rc = launch_transpose<float>(r, data, x_data_tf.get(), (int)n_col, (int)n_line, N, N, n_win);
         if (rc) return rc;
+        s.freq = {FreqStage::ExactRows, 0, xl, 0};
+        im.dataTF = x_data_tf.get(); im.rows = out_w; im.ws_rows = N; im.xstats = x_stats.get();
     }
+    if (stage == 1 && s.freq.route == FreqStage::Transposed)
+        return set_err(TRI_EUNSUPPORTED, "no single-sweep frequency stage for radius %d", (int)radius);
     HIPCHK(hipEventRecord(e0.get(), r.st));
     for (int i = 0; i < repeats && rc == TRI_OK; i++) {
-        if (xl) {
-            const float* srcW = reinterpret_cast<const float*>(flags4);
-            rc = launch_boxx<1>(r, xl, srcW, srcW + N, x_data_tf.get(), nullptr, out_w, nullptr, (int)n_col, (int)n_line, (int)n_col, (int)radius,
-                                2 * N, N, 0, N, 0, n_win, nullptr, x_stats.get());
-            if (rc == TRI_OK) rc = launch_transpose<float>(r, out_w, out_o, (int)n_line, (int)n_col, N, N, n_win);
-        } else if (stage == 2) {
+        if (stage == 2) {
             // spectrum path: byte flags [n_line][n_col] + data -> filtered weight and data images
             if (variant >= 2 && boxp_pick_block((int)radius, (int)n_col) == 0) rc = set_err(TRI_EUNSUPPORTED, "no stage pipeline for this shape");
-            else rc = launch_colfilter(r, 0, out_w, out_o, data, flags4, out_w, out_o, (int)n_line, (int)n_col, (int)radius, 0, 0, 0, 1, nullptr, false, true);
+            else rc = launch_colfilter(r, ColSrc::ByteFlags, out_w, out_o, data, flags4, out_w, out_o, (int)n_line, (int)n_col, (int)radius, 0, 0, 0, 1, COL_WEIGHTS_01);
         } else if (stage == 0) {
-            rc = launch_colfilter(r, 2, out_w, out_o, data, flags4, out_w, out_o, (int)n_line, (int)n_col, (int)radius, N, N, N,
-                                  n_win, nullptr, false, true);
+            float den_t;
+            rc = bg_time_stage(r, s, im, bst, &den_t);
         } else {
-            // frequency-axis stage + masked division from TF images (line = time row, n_col positions):
-            // the flagger's route for this radius (fused register / LDS ring kernel, or lane-per-stage
-            // filter followed by the division kernel)
-            const float* srcW = reinterpret_cast<const float*>(flags4);   // (n_win, 2, n_line, n_col): weight, weight * data
-            const float* srcO = srcW + N;
-            const int T = (int)n_line, Fa = (int)n_col, rad = (int)radius;
-            const int ksf = boxr_pick_ks_f(rad);
-            if (ksf > 0) {
-                rc = launch_boxf<1>(r, ksf, srcW, srcO, out_w, out_o, data, Fa, T, Fa, rad, 2 * N, N, N, n_win, nullptr);
-            } else if (colfilter_tf_usable(rad)) {
-                rc = launch_colfilter_tf<1>(r, srcW, srcO, out_w, out_o, data, Fa, T, Fa, rad, 2 * N, N, N, n_win, nullptr);
-            } else if (colfilter_t4_usable(rad)) {
-                float den_f = 0.0f;
-                rc = launch_colfilter_t4(r, srcW, srcO, out_w, out_o, Fa, T, Fa, rad, 2 * N, N, n_win, &den_f);
-                if (rc == TRI_OK) rc = launch_masked_div<1>(r, out_w, out_o, data, N, N, N, n_win, den_f);
-            } else {
-                rc = set_err(TRI_EUNSUPPORTED, "no single-sweep frequency stage for radius %d", rad);
-            }
+            rc = bg_freq_stage(r, s, im, bst, 0.0f);
         }
     }
     if (rc) return rc;
@@ -3041,7 +3038,7 @@ extern "C" int tri_uvcontsub_flagger(const void* vis_c64, const uint8_t* flags, 
             hipLaunchKernelGGL(k_uv_mean, dim3((unsigned)cdiv(F, 256), (unsigned)B), dim3(256), 0, st, v, rf, avg, T, F);
             hipLaunchKernelGGL(k_uv_lowpass, dim3((unsigned)B), dim3(256), 0, st, avg, smooth, F, K);
             // |vis - smooth|, the median flags and (in the same pass) the number of flagged samples per product
-            static const bool uv_scalar = [] { const char* e = getenv("TRI_UV_SCALAR"); return e && e[0] == '1'; }();   // (A/B, tests)
+            static const bool uv_scalar = is1(getenv("TRI_UV_SCALAR"));   // (A/B, tests)
             if (!uv_scalar && F % 4 == 0 && ((uintptr_t)v % 16 == 0) && ((uintptr_t)rf % 4 == 0) && ((uintptr_t)smooth % 16 == 0) &&
                 ((uintptr_t)absres % 16 == 0) && ((uintptr_t)mflags % 4 == 0))
                 hipLaunchKernelGGL(k_uv_resid4, dim3((unsigned)cdiv((int64_t)N, 2048), (unsigned)B), dim3(256), 0, st, v, rf, smooth, absres, mflags, cnt, T, F);
