@@ -325,6 +325,43 @@ int tri_scale_invariant_rank(const uint8_t *flags, uint8_t *out_flags,
                              void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The SIR operator with a mask of missing samples and a penalty (after
+ * AOFlagger's masked SIR operator; the definition is this project's own).
+ * `missing` has the shape of `flags` (nonzero = missing: absent cells of the
+ * window grid, dead samples, statically masked bands -- flags that are no
+ * detections).  For one line f[0..n), m[0..n), 0 <= eta < 1 and a finite
+ * penalty >= 0, with integer prefix counts for i = 0..n
+ *   M(i)   = number of missing samples in [0, i),  P(i) = i - M(i)
+ *   U(i)   = number of present and unflagged samples in [0, i)
+ *   W(i)   = (eta * (double)P(i) - (double)U(i)) - penalty * (double)M(i)
+ *            (four IEEE operations in that order, no FMA)
+ *   out[x] = max_{x < j <= n} W(j) >= min_{0 <= k <= x} W(k)   for a present x
+ *   out[x] = f[x] != 0                                         for a missing x
+ * i.e. a present x is flagged iff some interval containing it holds at most
+ * eta * (its present samples) - penalty * (its missing samples) present and
+ * unflagged samples: a missing sample counts neither as RFI nor as clean
+ * data, crossing it costs `penalty`, and it is never flagged or unflagged.
+ * Per window
+ *   out_flags = f | SIRm_time(f, m, eta_time) | SIRm_freq(f, m, eta_freq)
+ * where both axes read the INPUT masks and eta = 0 skips an axis.  With m all
+ * zero the result is tri_scale_invariant_rank's bit for bit; with penalty = 0
+ * it is, on the present samples, that of the line with the missing samples
+ * deleted; it shrinks as the penalty grows and always contains f.
+ * out_flags receives 0/1 and must overlap neither flags nor missing.
+ * TRI_EINVAL for NULL pointers, negative shapes, eta NaN or outside [0, 1), a
+ * penalty that is NaN, infinite or negative, and overlapping buffers;
+ * TRI_EWORKSPACE when workspace_bytes < tri_sir_masked_workspace_bytes() (0
+ * unless ntime > 1024 or nchan > 65536; larger than the unmasked workspace:
+ * two counts per line segment).  Empty shapes return TRI_OK without a launch.
+ */
+size_t tri_sir_masked_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan);
+int tri_scale_invariant_rank_masked(const uint8_t *flags, const uint8_t *missing,
+                                    uint8_t *out_flags,
+                                    int64_t n_win, int64_t ntime, int64_t nchan,
+                                    double eta_time, double eta_freq, double penalty,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Line-RMS statistics of (n_win, ntime, nchan) windows and the thresholding
  * of whole timesteps and whole channels on them (beyond the reference; the
  * model is AOFlagger's threshold_timestep_rms / threshold_channel_rms, the

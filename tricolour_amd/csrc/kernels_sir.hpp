@@ -18,6 +18,15 @@
 // A line longer than one block's span (S * 16 * K samples) is cut into segments along blockIdx.y and run in three
 // launches of the same kernel: SIR_COUNT writes each segment's unflagged count, SIR_MINMAX each segment's W minimum
 // and maximum (its U offset summed from the counts), SIR_FINAL folds the other segments' aggregates into the carries.
+//
+// MISSING: the masked operator.  A second mask m[0..n) (nonzero = missing) and a finite penalty >= 0:
+//   M(i) = missing samples in [0, i),  P(i) = i - M(i),  U(i) = present and unflagged samples in [0, i)   (integers)
+//   W(i) = (eta * (double)P(i) - (double)U(i)) - penalty * (double)M(i)       (four IEEE operations in that order)
+//   out[x] = present x: max_{x < j <= n} W(j) >= min_{0 <= k <= x} W(k);  missing x: f[x] != 0
+// Same decomposition: the column scan carries U and M as the two halves of one 64-bit count (so do the segment
+// counts of long lines), a second 16-bit mask per sub-chunk holds the missing samples.  With m all zero W is the
+// unmasked W (x - 0.0 == x), so the result is the unmasked operator's bit for bit.  All of it sits behind
+// `if constexpr (MISSING)`: the unmasked instantiations compile to what they were without it.
 #pragma once
 
 #define SIR_FULL 0     // the block spans the whole line
@@ -35,6 +44,17 @@ __device__ __forceinline__ unsigned sir_mask16(uint4 v) {
 }
 // 4-bit mask -> four 0/1 bytes
 __device__ __forceinline__ unsigned sir_bytes4(unsigned m) { return ((m & 0xFu) * 0x00204081u) & 0x01010101u; }
+
+// count carried through the column scan: U, or with a missing mask U (low word) and M (high word) in one add
+template <bool MISSING> struct sir_count { typedef int type; };
+template <> struct sir_count<true> { typedef unsigned long long type; };
+
+// W(i) from the integer prefix counts: u = U(i), mc = M(i) (MISSING only)
+template <bool MISSING>
+__device__ __forceinline__ double sir_w(double eta, double penalty, int i, int u, int mc) {
+    if constexpr (MISSING) return (eta * (double)(i - mc) - (double)u) - penalty * (double)mc;
+    else return eta * (double)i - (double)u;
+}
 
 // Exclusive scan of v over the S = NT / CB threads of one column (tid % CB) in thread order (REV: from the last
 // thread down), with `total` the column's full reduction.  sh: NT / 64 * CB entries, used by this call alone.
@@ -66,15 +86,19 @@ __device__ __forceinline__ T sir_col_scan(T v, T ident, Op op, T* sh, T& total) 
 // NT threads, CB lines per block, K sub-chunks of 16 samples per thread.
 // TIME: line L = (window, channel), sample x at L's window base + x * nchan + channel; else line L = (window, time
 // row), sample x at L * nchan + x.  VEC (frequency only, nchan % 16 == 0 and a 16-byte aligned base): uint4 loads and
-// stores.  OR: out |= result (the second axis of a two-axis call) instead of out = result.
-template <int NT, int CB, int K, int PHASE, bool TIME, bool VEC, bool OR>
+// stores.  OR: out |= result (the second axis of a two-axis call) instead of out = result.  MISSING: `miss` (laid
+// out as `in`) and `penalty` are read, ws_cnt holds one 64-bit (U, M) count per (line, segment); neither is touched
+// otherwise.
+template <int NT, int CB, int K, int PHASE, bool TIME, bool VEC, bool OR, bool MISSING = false>
 __global__ void __launch_bounds__(NT)
 k_sir(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t nlines, int64_t ntime, int64_t nchan,
-      double eta, int nseg, int* __restrict__ ws_cnt, double* __restrict__ ws_mn, double* __restrict__ ws_mx) {
+      double eta, int nseg, int* __restrict__ ws_cnt, double* __restrict__ ws_mn, double* __restrict__ ws_mx,
+      const uint8_t* __restrict__ miss, double penalty) {
     static_assert(!(TIME && VEC), "time lines are strided");
     constexpr int S = NT / CB;
     constexpr int SPAN = S * 16 * K;
-    __shared__ int sh_cnt[NT / 64 * CB];
+    typedef typename sir_count<MISSING>::type cnt_t;
+    __shared__ cnt_t sh_cnt[NT / 64 * CB];
     __shared__ double sh_mn[NT / 64 * CB];
     __shared__ double sh_mx[NT / 64 * CB];
 
@@ -88,7 +112,9 @@ k_sir(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t nlines,
     const int x0 = seg * SPAN + s * 16 * K;
 
     // ---- load: 16-bit flag masks, nothing set at or past n
+    // (MISSING: m = flagged or missing, i.e. not counted in U; mm = missing, and in its high half flagged and missing)
     unsigned m[K];
+    unsigned mm[MISSING ? K : 1];
     int nv[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
@@ -102,34 +128,55 @@ k_sir(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t nlines,
             for (int i = 0; i < 16; i++)
                 if (i < nv[k] && in[base + (int64_t)(xs + i) * ss]) m[k] |= 1u << i;
         }
-    }
-    int mine = 0;
+        if constexpr (MISSING) {
+            unsigned q = 0;
+            if (VEC) {
+                if (nv[k] > 0) q = sir_mask16(*reinterpret_cast<const uint4*>(miss + base + xs));
+            } else {
 #pragma unroll
-    for (int k = 0; k < K; k++) mine += nv[k] - __popc(m[k]);
-
-    // ---- U at the thread's first sample, U(n)
-    int col_total;
-    int u0 = sir_col_scan<NT, CB, false>(mine, 0, [](int a, int b) { return a + b; }, sh_cnt, col_total);
-    if (PHASE == SIR_COUNT) {
-        if (active && s == 0) ws_cnt[L * nseg + seg] = col_total;
-        return;
-    }
-    int useg = 0, uall = col_total;
-    if (PHASE != SIR_FULL && active) {
-        uall = 0;
-        for (int g = 0; g < nseg; g++) {
-            int t = ws_cnt[L * nseg + g];
-            if (g < seg) useg += t;
-            uall += t;
+                for (int i = 0; i < 16; i++)
+                    if (i < nv[k] && miss[base + (int64_t)(xs + i) * ss]) q |= 1u << i;
+            }
+            mm[k] = q | (m[k] & q) << 16;
+            m[k] |= q;
         }
     }
-    u0 += useg;
+    cnt_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        mine += nv[k] - __popc(m[k]);
+        if constexpr (MISSING) mine += (cnt_t)__popc(mm[k] & 0xFFFFu) << 32;
+    }
+
+    // ---- U (and M) at the thread's first sample, U(n) (and M(n))
+    cnt_t col_total;
+    cnt_t c0 = sir_col_scan<NT, CB, false>(mine, (cnt_t)0, [](cnt_t a, cnt_t b) { return a + b; }, sh_cnt, col_total);
+    cnt_t* __restrict__ ws_c = reinterpret_cast<cnt_t*>(ws_cnt);
+    if (PHASE == SIR_COUNT) {
+        if (active && s == 0) ws_c[L * nseg + seg] = col_total;
+        return;
+    }
+    cnt_t cseg = 0, call = col_total;
+    if (PHASE != SIR_FULL && active) {
+        call = 0;
+        for (int g = 0; g < nseg; g++) {
+            cnt_t t = ws_c[L * nseg + g];
+            if (g < seg) cseg += t;
+            call += t;
+        }
+    }
+    c0 += cseg;
+    int u0 = (int)c0, uall = (int)call, m0 = 0, mall = 0;
+    if constexpr (MISSING) {
+        u0 = (int)(c0 & 0xFFFFFFFFu), uall = (int)(call & 0xFFFFFFFFu);
+        m0 = (int)(c0 >> 32), mall = (int)(call >> 32);
+    }
 
     // ---- W minimum / maximum: the thread's minimum, each sub-chunk's maximum (the backward sweeps need those)
     double mx[K];
     double tmn = INFINITY, tmx = -INFINITY;
     {
-        int u = u0;
+        int u = u0, mc = m0;
 #pragma unroll
         for (int k = 0; k < K; k++) {
             const int xs = x0 + 16 * k;
@@ -137,10 +184,11 @@ k_sir(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t nlines,
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 if (i < nv[k]) {
-                    double w = eta * (double)(xs + i) - (double)u;
+                    double w = sir_w<MISSING>(eta, penalty, xs + i, u, mc);
                     tmn = fmin(tmn, w);
                     mx[k] = fmax(mx[k], w);
                     u += (m[k] >> i & 1u) ? 0 : 1;
+                    if constexpr (MISSING) mc += mm[k] >> i & 1u;
                 }
             }
             tmx = fmax(tmx, mx[k]);
@@ -157,7 +205,7 @@ k_sir(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t nlines,
         return;
     }
     if (!active) return;                    // no barrier follows
-    scar = fmax(scar, eta * (double)n - (double)uall);      // W(n)
+    scar = fmax(scar, sir_w<MISSING>(eta, penalty, n, uall, mall));      // W(n)
     if (PHASE == SIR_FINAL) {
         for (int g = 0; g < nseg; g++) {
             if (g < seg) pcar = fmin(pcar, ws_mn[L * nseg + g]);
@@ -169,7 +217,7 @@ k_sir(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t nlines,
 
     // ---- per sub-chunk: forward sweep -> min W(k <= x), backward sweep carrying max W(j > x)
     unsigned r[K];
-    int u = u0;
+    int u = u0, mc = m0;
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const int xs = x0 + 16 * k;
@@ -177,22 +225,25 @@ k_sir(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t nlines,
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             if (i < nv[k]) {
-                pcar = fmin(pcar, eta * (double)(xs + i) - (double)u);
+                pcar = fmin(pcar, sir_w<MISSING>(eta, penalty, xs + i, u, mc));
                 u += (m[k] >> i & 1u) ? 0 : 1;
+                if constexpr (MISSING) mc += mm[k] >> i & 1u;
             }
             P[i] = pcar;
         }
         double sc = k + 1 < K ? fmax(scar, mx[k + 1 < K ? k + 1 : k]) : scar;   // max W(j), j past the sub-chunk
-        int ub = u;                          // U(xs + nv)
+        int ub = u, mb = mc;                 // U(xs + nv), M(xs + nv)
         unsigned bits = 0;
 #pragma unroll
         for (int i = 15; i >= 0; i--) {
             if (i < nv[k]) {
                 if (sc >= P[i]) bits |= 1u << i;
                 ub -= (m[k] >> i & 1u) ? 0 : 1;
-                sc = fmax(sc, eta * (double)(xs + i) - (double)ub);
+                if constexpr (MISSING) mb -= mm[k] >> i & 1u;
+                sc = fmax(sc, sir_w<MISSING>(eta, penalty, xs + i, ub, mb));
             }
         }
+        if constexpr (MISSING) bits = (bits & ~mm[k]) | mm[k] >> 16;    // a missing sample keeps its flag
         r[k] = bits;
     }
 

@@ -682,6 +682,61 @@ def uvcontsub_flagger(vis, flags, major_cycles=5, or_original_from_cycle=1,
     return _like_flags(torch, out, flags, from_numpy)
 
 
+def _sir(flags, missing, eta_time, eta_freq, penalty):
+    """Both SIR calls: argument checks before any device work, then the library call (``missing is None``: the
+    unmasked entry point), in window batches when the workspace does not fit the budget."""
+    shape = tuple(flags.shape)
+    if len(shape) != 4:
+        raise ValueError("flags must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    if missing is not None and tuple(missing.shape) != shape:
+        raise ValueError("flags and missing must have the same shape, got %s and %s" % (shape, tuple(missing.shape)))
+    eta_time, eta_freq = float(eta_time), float(eta_freq)
+    for name, eta in (("eta_time", eta_time), ("eta_freq", eta_freq)):
+        if not 0.0 <= eta < 1.0:              # also rejects NaN
+            raise ValueError("%s must lie in [0, 1), got %r" % (name, eta))
+    if missing is not None:
+        penalty = float(penalty)
+        if not 0.0 <= penalty < float("inf"):     # also rejects NaN
+            raise ValueError("penalty must be finite and >= 0, got %r" % (penalty,))
+    torch = _require_gpu()
+    from_numpy = isinstance(flags, np.ndarray)
+    device = flags.device if (torch.is_tensor(flags) and flags.is_cuda) else \
+        torch.device("cuda", torch.cuda.current_device())
+    f8 = _flags_u8(torch, flags, device)
+    m8 = _flags_u8(torch, missing, device) if missing is not None else None
+    nbl, ncorr, ntime, nchan = (int(s) for s in shape)
+    n_win = nbl * ncorr
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    ws_bytes = lib.tri_sir_workspace_bytes if m8 is None else lib.tri_sir_masked_workspace_bytes
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            # the workspace holds per-segment aggregates of lines longer than one workgroup; batch the windows
+            # when even that does not fit
+            batch = n_win
+            nbytes = ws_bytes(batch, ntime, nchan)
+            if nbytes > 0:
+                budget = _workspace_budget(torch, device)
+                while batch > 1 and ws_bytes(batch, ntime, nchan) > budget:
+                    batch = (batch + 1) // 2
+                nbytes = ws_bytes(batch, ntime, nchan)
+            ws = _workspace(torch, device, nbytes) if nbytes > 0 else None
+            wsp, wsn = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                if m8 is None:
+                    _lib.check(lib.tri_scale_invariant_rank(
+                        f8.data_ptr() + w0 * per, out.data_ptr() + w0 * per, b, ntime, nchan,
+                        eta_time, eta_freq, wsp, wsn, stream))
+                else:
+                    _lib.check(lib.tri_scale_invariant_rank_masked(
+                        f8.data_ptr() + w0 * per, m8.data_ptr() + w0 * per, out.data_ptr() + w0 * per, b, ntime, nchan,
+                        eta_time, eta_freq, penalty, wsp, wsn, stream))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
 def scale_invariant_rank_operator(flags, eta_time=0.2, eta_freq=0.2):
     """Scale-invariant rank operator (Offringa, van de Gronde & Roerdink 2012,
     A&A 539, A95) on (bl, corr, time, chan) flags: a sample becomes flagged
@@ -690,43 +745,26 @@ def scale_invariant_rank_operator(flags, eta_time=0.2, eta_freq=0.2):
     read the input mask: ``out = f | SIR_time(f) | SIR_freq(f)``; ``eta = 0``
     leaves an axis out.  Returns a new array in the container / dtype of
     ``flags``; the input is not modified."""
-    shape = tuple(flags.shape)
-    if len(shape) != 4:
-        raise ValueError("flags must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
-    eta_time, eta_freq = float(eta_time), float(eta_freq)
-    for name, eta in (("eta_time", eta_time), ("eta_freq", eta_freq)):
-        if not 0.0 <= eta < 1.0:              # also rejects NaN
-            raise ValueError("%s must lie in [0, 1), got %r" % (name, eta))
-    torch = _require_gpu()
-    from_numpy = isinstance(flags, np.ndarray)
-    device = flags.device if (torch.is_tensor(flags) and flags.is_cuda) else \
-        torch.device("cuda", torch.cuda.current_device())
-    f8 = _flags_u8(torch, flags, device)
-    nbl, ncorr, ntime, nchan = (int(s) for s in shape)
-    n_win = nbl * ncorr
-    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
-    lib = _lib.lib()
-    with torch.cuda.device(device):
-        if out.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            # the workspace holds per-segment aggregates of lines longer than one workgroup; batch the windows
-            # when even that does not fit
-            batch = n_win
-            nbytes = lib.tri_sir_workspace_bytes(batch, ntime, nchan)
-            if nbytes > 0:
-                budget = _workspace_budget(torch, device)
-                while batch > 1 and lib.tri_sir_workspace_bytes(batch, ntime, nchan) > budget:
-                    batch = (batch + 1) // 2
-                nbytes = lib.tri_sir_workspace_bytes(batch, ntime, nchan)
-            ws = _workspace(torch, device, nbytes) if nbytes > 0 else None
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_scale_invariant_rank(
-                    f8.data_ptr() + w0 * per, out.data_ptr() + w0 * per, b, ntime, nchan,
-                    eta_time, eta_freq, ws.data_ptr() if ws is not None else None,
-                    ws.numel() if ws is not None else 0, stream))
-    return _like_flags(torch, out, flags, from_numpy)
+    return _sir(flags, None, eta_time, eta_freq, 0.0)
+
+
+def scale_invariant_rank_operator_masked(flags, missing, eta_time=0.2, eta_freq=0.2, penalty=0.1):
+    """:func:`scale_invariant_rank_operator` with a mask of missing samples
+    (``missing``, shape of ``flags``, nonzero = missing): samples that are
+    flagged without being detections -- absent cells of the window grid, dead
+    samples, statically masked bands.  A present sample becomes flagged when
+    some interval that contains it holds at most ``eta * (its present samples)
+    - penalty * (its missing samples)`` present, unflagged samples: missing
+    samples count neither as RFI nor as clean data, and crossing each costs
+    ``penalty`` (0: flags on either side of a gap join freely; large: a gap is
+    a wall).  A missing sample keeps its flag as it is.  ``out = f |
+    SIRm_time(f, m) | SIRm_freq(f, m)``, both axes from the inputs; with no
+    sample missing the result is :func:`scale_invariant_rank_operator`'s bit
+    for bit.  Definition: ``include/tricolour_amd.h``.  Returns a new array in
+    the container / dtype of ``flags``; the inputs are not modified."""
+    if missing is None:
+        raise ValueError("missing must be an array of the shape of flags")
+    return _sir(flags, missing, eta_time, eta_freq, penalty)
 
 
 def _line_rms_inputs(name, vis, flags):

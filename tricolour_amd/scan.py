@@ -27,7 +27,8 @@ _tls = threading.local()
 VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with_input_flags", "unflag",
                "flag_nans_zeros", "apply_static_mask",          # strat_executor.py:36-83
                "scale_invariant_rank_operator",                 # beyond the reference: flagging.scale_invariant_rank_operator
-               "threshold_line_rms")                            # beyond the reference: flagging.threshold_line_rms
+               "threshold_line_rms",                            # beyond the reference: flagging.threshold_line_rms
+               "mark_missing")                                  # beyond the reference: the missing mask of masked SIR steps
 
 
 # ---------------------------------------------------------------------------
@@ -98,7 +99,11 @@ def load_strategies(path):
 
 def check_strategies(strategies):
     """Raises the reference's errors for a strategy without a task or with an
-    unknown one (strat_executor.py:33-36, 82-83) before any work is done."""
+    unknown one (strat_executor.py:33-36, 82-83) before any work is done, and
+    a ``ValueError`` for a ``scale_invariant_rank_operator`` step whose
+    ``missing`` is not ``none`` / ``input`` / ``marked`` or is ``marked`` with
+    no ``mark_missing`` step before it."""
+    marked = False
     for strategy in strategies:
         try:
             task = strategy['task']
@@ -106,6 +111,14 @@ def check_strategies(strategies):
             raise ValueError("strategy has no 'task': %s" % strategy)
         if task not in VALID_TASKS:
             raise ValueError("Task '%s' does not name a valid task", task)
+        if task == "mark_missing":
+            marked = True
+        elif task == "scale_invariant_rank_operator":
+            which = (strategy.get('kwargs') or {}).get("missing", "none")
+            if which not in ("none", "input", "marked"):
+                raise ValueError("scale_invariant_rank_operator: missing must be 'none', 'input' or 'marked', got %r" % (which,))
+            if which == "marked" and not marked:
+                raise ValueError("scale_invariant_rank_operator: missing 'marked' needs an earlier mark_missing")
 
 
 def select_scans(scan_numbers, available):

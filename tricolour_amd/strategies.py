@@ -13,6 +13,7 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
     import torch
     original = flag_windows.clone() if torch.is_tensor(flag_windows) else flag_windows.copy()
     lor = torch.logical_or if torch.is_tensor(flag_windows) else (lambda a, b: a | b)
+    marked = None                 # the last mark_missing snapshot
     for strategy in strategies:
         try:
             task = strategy['task']
@@ -34,8 +35,22 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
             flag_windows = flag_windows * 0 if not torch.is_tensor(flag_windows) else torch.zeros_like(flag_windows)
         elif task == "flag_nans_zeros":
             flag_windows = flagging.flag_nans_and_zeros(vis_windows, flag_windows)   # :63
+        elif task == "mark_missing":
+            # what is flagged by now is missing data, not a detection: the mask of later masked SIR steps
+            marked = flag_windows.clone() if torch.is_tensor(flag_windows) else flag_windows.copy()
         elif task == "scale_invariant_rank_operator":
-            new_flags = flagging.scale_invariant_rank_operator(flag_windows, **kw)
+            kw = dict(kw)
+            which = kw.pop("missing", "none")
+            penalty = kw.pop("missing_penalty", 0.1)
+            if which == "none":
+                new_flags = flagging.scale_invariant_rank_operator(flag_windows, **kw)
+            elif which in ("input", "marked"):
+                if which == "marked" and marked is None:
+                    raise ValueError("scale_invariant_rank_operator: missing 'marked' needs an earlier mark_missing")
+                new_flags = flagging.scale_invariant_rank_operator_masked(
+                    flag_windows, original if which == "input" else marked, penalty=penalty, **kw)
+            else:
+                raise ValueError("scale_invariant_rank_operator: missing must be 'none', 'input' or 'marked', got %r" % (which,))
             flag_windows = lor(new_flags, flag_windows)
         elif task == "threshold_line_rms":
             new_flags = flagging.threshold_line_rms(vis_windows, flag_windows, **kw)
