@@ -273,7 +273,8 @@ int tri_flag_nans_and_zeros(const void *vis, int vis_dtype, const uint8_t *flags
  * one call per mask) and flag_autos (flagging.py:90-93): out = flags, then on
  * every baseline with bl_sel[bl] != 0 either out |= chan_mask (mode 0, "or")
  * or out = chan_mask (mode 1, "override"), broadcast over corr and time.
- * flags / out: (nbl, ncorr, ntime, nchan) uint8; may alias.  The channel mask
+ * flags / out: (nbl, ncorr, ntime, nchan) uint8; may alias.  Any nbl and
+ * ncorr * ntime: the call launches slabs of 65535 x 65535.  The channel mask
  * and the baseline selection (uv-range test on antenna positions) are
  * computed on the host exactly as flagging.py:131-160 does.
  */

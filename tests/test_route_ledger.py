@@ -17,10 +17,22 @@ Row of SWITCHES
              launched under env whatever base does.
 A kernel-name fragment without '<' names a kernel whatever its template arguments ("k_reject4" is not "k_reject4_t");
 with '<' it is a prefix of the instantiation ("k_median2<true, false, 16>").
+
+Row of KERNELS
+    "flagger" / "unlaunched" / "file.py::test"   as above and below
+    dict(test="file.py::test", instances=[...])  the pack / unpack, scan and strategy-step kernels of the other entry
+             points: `instances` lists every instantiation a launch site of tricolour_amd.hip can produce, as fragments
+             with their template arguments ("k_pack_v<2>", "k_pack_scan_v<4, true, false, true>"; the bare name for a
+             kernel that is no template).  An entry dict(name="k_x<3>", unreachable="why") is an instantiation no public
+             call can reach.  The scans below hold the lists to the launch sites, and
+             tests/test_entry_kernels_gpu.py launches every reachable one in a call it compares with a host reference.
 """
 import glob
+import itertools
 import os
 import re
+
+import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -135,6 +147,19 @@ _ROWS = "test_scan_stream_gpu.py::"
 _UV = "test_uvcontsub.py::test_gpu_uvcontsub_agreement"
 _LRMS = "test_line_rms.py::test_gpu_small_and_odd_shapes"
 _MEDBIG = _PARITY + "test_median_kernels"
+_ENTRY = "test_entry_kernels_gpu.py::test_every_listed_instantiation_met_a_host_reference"
+
+# the two macro-expanded launch families of the fused scan pack
+SCAN_FAMILIES = {"k_pack_scan_v": "TRI_PACK_SCAN_V", "k_pack_scan_rows_v": "TRI_PACK_SCAN_ROWS_V"}
+
+
+def _scan_family(kernel):
+    return ["%s<%d, %s, %s, %s>" % ((kernel, nc) + tuple("true" if b else "false" for b in bits))
+            for nc in (1, 2, 4) for bits in itertools.product((False, True), repeat=3)]
+
+
+def _inst(test, *instances):
+    return dict(test=test, instances=list(instances))
 
 # "flagger": launched by sum_threshold_flagger on some route -- test_route_matrix_gpu.py must see it in an oracle-checked log
 KERNELS = {
@@ -157,15 +182,16 @@ KERNELS = {
     "k_abs_c64": _PARITY + "test_hypotf_kat",
     "k_panelize": _PARITY + "test_fused_sumthreshold_kernel_vs_generic_and_oracle",
     "k_unpanel_w": _PARITY + "test_fused_sumthreshold_kernel_vs_generic_and_oracle",
-    "k_fill_windows": "test_packing.py::test_gpu_pack_flag_unpack",
-    "k_pack": "test_packing.py::test_gpu_pack_flag_unpack", "k_pack_v": "test_packing.py::test_gpu_pack_flag_unpack",
-    "k_unpack_v": "test_packing.py::test_gpu_pack_flag_unpack", "k_unpack": "test_packing.py::test_gpu_pack_flag_unpack",
-    "k_flag_nans_zeros": "test_strategy_steps.py::test_gpu_strategy_steps",
-    "k_apply_bl_chan_mask": "test_strategy_steps.py::test_gpu_strategy_steps",
+    "k_fill_windows": _inst("test_packing.py::test_gpu_pack_flag_unpack", "k_fill_windows"),
+    "k_pack": _inst(_ENTRY, "k_pack"), "k_pack_v": _inst(_ENTRY, "k_pack_v<1>", "k_pack_v<2>", "k_pack_v<4>"),
+    "k_unpack_v": _inst(_ENTRY, "k_unpack_v<1>", "k_unpack_v<2>", "k_unpack_v<4>"), "k_unpack": _inst(_ENTRY, "k_unpack"),
+    # (the template argument is the TRI_VIS_* code: 0 complex64, 1 float32)
+    "k_flag_nans_zeros": _inst(_ENTRY, "k_flag_nans_zeros<0>", "k_flag_nans_zeros<1>"),
+    "k_apply_bl_chan_mask": _inst(_ENTRY, "k_apply_bl_chan_mask"),
     "k_uv_count": "unlaunched", "k_uv_diff": "unlaunched",
     "k_uv_mean": _UV, "k_uv_lowpass": _UV, "k_uv_resid": _UV, "k_uv_resid4": _UV, "k_uv_apply": _UV, "k_uv_apply4": _UV,
-    "k_window_counts": "test_window_statistics.py::test_gpu_window_counts",
-    "k_stokes_intensity": "test_stokes.py::test_gpu_intensities",
+    "k_window_counts": _inst("test_window_statistics.py::test_gpu_window_counts", "k_window_counts<true>", "k_window_counts<false>"),
+    "k_stokes_intensity": _inst(_ENTRY, "k_stokes_intensity<float>", "k_stokes_intensity<double>"),
     # kernels_linerms
     "k_lrms_power": _LRMS, "k_lrms_combine": _LRMS, "k_lrms_decide": _LRMS, "k_lrms_apply": _LRMS,
     # kernels_median
@@ -175,10 +201,13 @@ KERNELS = {
     # kernels_reject / reject_tile
     "k_median_reject": "flagger", "k_mr_predict": "flagger", "k_mr_pass": "flagger", "k_mr_finish": "flagger",
     # kernels_scan
-    "k_pack_scan_v": _SCAN + "test_gpu_pack_scan_matches_unfused_kernels", "k_pack_scan": _SCAN + "test_gpu_pack_scan_matches_unfused_kernels",
-    "k_unpack_scan": _SCAN + "test_gpu_unpack_scan_matches_numpy",
-    "k_pack_scan_rows_v": _ROWS + "test_gpu_pack_scan_rows_matches_pack_scan", "k_pack_scan_rows": _ROWS + "test_gpu_pack_scan_rows_matches_pack_scan",
-    "k_unpack_scan_rows": _ROWS + "test_gpu_unpack_scan_rows_matches_unpack_scan",
+    # (NC in {1, 2, 4}) x STOKES x MODEL x FLAGS: the launch macros TRI_PACK_SCAN_V / TRI_PACK_SCAN_ROWS_V
+    "k_pack_scan_v": _inst(_SCAN + "test_gpu_pack_scan_matches_unfused_kernels", *_scan_family("k_pack_scan_v")),
+    "k_pack_scan": _inst(_SCAN + "test_gpu_pack_scan_matches_unfused_kernels", "k_pack_scan"),
+    "k_unpack_scan": _inst(_SCAN + "test_gpu_unpack_scan_matches_numpy", "k_unpack_scan<4>", "k_unpack_scan<0>"),
+    "k_pack_scan_rows_v": _inst(_ROWS + "test_gpu_pack_scan_rows_matches_pack_scan", *_scan_family("k_pack_scan_rows_v")),
+    "k_pack_scan_rows": _inst(_ROWS + "test_gpu_pack_scan_rows_matches_pack_scan", "k_pack_scan_rows"),
+    "k_unpack_scan_rows": _inst(_ROWS + "test_gpu_unpack_scan_rows_matches_unpack_scan", "k_unpack_scan_rows<4>", "k_unpack_scan_rows<0>"),
     # kernels_sir
     "k_sir": "test_sir.py::test_gpu_sir_small_and_odd_shapes",
     # kernels_sumthreshold
@@ -208,6 +237,34 @@ def switch_legs(name):
     return SWITCHES[name].get("legs", [])
 
 
+def named_test(where):
+    """The test a KERNELS row names, or None ("flagger", "unlaunched")."""
+    if isinstance(where, dict):
+        return where["test"]
+    return where if "::" in where else None
+
+
+def instance_rows():
+    """{kernel: row} of the KERNELS rows that list their instantiations."""
+    return {k: w for k, w in KERNELS.items() if isinstance(w, dict)}
+
+
+def listed_instances(kernel, reachable_only=False):
+    out = []
+    for item in KERNELS[kernel]["instances"]:
+        if isinstance(item, dict):
+            if not reachable_only:
+                out.append(item["name"])
+        else:
+            out.append(item)
+    return out
+
+
+def reachable_instances():
+    """Every fragment tests/test_entry_kernels_gpu.py has to meet."""
+    return [f for k in sorted(instance_rows()) for f in listed_instances(k, reachable_only=True)]
+
+
 # ---- the scans ----
 
 def _sources(directory=CSRC):
@@ -230,6 +287,55 @@ def scan_kernels(directory=CSRC):
     found = set()
     for text in _sources(directory).values():
         found.update(re.findall(r"__global__[\s\S]{0,200}?\b(k_\w+)\s*\(", text))
+    return found
+
+
+def _abi_codes():
+    """TRI_* enumerators of the C header with their values (template arguments are written with them)."""
+    with open(os.path.join(ROOT, "include", "tricolour_amd.h"), encoding="utf-8") as fh:
+        return dict(re.findall(r"^\s*(TRI_[A-Z0-9_]+)\s*=\s*(-?\d+)\s*,", fh.read(), re.M))
+
+
+def _expand_launch_macros(hip):
+    """Replaces every use of a function-like macro whose body launches kernels (defined and undefined again inside
+    the function that uses it) by its body with the parameters substituted; the definitions themselves go."""
+    define = re.compile(r"#define\s+(\w+)\(([\w\s,]*)\)((?:[^\n]*\\\n)*[^\n]*\n)")
+    pos = 0
+    while True:
+        m = define.search(hip, pos)
+        if m is None:
+            return hip
+        name, params, body = m.group(1), [p.strip() for p in m.group(2).split(",")], m.group(3)
+        if "hipLaunchKernelGGL" not in body or name == "hipLaunchKernelGGL":
+            pos = m.end()
+            continue
+        body = body.replace("\\\n", "\n")
+
+        def use(u, params=params, body=body):
+            args = [a.strip() for a in u.group(1).split(",")]
+            if len(args) != len(params):
+                return u.group(0)
+            text = body
+            for p, a in zip(params, args):
+                text = re.sub(r"\b%s\b" % re.escape(p), a, text)
+            return text
+        hip = hip[:m.start()] + re.sub(r"\b%s\(([^()]*)\)" % re.escape(name), use, hip[m.end():])
+        pos = m.start()
+
+
+def scan_instances(directory=CSRC):
+    """{kernel: set of instantiations} of the launch sites of tricolour_amd.hip, launch macros expanded, template
+    arguments in the demangler's spelling ("k_pack_scan_v<4, true, false, true>"; TRI_* codes as their numbers)."""
+    with open(os.path.join(directory, "tricolour_amd.hip"), encoding="utf-8") as fh:
+        hip = re.sub(r"//[^\n]*", "", fh.read())
+    codes = _abi_codes()
+    found = {}
+    for m in re.finditer(r"hipLaunchKernelGGL\(\s*\(?\s*(k_\w+)\s*(?:<([^<>;()]*)>)?", _expand_launch_macros(hip)):
+        kernel, args = m.group(1), m.group(2)
+        frag = kernel
+        if args is not None:
+            frag += "<%s>" % ", ".join(codes.get(a.strip(), a.strip()) for a in args.split(","))
+        found.setdefault(kernel, set()).add(frag)
     return found
 
 
@@ -298,14 +404,27 @@ def test_every_kernel_has_a_row():
 
 
 def test_the_scans_notice_a_change(tmp_path):
-    """A renamed getenv string or an added kernel in a copy of the sources changes what the scans find."""
+    """A renamed getenv string, an added kernel or an added instantiation in a copy of the sources changes what the
+    scans find."""
     for path, text in _sources().items():
         text = text.replace('getenv("TRI_ST_NO_PIPE")', 'getenv("TRI_ST_NOPIPE")')
         if path.endswith("kernels_sir.hpp"):
             text += "\ntemplate <int N>\n__global__ void __launch_bounds__(64, f(N))\nk_added_later(const float* a) {}\n"
+        if path.endswith("tricolour_amd.hip"):
+            # one more instantiation at a literal launch site, one more use of a launch macro
+            text = text.replace("        else if (ncorr == 1)\n            hipLaunchKernelGGL(k_pack_v<1>,",
+                                "        else if (ncorr == 8)\n            hipLaunchKernelGGL(k_pack_v<8>, grid);\n"
+                                "        else if (ncorr == 1)\n            hipLaunchKernelGGL(k_pack_v<1>,", 1)
+            text = text.replace("        if (vec && ncorr == 4 && stokes) TRI_PACK_SCAN_V(4, true);",
+                                "        if (vec && ncorr == 8) TRI_PACK_SCAN_V(8, false);\n"
+                                "        else if (vec && ncorr == 4 && stokes) TRI_PACK_SCAN_V(4, true);", 1)
         (tmp_path / os.path.basename(path)).write_text(text, encoding="utf-8")
     assert scan_getenv(str(tmp_path)) ^ set(SWITCHES) == {"TRI_ST_NO_PIPE", "TRI_ST_NOPIPE"}
     assert scan_kernels(str(tmp_path)) - set(KERNELS) == {"k_added_later"}
+    before, after = scan_instances(), scan_instances(str(tmp_path))
+    added = {f for k in after for f in after[k] - before.get(k, set())}
+    assert added == {"k_pack_v<8>"} | {"k_pack_scan_v<8, false, %s, %s>" % (m, f) for m in ("true", "false") for f in ("true", "false")}
+    assert all(before[k] <= after[k] for k in before)
 
 
 def test_rows_are_well_formed():
@@ -331,7 +450,72 @@ def test_rows_are_well_formed():
     assert {n for n, r in SWITCHES.items() if r["cls"] not in ("route", "geometry", "unreachable")} == NOT_IN_MATRIX
     assert {n for n, r in SWITCHES.items() if r["cls"] == "elsewhere"} == {"TRI_NO_FUSED_RESID_TF", "TRI_BG_COPY_FLAGS", "TRI_UV_SCALAR"}
     for kernel, where in KERNELS.items():
-        assert where in ("flagger", "unlaunched") or "::" in where, kernel
+        if isinstance(where, dict):
+            assert set(where) == {"test", "instances"} and "::" in where["test"] and where["instances"], kernel
+            for item in where["instances"]:
+                if isinstance(item, dict):
+                    assert set(item) == {"name", "unreachable"} and item["unreachable"], kernel
+                else:
+                    assert isinstance(item, str), kernel
+            names = listed_instances(kernel)
+            assert len(set(names)) == len(names), kernel
+        else:
+            assert where in ("flagger", "unlaunched") or "::" in where, kernel
+
+
+# the kernels whose rows list their instantiations: those of kernels_scan.hpp and the pack / unpack, strategy-step,
+# flag-count and Stokes kernels of kernels_elementwise.hpp
+INSTANCE_KERNELS = {"k_fill_windows", "k_pack", "k_pack_v", "k_unpack_v", "k_unpack", "k_flag_nans_zeros", "k_apply_bl_chan_mask",
+                    "k_window_counts", "k_stokes_intensity"}
+
+
+def test_instance_rows_cover_the_entry_point_kernels():
+    with open(os.path.join(CSRC, "kernels_scan.hpp"), encoding="utf-8") as fh:
+        scan_kernels_ = set(re.findall(r"__global__[\s\S]{0,200}?\b(k_\w+)\s*\(", fh.read()))
+    assert len(scan_kernels_) == 6
+    assert set(instance_rows()) == INSTANCE_KERNELS | scan_kernels_
+    for kernel in instance_rows():
+        for frag in listed_instances(kernel):
+            assert base_name(frag) == kernel, (kernel, frag)
+            assert frag == kernel or re.match(r"^%s<[^<>]+>$" % kernel, frag), frag
+
+
+def test_listed_instances_are_the_launch_sites():
+    """Every instantiation a launch site of tricolour_amd.hip produces is listed, and nothing else is."""
+    found = scan_instances()
+    for kernel in sorted(instance_rows()):
+        listed = set(listed_instances(kernel))
+        assert found.get(kernel, set()) == listed, "%s: launched but not listed %s; listed but not launched %s" % (
+            kernel, sorted(found.get(kernel, set()) - listed), sorted(listed - found.get(kernel, set())))
+
+
+def test_the_literal_launch_sites_alone_miss_the_macro_families():
+    """The macro families are found through the macro expansion only: without it the scan sees none of their
+    instantiations (so the literal scan and the expansion are both at work), and with it the full product."""
+    with open(os.path.join(CSRC, "tricolour_amd.hip"), encoding="utf-8") as fh:
+        hip = re.sub(r"//[^\n]*", "", fh.read())
+    for kernel, macro in SCAN_FAMILIES.items():
+        literal = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*%s\s*<([^<>;()]*)>" % kernel, hip)
+        assert literal and all(re.search(r"\bNC\b", a) and re.search(r"\bS\b", a) for a in literal), kernel
+        assert "#define %s(NC, S)" % macro in hip and "#undef %s" % macro in hip
+        product = {"%s<%d, %s, %s, %s>" % (kernel, nc, s, m, f) for nc in (1, 2, 4) for s in ("true", "false")
+                   for m in ("true", "false") for f in ("true", "false")}
+        assert len(product) == 24 and set(listed_instances(kernel)) == product, kernel
+        assert scan_instances()[kernel] == product, kernel
+
+
+def test_a_wrong_ledger_row_fails_the_scan(monkeypatch):
+    """A listed instantiation the source does not launch, and a launched one that is not listed, both show."""
+    found = scan_instances()
+    monkeypatch.setitem(KERNELS, "k_pack_v", _inst(_ENTRY, "k_pack_v<1>", "k_pack_v<2>", "k_pack_v<4>", "k_pack_v<3>"))
+    assert set(listed_instances("k_pack_v")) - found["k_pack_v"] == {"k_pack_v<3>"}
+    monkeypatch.setitem(KERNELS, "k_pack_v", _inst(_ENTRY, "k_pack_v<1>", "k_pack_v<4>"))
+    assert found["k_pack_v"] - set(listed_instances("k_pack_v")) == {"k_pack_v<2>"}
+    with pytest.raises(AssertionError):
+        test_listed_instances_are_the_launch_sites()
+    monkeypatch.setitem(KERNELS, "k_pack_v", _inst(_ENTRY, "k_pack_v<1>", "k_pack_v<2>", dict(name="k_pack_v<4>", unreachable="an example")))
+    test_listed_instances_are_the_launch_sites()
+    assert "k_pack_v<4>" not in reachable_instances() and "k_pack_v<2>" in reachable_instances()
 
 
 def _function_exists(ref):
@@ -341,7 +525,7 @@ def _function_exists(ref):
 
 
 def test_named_tests_exist():
-    refs = {w for w in KERNELS.values() if "::" in w} | {r["test"] for r in SWITCHES.values() if r.get("test")}
+    refs = {named_test(w) for w in KERNELS.values() if named_test(w)} | {r["test"] for r in SWITCHES.values() if r.get("test")}
     missing = sorted(r for r in refs if not _function_exists(r))
     assert not missing, missing
 

@@ -1125,15 +1125,16 @@ __global__ void k_flag_nans_zeros(const void* __restrict__ vis, const uint8_t* _
 // out = chan_mask (mode 1), broadcast over corr and time.  Serves
 // apply_static_mask (flagging.py:151-172, one call per mask) and flag_autos
 // (flagging.py:90-93: all-ones mask on the auto-correlation baselines).
-// In-place safe (out == flags).  grid (ceil(nchan/256), ncorr*ntime, nbl)
+// In-place safe (out == flags).  grid (ceil(nchan/256), rows of the slab, baselines of the slab): the slab starts
+// at row row0 of baseline bl0 (a grid dimension holds at most 65535)
 __global__ void k_apply_bl_chan_mask(const uint8_t* __restrict__ flags, uint8_t* __restrict__ out,
                                      const uint8_t* __restrict__ bl_sel,
                                      const uint8_t* __restrict__ chan_mask, int mode, int nchan,
-                                     size_t rows_per_bl) {
+                                     size_t rows_per_bl, size_t row0, size_t bl0) {
     int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nchan) return;
-    size_t bl = blockIdx.z;
-    size_t a = (bl * rows_per_bl + blockIdx.y) * (size_t)nchan + f;
+    size_t bl = bl0 + blockIdx.z;
+    size_t a = (bl * rows_per_bl + row0 + blockIdx.y) * (size_t)nchan + f;
     uint8_t v = flags[a];
     if (bl_sel[bl]) v = mode == 0 ? (uint8_t)((v | chan_mask[f]) ? 1 : 0) : (uint8_t)(chan_mask[f] ? 1 : 0);
     out[a] = v;

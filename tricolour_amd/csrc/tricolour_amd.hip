@@ -2952,11 +2952,18 @@ extern "C" int tri_apply_baseline_channel_mask(const uint8_t* flags, uint8_t* ou
     if (mode != 0 && mode != 1) return set_err(TRI_EINVAL, "mode must be 0 (or) or 1 (override)");
     if (nbl < 0 || ncorr < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
     if (nbl == 0 || ncorr * ntime == 0 || nchan == 0) return TRI_OK;
-    if (ncorr * ntime > 65535 || nbl > 65535) return set_err(TRI_EUNSUPPORTED, "corr*time and bl must each be <= 65535 per call");
-    dim3 grid((unsigned)cdiv(nchan, 256), (unsigned)(ncorr * ntime), (unsigned)nbl);
-    hipLaunchKernelGGL(k_apply_bl_chan_mask, grid, dim3(256), 0, (hipStream_t)stream, flags, out_flags, bl_sel,
-                       chan_mask, mode, (int)nchan, (size_t)(ncorr * ntime));
-    LAUNCHCHK();
+    if (nchan > 0x7FFFFFFF) return set_err(TRI_EUNSUPPORTED, "dimension too large for one call");
+    // slabs of at most 65535 rows (gridDim.y) of at most 65535 baselines (gridDim.z), as for_row_slabs cuts rows
+    const int64_t rows = ncorr * ntime;
+    for (int64_t b0 = 0; b0 < nbl; b0 += 65535) {
+        for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
+            dim3 grid((unsigned)cdiv(nchan, 256), (unsigned)std::min<int64_t>(65535, rows - r0),
+                      (unsigned)std::min<int64_t>(65535, nbl - b0));
+            hipLaunchKernelGGL(k_apply_bl_chan_mask, grid, dim3(256), 0, (hipStream_t)stream, flags, out_flags, bl_sel,
+                               chan_mask, mode, (int)nchan, (size_t)rows, (size_t)r0, (size_t)b0);
+            LAUNCHCHK();
+        }
+    }
     return TRI_OK;
 }
 
