@@ -464,7 +464,10 @@ int tri_bench_sumthreshold(const float *data, const double *mad, uint8_t *out,
  *            receive the filtered weight and weight * data images, divided by
  *            float32(2 r + 1) ** 4.
  * `variant`: 0 = the flagger's default route for this radius, 1 = LDS delay
- * lines only (K4b / K4c / multi-pass), 2 = register delay lines (K4r).
+ * lines only (K4b / K4c), 2 = register delay lines (K4r).  Stages 0 and 2:
+ * TRI_EUNSUPPORTED where the route would be the in-place multi-pass filter
+ * (K4), which needs images padded to n_line + 4 r rows -- stage 0 beyond
+ * LANE4_R_MAX, stage 2 beyond the register rings and the stage pipeline.
  * (Stage 1, radius >= 56: the flagger takes the exact row filter, variant 0 the stage pipeline; variant 4 is K4x.)
  * For stage 2: 0 = default route, 1 = register delay lines (K4r), 2 / 3 = the
  * stage pipeline across four waves (K4p) with blocks of 16 / 8 positions

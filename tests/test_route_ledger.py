@@ -26,11 +26,27 @@ Row of KERNELS
              kernel that is no template).  An entry dict(name="k_x<3>", unreachable="why") is an instantiation no public
              call can reach.  The scans below hold the lists to the launch sites, and
              tests/test_entry_kernels_gpu.py launches every reachable one in a call it compares with a host reference.
+    dict(test=..., instances=[...], flagger=True)   the box-filter kernels (BOX_KERNELS): launched by the flagger -- they
+             count as `flagger` kernels for test_route_matrix_gpu.py (is_flagger) -- and listed by instantiation as
+             well.  They are launched from template functions behind the dispatchers' `switch` statements, which the
+             launch-site scan cannot follow, so these rows are held to the symbol table of the built library instead
+             (one weak __device_stub__ symbol per instantiation: test_box_rows_are_the_library_symbols), and
+             tests/test_boxfilter_instances_gpu.py launches every reachable one in a call it compares with the
+             oracle.  Besides `unreachable`, an entry of these rows may be dict(name=..., switch="TRI_X"): reachable only
+             under route switches that need a process of their own beyond the three that module starts (one entry:
+             TRI_FILTER_DIRECT_FT acts under TRI_NO_PACKED_FLAGS=1 only); the leg of that switch in
+             test_route_matrix_gpu.py, compared with the oracle, must then name exactly this instantiation as `new` or
+             `present`.
+
+Held to the launch sites (test_listed_instances_are_the_launch_sites): the pack / unpack, scan, strategy-step, Stokes and
+window-count rows.  Held to the symbol table: the rows of BOX_KERNELS.  The open remainder: k_sir (152 instantiations),
+the median, rejection, SumThreshold, uv-contsub and line-RMS families keep rows by base name only.
 """
 import glob
 import itertools
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -161,13 +177,68 @@ def _scan_family(kernel):
 def _inst(test, *instances):
     return dict(test=test, instances=list(instances))
 
+
+_BOX = "test_boxfilter_instances_gpu.py::test_every_listed_box_instantiation_met_a_host_reference"
+
+
+def _no(name, why):
+    return dict(name=name, unreachable=why)
+
+
+def _box(*instances):
+    return dict(test=_BOX, instances=list(instances), flagger=True)
+
+
+def _tf(b):
+    return "true" if b else "false"
+
+
+_NO_BOXW = ("launch_boxw runs behind boxw_usable() in the flagger's route only (the hook's named variants switch it off); at "
+            "2r = 22 .. 30 that route is the LDS-ring kernel: boxr_pick_ks_t() takes 2r == 20 or 2r >= 32, the stage pipeline 2r >= BOXQ_MIN_2R = 56")
+_NO_BOXT16 = "boxr_pick_ks_t() returns a ring size only for 2r >= 32 (32 slots or more) or 2r == 20 (20 slots)"
+_NO_BOXT20 = "KS = 20 is picked at 2r == 20 only: the LDS part of the delay line is empty"
+_NO_DIVIDE = "its only launch site always defers the division to k_masked_div (deferred_denom is never NULL there)"
+
+# the box-filter families: every instantiation in the built library.  What picks each one:
+BOX_ROWS = {
+    # launch_boxw: 2r = 20 .. 110
+    "k_boxw": _box(*[("k_boxw<%d>" % r2 if not 22 <= r2 <= 30 else _no("k_boxw<%d>" % r2, _NO_BOXW)) for r2 in range(20, 111, 2)]),
+    # launch_boxt / launch_boxt_ks: <KS, LDS part present, image>
+    "k_boxt": _box(*[_no("k_boxt<16, %s, %d>" % (_tf(l), i), _NO_BOXT16) for l in (False, True) for i in (0, 1)],
+                   *["k_boxt<20, false, %d>" % i for i in (0, 1)], *[_no("k_boxt<20, true, %d>" % i, _NO_BOXT20) for i in (0, 1)],
+                   *["k_boxt<%d, %s, %d>" % (ks, _tf(l), i) for ks in (32, 64, 80) for l in (False, True) for i in (0, 1)]),
+    "k_boxt_spec": _box(*["k_boxt_spec<%d, %s>" % (ks, _tf(l)) for ks in (8, 16, 32, 64, 80) for l in (False, True)]),
+    "k_boxp_spec": _box("k_boxp_spec<16, 16>", "k_boxp_spec<8, 16>"),
+    # launch_boxq: <KS, image, block>
+    "k_boxq": _box(*["k_boxq<%d, %d, 8>" % (ks, i) for ks in (32, 40, 48, 56, 64, 80) for i in (0, 1)],
+                   *["k_boxq<%d, %d, 16>" % (ks, i) for ks in (16, 32, 48, 64, 80, 96) for i in (0, 1)]),
+    "k_boxq_deep": _box(*["k_boxq_deep<%d, %d>" % (ks, i) for ks in (80, 96) for i in (0, 1)]),
+    # launch_boxf, the stage pipeline: <KS, MODE, block> (no <80, 2, 8>: it would spill)
+    "k_boxqf": _box(*["k_boxqf<%d, %d, 8>" % (ks, m) for ks in (16, 24, 32, 40, 48, 56, 64, 72) for m in (1, 2)], "k_boxqf<80, 1, 8>",
+                    *["k_boxqf<%d, %d, 16>" % (ks, m) for ks in (16, 32, 48, 64, 80, 96) for m in (1, 2)]),
+    # launch_boxf_ks: <KS, LDS part present, MODE, waves per SIMD> (KS = 32 with more than 14 LDS slots: one wave)
+    "k_boxf": _box(*["k_boxf<%d, %s, %d, %d>" % (ks, _tf(l), m, 1 if ks >= 64 else 2) for ks in (8, 16, 32, 64, 80) for l in (False, True) for m in (1, 2)],
+                   "k_boxf<32, true, 1, 1>", "k_boxf<32, true, 2, 1>"),
+    # launch_boxx: <threads per image, chunk, MODE, verified reciprocal>
+    # (<256, 19, *, false> under TRI_BOXX_NTI=256 only: r > 128 implies r >= 64, where the 128-thread candidates come first)
+    "k_boxx": _box(*["k_boxx<%d, %d, %d, %s>" % (nti, l, m, _tf(rc)) for nti, l in ((128, 37), (128, 41), (256, 17), (256, 19), (256, 21), (256, 25)) for m in (1, 2) for rc in (True, False)]),
+    "k_colfilter": _box("k_colfilter<0>", "k_colfilter<1>"),
+    # <source (0 byte flags, 1 float images, 2 packed flags), divides itself, transposed output>
+    "k_colfilter_lds": _box("k_colfilter_lds<0, true, false>", "k_colfilter_lds<1, true, false>", "k_colfilter_lds<1, false, false>",
+                            dict(name="k_colfilter_lds<1, true, true>", switch="TRI_FILTER_DIRECT_FT"),
+                            "k_colfilter_lds<2, true, false>", "k_colfilter_lds<2, false, false>"),
+    "k_colfilter_lds_t": _box("k_colfilter_lds_t<false>", _no("k_colfilter_lds_t<true>", _NO_DIVIDE)),
+    "k_colfilter_lds_tf": _box("k_colfilter_lds_tf<1>", "k_colfilter_lds_tf<2>"),
+    # <source (3: the time stage's TF images), divides itself>
+    "k_colfilter_lane4": _box(_no("k_colfilter_lane4<0, true>", "byte flags have no lane-per-stage kernel (launch_colfilter): only its LDS opt-in names it"),
+                              "k_colfilter_lane4<1, true>", "k_colfilter_lane4<1, false>", "k_colfilter_lane4<2, true>", "k_colfilter_lane4<2, false>",
+                              "k_colfilter_lane4<3, false>", _no("k_colfilter_lane4<3, true>", _NO_DIVIDE)),
+}
+BOX_KERNELS = tuple(BOX_ROWS)
+
 # "flagger": launched by sum_threshold_flagger on some route -- test_route_matrix_gpu.py must see it in an oracle-checked log
 KERNELS = {
-    # kernels_boxexact / boxfilter / boxline / boxpipe / boxweight
-    "k_boxx": "flagger", "k_colfilter": "flagger", "k_colfilter_lds": "flagger", "k_colfilter_lds_t": "flagger",
-    "k_colfilter_lds_tf": "flagger", "k_colfilter_lane4": "flagger", "k_boxt": "flagger", "k_boxt_spec": "flagger",
-    "k_boxf": "flagger", "k_boxp_spec": "flagger", "k_boxq": "flagger", "k_boxq_deep": "flagger", "k_boxqf": "flagger",
-    "k_boxw": "flagger",
+    # kernels_boxexact / boxfilter / boxline / boxpipe / boxweight: BOX_ROWS below (listed by instantiation)
     # kernels_elementwise: the flagger's passes
     "k_prepare": "flagger", "k_transpose": "flagger", "k_unpanel": "flagger", "k_transpose_u8w": "flagger",
     "k_build_wo": "flagger", "k_build_wo4": "flagger", "k_masked_div": "flagger", "k_reject": "flagger",
@@ -216,6 +287,7 @@ KERNELS = {
     "k_tables": "flagger", "k_gather_col_f32": "flagger", "k_gather_col_u8": "flagger", "k_normalise_flags": "flagger",
     "k_check_box_divide": _PARITY + "test_division_by_box_denominator",
 }
+KERNELS.update(BOX_ROWS)
 
 
 def matches(fragment, name):
@@ -244,9 +316,55 @@ def named_test(where):
     return where if "::" in where else None
 
 
+def is_flagger(kernel):
+    """Whether sum_threshold_flagger launches the kernel on some route (the rows of BOX_KERNELS say so in a field)."""
+    where = KERNELS.get(kernel)
+    return where == "flagger" or (isinstance(where, dict) and bool(where.get("flagger")))
+
+
 def instance_rows():
-    """{kernel: row} of the KERNELS rows that list their instantiations."""
-    return {k: w for k, w in KERNELS.items() if isinstance(w, dict)}
+    """{kernel: row} of the KERNELS rows held to the launch sites: those that list their instantiations, the box-filter
+    rows (held to the symbol table) apart."""
+    return {k: w for k, w in KERNELS.items() if isinstance(w, dict) and not w.get("flagger")}
+
+
+def box_instances(kernel, reachable_only=False):
+    """The instantiations a row of BOX_KERNELS lists (`switch` entries count as reachable)."""
+    out = []
+    for item in KERNELS[kernel]["instances"]:
+        if not isinstance(item, dict):
+            out.append(item)
+        elif not (reachable_only and "unreachable" in item):
+            out.append(item["name"])
+    return out
+
+
+def switch_met_instances():
+    """{instantiation: switch} of the BOX_KERNELS entries the route matrix meets under a switch of its own."""
+    return {item["name"]: item["switch"] for k in BOX_KERNELS for item in KERNELS[k]["instances"] if isinstance(item, dict) and "switch" in item}
+
+
+def box_row_errors(symbols):
+    """What differs between the rows of BOX_KERNELS and a list of the library's kernel instantiations."""
+    out = []
+    for kernel in BOX_KERNELS:
+        listed, built = set(box_instances(kernel)), {n for n in symbols if base_name(n) == kernel}
+        if listed != built:
+            out.append("%s: in the library but not listed %s; listed but not in the library %s" % (kernel, sorted(built - listed), sorted(listed - built)))
+    return out
+
+
+def library_instances(path):
+    """The kernel instantiations of a built library: one weak __device_stub__ symbol each, template arguments in the
+    demangler's spelling."""
+    for nm in ("nm", "/opt/rocm/llvm/bin/llvm-nm"):
+        try:
+            text = subprocess.run([nm, "-C", path], capture_output=True, text=True, check=True).stdout
+            break
+        except (OSError, subprocess.CalledProcessError):
+            text = None
+    assert text, "no nm to read %s with" % path
+    return sorted(set(re.findall(r"__device_stub__(k_\w+(?:<[^()]*>)?)\(", text)))
 
 
 def listed_instances(kernel, reachable_only=False):
@@ -451,13 +569,16 @@ def test_rows_are_well_formed():
     assert {n for n, r in SWITCHES.items() if r["cls"] == "elsewhere"} == {"TRI_NO_FUSED_RESID_TF", "TRI_BG_COPY_FLAGS", "TRI_UV_SCALAR"}
     for kernel, where in KERNELS.items():
         if isinstance(where, dict):
-            assert set(where) == {"test", "instances"} and "::" in where["test"] and where["instances"], kernel
+            assert set(where) - {"flagger"} == {"test", "instances"} and "::" in where["test"] and where["instances"], kernel
+            assert ("flagger" in where) == (kernel in BOX_KERNELS) and where.get("flagger", True) is True, kernel
             for item in where["instances"]:
                 if isinstance(item, dict):
-                    assert set(item) == {"name", "unreachable"} and item["unreachable"], kernel
+                    assert set(item) in ({"name", "unreachable"}, {"name", "switch"}) and all(item.values()), kernel
+                    assert "switch" not in item or kernel in BOX_KERNELS, kernel
                 else:
                     assert isinstance(item, str), kernel
-            names = listed_instances(kernel)
+            names = box_instances(kernel) if kernel in BOX_KERNELS else listed_instances(kernel)
+            assert all(base_name(n) == kernel and (n == kernel or re.match(r"^%s<[^<>]+>$" % kernel, n)) for n in names), kernel
             assert len(set(names)) == len(names), kernel
         else:
             assert where in ("flagger", "unlaunched") or "::" in where, kernel
@@ -516,6 +637,62 @@ def test_a_wrong_ledger_row_fails_the_scan(monkeypatch):
     monkeypatch.setitem(KERNELS, "k_pack_v", _inst(_ENTRY, "k_pack_v<1>", "k_pack_v<2>", dict(name="k_pack_v<4>", unreachable="an example")))
     test_listed_instances_are_the_launch_sites()
     assert "k_pack_v<4>" not in reachable_instances() and "k_pack_v<2>" in reachable_instances()
+
+
+def test_box_rows_are_the_library_symbols():
+    """The rows of BOX_KERNELS against the symbol table of the built library (built here if it is missing, as for
+    tests/test_abi.py): an instantiation added to a dispatcher, removed or renamed without its row fails here."""
+    from tricolour_amd import _lib
+    _lib.build()
+    symbols = library_instances(_lib.LIB_PATH)
+    assert len(symbols) > 300 and set(BOX_KERNELS) <= {base_name(n) for n in symbols}, len(symbols)
+    # (the log the GPU tests compare with spells the names as the symbol table does)
+    assert "k_boxqf<40, 2, 8>" in symbols and "k_boxf<32, true, 2, 1>" in symbols and "k_boxw<110>" in symbols
+    errors = box_row_errors(symbols)
+    assert not errors, "\n".join(errors)
+
+
+def test_a_wrong_box_row_fails_against_the_symbols(monkeypatch):
+    """A row with a name too many and a row with a name missing both fail against a given symbol list, unreachable
+    entries included; so does an instantiation a dispatcher gained."""
+    symbols = [n for k in BOX_KERNELS for n in box_instances(k)] + ["k_sir<4, true>", "k_pack_v<2>"]
+    assert not box_row_errors(symbols)
+    gained = box_row_errors(symbols + ["k_boxqf<88, 1, 8>"])
+    assert len(gained) == 1 and "not listed ['k_boxqf<88, 1, 8>']" in gained[0], gained
+    for lost in ("k_boxw<46>", "k_boxt<16, true, 0>"):                       # a reachable one, an unreachable one
+        errors = box_row_errors([n for n in symbols if n != lost])
+        assert len(errors) == 1 and "not in the library ['%s']" % lost in errors[0], errors
+    row = KERNELS["k_boxp_spec"]
+    monkeypatch.setitem(KERNELS, "k_boxp_spec", dict(row, instances=row["instances"] + ["k_boxp_spec<4, 16>"]))
+    errors = box_row_errors(symbols)
+    assert len(errors) == 1 and errors[0].startswith("k_boxp_spec:") and "not in the library ['k_boxp_spec<4, 16>']" in errors[0], errors
+    monkeypatch.setitem(KERNELS, "k_boxp_spec", dict(row, instances=row["instances"][:1]))
+    errors = box_row_errors(symbols)
+    assert len(errors) == 1 and "not listed ['k_boxp_spec<8, 16>']" in errors[0], errors
+    monkeypatch.setitem(KERNELS, "k_boxp_spec", dict(row, instances=[row["instances"][0], _no("k_boxp_spec<8, 16>", "an example")]))
+    assert not box_row_errors(symbols)
+    assert "k_boxp_spec<8, 16>" not in box_instances("k_boxp_spec", reachable_only=True)
+
+
+def test_box_rows_cover_the_box_filter_kernels():
+    """BOX_KERNELS are the kernels of the five box-filter headers, all of them; each is still a flagger kernel."""
+    found = set()
+    for name in ("kernels_boxexact.hpp", "kernels_boxfilter.hpp", "kernels_boxline.hpp", "kernels_boxpipe.hpp", "kernels_boxweight.hpp"):
+        with open(os.path.join(CSRC, name), encoding="utf-8") as fh:
+            found.update(re.findall(r"__global__[\s\S]{0,200}?\b(k_\w+)\s*\(", fh.read()))
+    assert found == set(BOX_KERNELS), sorted(found ^ set(BOX_KERNELS))
+    assert all(is_flagger(k) for k in BOX_KERNELS) and not is_flagger("k_pack_v") and is_flagger("k_prepare")
+
+
+def test_switch_entries_are_named_by_their_route_leg():
+    """A `switch` entry is met by test_route_matrix_gpu.py: a leg of that switch must name exactly this instantiation as
+    new or present, so that its oracle-checked log is known to hold it."""
+    for frag, switch in switch_met_instances().items():
+        named = set()
+        for leg in switch_legs(switch):
+            for what in leg["cases"].values():
+                named.update(what.get("new", []) + what.get("present", []))
+        assert SWITCHES[switch]["cls"] == "route" and frag in named, (frag, switch, sorted(named))
 
 
 def _function_exists(ref):

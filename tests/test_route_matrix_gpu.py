@@ -52,7 +52,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_route_ledger import KERNELS, SWITCHES, base_name, launches
+from test_route_ledger import KERNELS, SWITCHES, base_name, is_flagger, launches
 from test_final_pass_routes_gpu import TAP_F32, TAP_U8, same_f32
 
 pytestmark = pytest.mark.gpu
@@ -399,7 +399,7 @@ def test_every_flagger_kernel_met_the_oracle(children, expected):
                 seen.setdefault(base_name(name), set()).add(name)
     for base in sorted(seen):
         print("%s: %s" % (base, "; ".join(sorted(seen[base]))))
-    missing = sorted(k for k, where in KERNELS.items() if where == "flagger" and k not in seen)
-    stray = sorted(k for k in seen if KERNELS.get(k) != "flagger")
+    missing = sorted(k for k in KERNELS if is_flagger(k) and k not in seen)
+    stray = sorted(k for k in seen if not is_flagger(k))
     assert not missing, "flagger kernels no oracle-checked call launched: %s" % missing
     assert not stray, "kernels launched by the flagger that the ledger places elsewhere: %s" % stray

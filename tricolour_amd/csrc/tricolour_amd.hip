@@ -806,6 +806,9 @@ enum ColFlag : unsigned {
     COL_WEIGHTS_01 = 2        // the weights are 0 / 1: integer arithmetic where it is exact
 };
 enum class ColFamily { SpecPipe, SpecRing, StagePipe, RegRing, Lane4, LdsRing, MultiPass };   // K4p, K4r (spectrum), K4q, K4r, K4c, K4b, K4
+// tri_bench_boxfilter sets this: its images are the caller's, n rows each, without the n + 4r rows the in-place
+// multi-pass kernel works in -- launch_colfilter then refuses that family instead of launching it
+thread_local bool g_colfilter_unpadded = false;
 
 // One axis of masked_gaussian_filter's two box filters (weight image and data image) on a column-layout image pair.
 // Output: rows [0,n) of dstW / dstO.  deferred_denom (optional): where the kernel can, the division by float32(d)**4 is left
@@ -844,6 +847,8 @@ int launch_colfilter(const Run& r, ColSrc src, float* bufW, float* bufO, const f
         }
         fam = bt > 0 ? ColFamily::LdsRing : ColFamily::MultiPass;
     }
+    if (fam == ColFamily::MultiPass && g_colfilter_unpadded)
+        return set_err(TRI_EUNSUPPORTED, "radius %d takes the in-place multi-pass filter, which needs images padded to n + 4r rows", rad);
     // --- launch ---
     // (kernels that build their images ignore bufW / bufO)
     const bool built = src != ColSrc::Images, divide = !deferred_denom;
@@ -2615,6 +2620,7 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     HIPCHK(hipEventCreate(e1.out()));
     const size_t N = (size_t)n_line * n_col;
     const RouteOverrides saved;
+    ScopedSet<bool> unpadded(g_colfilter_unpadded, true);
     g_boxr_override = variant == 0 ? -1 : (variant == 1 ? 0 : 1);
     g_boxw_override = variant == 0 ? -1 : 0;            // the named variants run BOTH images through their own kernels
     // stage 2: 0 = the flagger's route, 1 = register rings, 2 / 3 = stage pipeline with blocks of 16 / 8
