@@ -526,6 +526,27 @@ int tri_sum_threshold_flagger_debug(const void *vis, int vis_dtype,
                                     void *stream, float *dbg_f32, uint8_t *dbg_u8);
 
 /*
+ * Test hook: tri_uvcontsub_flagger (same arguments, launches and flags) that additionally taps the LAST major
+ * cycle's intermediates of ALL n_cp products into caller-provided device buffers, indexed by the global product
+ * number also when the call runs in several workspace batches.  Any buffer may be NULL; with major_cycles == 0
+ * they are left untouched.
+ *   dbg_avg    (n_cp, nchan) complex64         time-mean spectrum (k_uv_mean)
+ *   dbg_smooth (n_cp, nchan) complex64         its low-passed form (k_uv_lowpass)
+ *   dbg_absres (n_cp, ntime, nchan) float32    |vis - smooth|
+ *   dbg_mflags (n_cp, ntime, nchan) uint8      samples the MAD ignores: flagged at the cycle's start, or NaN residual
+ *   dbg_med    (n_cp, 2) float64               median of the residual and median of | residual - median | (NaN: nothing to take it of)
+ *   dbg_cnt    (n_cp) uint32                   flagged samples at the cycle's start
+ * No reference counterpart.
+ */
+int tri_uvcontsub_flagger_debug(const void *vis_c64, const uint8_t *flags, uint8_t *out_flags,
+                                int64_t n_cp, int64_t ntime, int64_t nchan,
+                                int64_t major_cycles, int64_t or_original_from_cycle,
+                                int64_t taylor_degrees, double sigma,
+                                void *workspace, size_t workspace_bytes, void *stream,
+                                void *dbg_avg, void *dbg_smooth, float *dbg_absres,
+                                uint8_t *dbg_mflags, double *dbg_med, uint32_t *dbg_cnt);
+
+/*
  * Measurement / test hook: ONE rejection step of the background loop,
  *     flags |= resid > median_abs(resid[~flags]) * 1.4826 * reject     per (window, chunk) block
  * (flagging.py:553-574 with _median_abs :267), by the one-pass route the flagger

@@ -39,8 +39,10 @@ Row of KERNELS
              `present`.
 
 Held to the launch sites (test_listed_instances_are_the_launch_sites): the pack / unpack, scan, strategy-step, Stokes and
-window-count rows.  Held to the symbol table: the rows of BOX_KERNELS.  The open remainder: k_sir (152 instantiations),
-the median, rejection, SumThreshold, uv-contsub and line-RMS families keep rows by base name only.
+window-count rows.  The uv-contsub rows and those of its multi-workgroup median (k_medbig_*) as well: every instantiation behind
+tri_uvcontsub_flagger is met, stage by stage, by tests/test_uvcontsub_kernels_gpu.py (`also` names a second test that runs
+the kernel against a reference).  Held to the symbol table: the rows of BOX_KERNELS.  The open remainder: k_sir (152
+instantiations), the segmented-median, rejection, SumThreshold and line-RMS families keep rows by base name only.
 """
 import glob
 import itertools
@@ -164,6 +166,9 @@ _UV = "test_uvcontsub.py::test_gpu_uvcontsub_agreement"
 _LRMS = "test_line_rms.py::test_gpu_small_and_odd_shapes"
 _MEDBIG = _PARITY + "test_median_kernels"
 _ENTRY = "test_entry_kernels_gpu.py::test_every_listed_instantiation_met_a_host_reference"
+UV_CLOSING = "test_uvcontsub_kernels_gpu.py::test_every_uvcontsub_instantiation_met_its_stage_references"
+# the closing tests of the GPU modules that demand their own rows; rows that name any other test are demanded by _ENTRY's
+CLOSING_TESTS = (_ENTRY, UV_CLOSING)
 
 # the two macro-expanded launch families of the fused scan pack
 SCAN_FAMILIES = {"k_pack_scan_v": "TRI_PACK_SCAN_V", "k_pack_scan_rows_v": "TRI_PACK_SCAN_ROWS_V"}
@@ -174,8 +179,11 @@ def _scan_family(kernel):
             for nc in (1, 2, 4) for bits in itertools.product((False, True), repeat=3)]
 
 
-def _inst(test, *instances):
-    return dict(test=test, instances=list(instances))
+def _inst(test, *instances, also=None):
+    row = dict(test=test, instances=list(instances))
+    if also:
+        row["also"] = also
+    return row
 
 
 _BOX = "test_boxfilter_instances_gpu.py::test_every_listed_box_instantiation_met_a_host_reference"
@@ -260,15 +268,20 @@ KERNELS = {
     "k_flag_nans_zeros": _inst(_ENTRY, "k_flag_nans_zeros<0>", "k_flag_nans_zeros<1>"),
     "k_apply_bl_chan_mask": _inst(_ENTRY, "k_apply_bl_chan_mask"),
     "k_uv_count": "unlaunched", "k_uv_diff": "unlaunched",
-    "k_uv_mean": _UV, "k_uv_lowpass": _UV, "k_uv_resid": _UV, "k_uv_resid4": _UV, "k_uv_apply": _UV, "k_uv_apply4": _UV,
+    "k_uv_mean": _inst(UV_CLOSING, "k_uv_mean", also=_UV), "k_uv_lowpass": _inst(UV_CLOSING, "k_uv_lowpass", also=_UV),
+    "k_uv_resid": _inst(UV_CLOSING, "k_uv_resid", also=_UV), "k_uv_resid4": _inst(UV_CLOSING, "k_uv_resid4", also=_UV),
+    "k_uv_apply": _inst(UV_CLOSING, "k_uv_apply", also=_UV), "k_uv_apply4": _inst(UV_CLOSING, "k_uv_apply4", also=_UV),
     "k_window_counts": _inst("test_window_statistics.py::test_gpu_window_counts", "k_window_counts<true>", "k_window_counts<false>"),
     "k_stokes_intensity": _inst(_ENTRY, "k_stokes_intensity<float>", "k_stokes_intensity<double>"),
     # kernels_linerms
     "k_lrms_power": _LRMS, "k_lrms_combine": _LRMS, "k_lrms_decide": _LRMS, "k_lrms_apply": _LRMS,
     # kernels_median
     "k_median": "flagger", "k_median2": "flagger", "k_median_wave": "flagger", "k_spec_from_med": "flagger",
-    "k_medbig_range": _MEDBIG, "k_medbig_hist": _MEDBIG, "k_medbig_pick": _MEDBIG, "k_medbig_compact": _MEDBIG,
-    "k_medbig_select": _MEDBIG,
+    # (the template argument: 16-byte loads; both forms with and without a centre in tests/test_uvcontsub_kernels_gpu.py)
+    "k_medbig_range": _inst(UV_CLOSING, "k_medbig_range", also=_MEDBIG), "k_medbig_pick": _inst(UV_CLOSING, "k_medbig_pick", also=_MEDBIG),
+    "k_medbig_hist": _inst(UV_CLOSING, "k_medbig_hist<true>", "k_medbig_hist<false>", also=_MEDBIG),
+    "k_medbig_compact": _inst(UV_CLOSING, "k_medbig_compact<true>", "k_medbig_compact<false>", also=_MEDBIG),
+    "k_medbig_select": _inst(UV_CLOSING, "k_medbig_select<true>", "k_medbig_select<false>", also=_MEDBIG),
     # kernels_reject / reject_tile
     "k_median_reject": "flagger", "k_mr_predict": "flagger", "k_mr_pass": "flagger", "k_mr_finish": "flagger",
     # kernels_scan
@@ -378,9 +391,12 @@ def listed_instances(kernel, reachable_only=False):
     return out
 
 
-def reachable_instances():
-    """Every fragment tests/test_entry_kernels_gpu.py has to meet."""
-    return [f for k in sorted(instance_rows()) for f in listed_instances(k, reachable_only=True)]
+def reachable_instances(closing=_ENTRY):
+    """Every fragment the closing test `closing` of a GPU module has to meet: the rows that name it -- and, for
+    tests/test_entry_kernels_gpu.py, also the rows that name a test which is no module's closing test."""
+    assert closing in CLOSING_TESTS, closing
+    mine = lambda row: row["test"] == closing or (closing == _ENTRY and row["test"] not in CLOSING_TESTS)
+    return [f for k, row in sorted(instance_rows().items()) if mine(row) for f in listed_instances(k, reachable_only=True)]
 
 
 # ---- the scans ----
@@ -569,7 +585,8 @@ def test_rows_are_well_formed():
     assert {n for n, r in SWITCHES.items() if r["cls"] == "elsewhere"} == {"TRI_NO_FUSED_RESID_TF", "TRI_BG_COPY_FLAGS", "TRI_UV_SCALAR"}
     for kernel, where in KERNELS.items():
         if isinstance(where, dict):
-            assert set(where) - {"flagger"} == {"test", "instances"} and "::" in where["test"] and where["instances"], kernel
+            assert set(where) - {"flagger", "also"} == {"test", "instances"} and "::" in where["test"] and where["instances"], kernel
+            assert "also" not in where or ("::" in where["also"] and where["also"] != where["test"] and kernel not in BOX_KERNELS), kernel
             assert ("flagger" in where) == (kernel in BOX_KERNELS) and where.get("flagger", True) is True, kernel
             for item in where["instances"]:
                 if isinstance(item, dict):
@@ -588,6 +605,10 @@ def test_rows_are_well_formed():
 # flag-count and Stokes kernels of kernels_elementwise.hpp
 INSTANCE_KERNELS = {"k_fill_windows", "k_pack", "k_pack_v", "k_unpack_v", "k_unpack", "k_flag_nans_zeros", "k_apply_bl_chan_mask",
                     "k_window_counts", "k_stokes_intensity"}
+# ... and the kernels behind tri_uvcontsub_flagger: kernels_elementwise.hpp's k_uv_* that have a launch site, kernels_median.hpp's K3d
+UV_KERNELS = {"k_uv_mean", "k_uv_lowpass", "k_uv_resid", "k_uv_resid4", "k_uv_apply", "k_uv_apply4",
+              "k_medbig_range", "k_medbig_hist", "k_medbig_pick", "k_medbig_compact", "k_medbig_select"}
+INSTANCE_KERNELS |= UV_KERNELS
 
 
 def test_instance_rows_cover_the_entry_point_kernels():
@@ -595,6 +616,8 @@ def test_instance_rows_cover_the_entry_point_kernels():
         scan_kernels_ = set(re.findall(r"__global__[\s\S]{0,200}?\b(k_\w+)\s*\(", fh.read()))
     assert len(scan_kernels_) == 6
     assert set(instance_rows()) == INSTANCE_KERNELS | scan_kernels_
+    uv = {k for k in KERNELS if k.startswith(("k_uv_", "k_medbig_"))}
+    assert uv - UV_KERNELS == {"k_uv_count", "k_uv_diff"} and all(KERNELS[k] == "unlaunched" for k in uv - UV_KERNELS)
     for kernel in instance_rows():
         for frag in listed_instances(kernel):
             assert base_name(frag) == kernel, (kernel, frag)
@@ -703,6 +726,7 @@ def _function_exists(ref):
 
 def test_named_tests_exist():
     refs = {named_test(w) for w in KERNELS.values() if named_test(w)} | {r["test"] for r in SWITCHES.values() if r.get("test")}
+    refs |= {w["also"] for w in KERNELS.values() if isinstance(w, dict) and w.get("also")}
     missing = sorted(r for r in refs if not _function_exists(r))
     assert not missing, missing
 

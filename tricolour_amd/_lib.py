@@ -159,6 +159,10 @@ _SIGNATURES = {
     "tri_uvcontsub_flagger": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_size_t,
                                         C.c_void_p]),
+    "tri_uvcontsub_flagger_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                              C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
     "tri_sir_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "tri_scale_invariant_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                            C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -1160,6 +1160,9 @@ __global__ void k_uv_count(const uint8_t* __restrict__ rflags, unsigned* __restr
 
 // nanmean over time per channel (:1037-1044): complex64 accumulation in time
 // order, count of samples that are neither flagged nor NaN; none -> 0.
+// A sum that is not finite in either component -> 0 as well: the reference resets avg[isnan(avg)] = 0 (:1044), and numpy's
+// complex division gives a NaN component to every such sum (+Inf and -Inf in a channel: nan + nan j; a single +Inf:
+// inf + nan j), so an unflagged infinity costs its channel's mean, not the whole product's smooth spectrum.
 // grid (ceil(F/256), n_cp)
 __global__ void k_uv_mean(const float2* __restrict__ vis, const uint8_t* __restrict__ rflags,
                           float2* __restrict__ avg, int T, int F) {
@@ -1175,7 +1178,7 @@ __global__ void k_uv_mean(const float2* __restrict__ vis, const uint8_t* __restr
         if (!rflags[a] && !isnan(z.x) && !isnan(z.y)) { sr += z.x; si += z.y; n++; }
     }
     float2 m = make_float2(0.0f, 0.0f);
-    if (n > 0) m = make_float2((float)((double)sr / (double)n), (float)((double)si / (double)n));
+    if (n > 0 && isfinite(sr) && isfinite(si)) m = make_float2((float)((double)sr / (double)n), (float)((double)si / (double)n));
     avg[cp * (size_t)F + f] = m;
 }
 

@@ -3008,11 +3008,15 @@ static int launch_median_big(hipStream_t st, const float* data, const uint8_t* f
     return TRI_OK;
 }
 
-extern "C" int tri_uvcontsub_flagger(const void* vis_c64, const uint8_t* flags, uint8_t* out_flags,
-                                     int64_t n_cp, int64_t ntime, int64_t nchan,
-                                     int64_t major_cycles, int64_t or_original_from_cycle,
-                                     int64_t taylor_degrees, double sigma, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
+// Caller-provided device buffers of tri_uvcontsub_flagger_debug (any may be NULL), indexed by the GLOBAL product number:
+// avg / smooth (n_cp, F), absres / mflags (n_cp, T, F), med (n_cp, 2) = {first median, MAD}, cnt (n_cp)
+struct UvTaps { float2* avg; float2* smooth; float* absres; uint8_t* mflags; double* med; unsigned* cnt; };
+
+static int uvcontsub_impl(const void* vis_c64, const uint8_t* flags, uint8_t* out_flags,
+                          int64_t n_cp, int64_t ntime, int64_t nchan,
+                          int64_t major_cycles, int64_t or_original_from_cycle,
+                          int64_t taylor_degrees, double sigma, void* workspace,
+                          size_t workspace_bytes, void* stream, const UvTaps* taps) {
     if (!vis_c64 || !flags || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
     if (n_cp < 0 || ntime <= 0 || nchan <= 0) return set_err(TRI_EINVAL, "bad shape");
     if (taylor_degrees < 0 || taylor_degrees > 64) return set_err(TRI_EUNSUPPORTED, "taylor_degrees must be in [0, 64]");
@@ -3069,9 +3073,43 @@ extern "C" int tri_uvcontsub_flagger(const void* vis_c64, const uint8_t* flags, 
             else
                 hipLaunchKernelGGL(k_uv_apply, dim3((unsigned)cdiv((int64_t)N, 256), (unsigned)B), dim3(256), 0, st, absres, mad, cnt, rf, (float)sigma, mi >= or_original_from_cycle ? 1 : 0, N);
             LAUNCHCHK();
+            if (taps && mi == major_cycles - 1) {
+                // the last cycle's state of this batch, device to device on the call's stream, to the products' global places
+                const size_t g = (size_t)c0, nb = (size_t)B;
+                if (taps->avg) HIPCHK(hipMemcpyAsync(taps->avg + g * F, avg, nb * F * sizeof(float2), hipMemcpyDeviceToDevice, st));
+                if (taps->smooth) HIPCHK(hipMemcpyAsync(taps->smooth + g * F, smooth, nb * F * sizeof(float2), hipMemcpyDeviceToDevice, st));
+                if (taps->absres) HIPCHK(hipMemcpyAsync(taps->absres + g * N, absres, nb * N * sizeof(float), hipMemcpyDeviceToDevice, st));
+                if (taps->mflags) HIPCHK(hipMemcpyAsync(taps->mflags + g * N, mflags, nb * N, hipMemcpyDeviceToDevice, st));
+                if (taps->med) {
+                    HIPCHK(hipMemcpy2DAsync(taps->med + 2 * g, 2 * sizeof(double), med1, sizeof(double), sizeof(double), nb, hipMemcpyDeviceToDevice, st));
+                    HIPCHK(hipMemcpy2DAsync(taps->med + 2 * g + 1, 2 * sizeof(double), mad, sizeof(double), sizeof(double), nb, hipMemcpyDeviceToDevice, st));
+                }
+                if (taps->cnt) HIPCHK(hipMemcpyAsync(taps->cnt + g, cnt, nb * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
+            }
         }
     }
     return TRI_OK;
+}
+
+extern "C" int tri_uvcontsub_flagger(const void* vis_c64, const uint8_t* flags, uint8_t* out_flags,
+                                     int64_t n_cp, int64_t ntime, int64_t nchan,
+                                     int64_t major_cycles, int64_t or_original_from_cycle,
+                                     int64_t taylor_degrees, double sigma, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return uvcontsub_impl(vis_c64, flags, out_flags, n_cp, ntime, nchan, major_cycles, or_original_from_cycle, taylor_degrees,
+                          sigma, workspace, workspace_bytes, stream, nullptr);
+}
+
+// Test hook: as above, additionally taps the LAST major cycle's intermediates of every product (see UvTaps)
+extern "C" int tri_uvcontsub_flagger_debug(const void* vis_c64, const uint8_t* flags, uint8_t* out_flags,
+                                           int64_t n_cp, int64_t ntime, int64_t nchan,
+                                           int64_t major_cycles, int64_t or_original_from_cycle,
+                                           int64_t taylor_degrees, double sigma, void* workspace,
+                                           size_t workspace_bytes, void* stream, void* dbg_avg, void* dbg_smooth,
+                                           float* dbg_absres, uint8_t* dbg_mflags, double* dbg_med, uint32_t* dbg_cnt) {
+    UvTaps t{(float2*)dbg_avg, (float2*)dbg_smooth, dbg_absres, dbg_mflags, dbg_med, dbg_cnt};
+    return uvcontsub_impl(vis_c64, flags, out_flags, n_cp, ntime, nchan, major_cycles, or_original_from_cycle, taylor_degrees,
+                          sigma, workspace, workspace_bytes, stream, &t);
 }
 
 // ---------------------------------------------------------------------------
