@@ -6,8 +6,9 @@ intermediates of window 0 must equal the oracle's bit for bit, and the kernel lo
 log of the row's base setting exactly as the row says (`gone`, `new`, `present`).  One child with nothing set gives
 the default logs.  The union of all logs must contain every kernel KERNELS marks `flagger`.
 
-The cases are derived from the conditions of the launch functions in tricolour_amd.hip (radii: box_radius(sigma) =
-floor(sqrt(3 sigma^2 + 1) / 2); W windows, T times, F channels, G chunks):
+The cases are derived from the conditions of the route picks (pick_iteration, pick_bg_step, pick_freq_stage) and of the
+launch functions in tricolour_amd.hip (radii: box_radius(sigma) = floor(sqrt(3 sigma^2 + 1) / 2); W windows, T times,
+F channels, G chunks):
 
 tile        2 x 256 x 2688, G = 10: blocks of 269 x 256, (maxchunk - 1) T = 68608 >= 65536 -- K3t is the default; time
             radii 21 / 10 (k_boxt<32>, the all-register k_boxt<20>, the integer weight filter k_boxw), column panels
@@ -40,7 +41,7 @@ Route picks that depend on the shape alone, and who sits on either side:
   BOXX_MIN_R = 56: exact (60, 121) / filters (44)
   interpolation segments cdiv(L, 512) >= 2: blocks / tiny
   spectrum stage pipeline needs an even window count: blocks (2 windows, k_boxp_spec) / long_block (1, k_boxt_spec)
-  T % 16 == 0 (FT flags updated in place): blocks / unpacked; F % 64 == 0 (panels): blocks / odd_f
+  T % 16 == 0 (SpecOr::FtInPlace*: FT flags updated in place): blocks / unpacked; F % 64 == 0 (IterStep::panel): blocks / odd_f
   windows of 2^31 bytes or more (st_use_mask: L C 4 < 2^31; boxw_usable, launch_colfilter, launch_boxf, ksf_of,
         tf_native: n C 4 < 2^31; launch_median row4: RS max(R, panel_rows) 4 < 2^32; K3r: N 4 < 2^32): a window of
         2^29 samples = 4 GB of visibilities cannot be flagged in a test; only the lower side is run (every case)

@@ -189,7 +189,8 @@ struct Ws {
     uint8_t *iter, *flagsTF, *flagsFT, *bgfTF, *bgfFT, *tflTF, *fflFT, *fflTF, *comb, *dil;
     // Time-major residual as column panels, written by the final frequency stage (window stride T * Fa).  No memory of
     // its own: it lies over bgfTF | bgfFT | comb | dil, four byte images that are dead from the final pass's frequency
-    // stage until the combine / dilate pass on the route that uses it.
+    // stage until the combine / dilate pass where it is used (IterStep::fused_resid, so Finish::FusedDilate: ws.comb is
+    // never read and ws.dil is written after the last reader).
     float* residP;
     int *rowcnt, *colcnt;
     double* med;      // medians: max(Fa, T*G) per window
@@ -401,8 +402,9 @@ struct Run {
     // NaNs folded into the running flags; the time-axis filter masks by its own flags),
     // ws.dataFT their transpose, masked in place every iteration (the flags only grow)
     bool ampl_cached = false;
-    // the iteration's input flags in TF layout while ws.dataTF is unmasked (K4x masks its data row with them:
-    // data is zero where the iteration's _average_freq flagged it, flagging.py:858-870), else NULL
+    // the running flags (ws.iter: every iteration's input flags, in TF layout when nothing is averaged) while ws.dataTF is
+    // unmasked (K4x masks its data row with them: data is zero where the iteration's _average_freq flagged it,
+    // flagging.py:858-870), else NULL.  Set once per process_windows() call, beside ampl_cached.
     const uint8_t* data_mask = nullptr;
     size_t data_mask_ws = 0;
 };
@@ -906,9 +908,6 @@ bool st_use_pipe(const StWin& sw) {
     static const bool off = is1(getenv("TRI_ST_NO_PIPE"));
     return !off && sw.nw >= 1 && sw.nw <= 8 && stp_lds_bytes(sw) <= 160 * 1024;
 }
-
-// TRI_ST_NO_PANEL=1: the time-axis SumThreshold and whoever shares its images read plain rows, never column panels (A/B runs)
-static bool st_no_panel() { static const bool off = is1(getenv("TRI_ST_NO_PANEL")); return off; }
 
 // The SumThreshold kernels (kernels_sumthreshold.hpp): k_colst_dyn (any windows), k_colst_fused (register cascade),
 // k_colst_mask (lane-mask cascade) on rows or on 64-column panels, k_colst_pipe (up to eight windows, K7p)
@@ -1779,233 +1778,322 @@ int background2d(const Run& r, bool flagsFT_current, float* residP = nullptr, bo
                          st.wrote_panel ? residP : nullptr, N);
 }
 
-// One major iteration (_get_flags_impl, flagging.py:745-781) for a batch.
-template <int VD>
-int run_iteration(Run& r, const void* vis, uint8_t* iter_flags, uint8_t* out_flags, bool update_iter, bool tap) {
-    const Plan& pl = r.pl;
-    const Ws& ws = r.ws;
-    const tri_params* p = r.p;
-    int T = (int)pl.T, F = (int)pl.F, Fa = (int)pl.Fa, G = (int)pl.G;
-    int64_t W = r.Wb;
-    int Wn = (int)W;
-    size_t N = (size_t)T * Fa, NF = (size_t)T * F;
-    size_t wsB = (size_t)pl.PF * T;
-    int rc;
+// ---- the routes of one major iteration, picked once per process_windows() call (pick_iteration) and then only switched on -------------
 
-    // flagging.py:756  _average_freq
-    static const bool no_fused_begin = is1(getenv("TRI_NO_FUSED_BEGIN"));
-    const bool fused_begin = r.ampl_cached && !no_fused_begin && T % 4 == 0 && Fa % 4 == 0 && N % 4 == 0 &&
-                             ((uintptr_t)iter_flags % 4 == 0);
-    if (fused_begin) {
-        // flagsTF = running flags (NaNs already folded in), flagsFT = their transpose,
-        // cached FT amplitudes masked -- one pass over the flags
-        dim3 gridw((unsigned)cdiv(Fa, 64), (unsigned)cdiv(T, 128), (unsigned)W);
-        hipLaunchKernelGGL((k_transpose_u8w<true, true>), gridw, dim3(256), 0, r.st, iter_flags, ws.flagsFT, ws.flagsTF, ws.dataFT,
-                           T, Fa, N, N, N, N);
-        LAUNCHCHK();
-    } else if (r.ampl_cached) {
-        // amplitudes (both layouts) were made once for the batch; this iteration's
-        // flags = running flags (NaNs already folded in)
-        rc = launch_u8<0>(r, iter_flags, ws.flagsTF, N, N, N, W);
-        if (rc) return rc;
-    } else {
-        if (pl.vec)
-            hipLaunchKernelGGL(k_prepare4<VD>, dim3((unsigned)cdiv(N * (size_t)W / 4, 256)), dim3(256), 0, r.st, vis, iter_flags, ws.dataTF, ws.flagsTF, N * (size_t)W / 4);
-        else
-            hipLaunchKernelGGL(k_prepare<VD>, grid1(N, W), dim3(256), 0, r.st, vis, iter_flags, ws.dataTF, ws.flagsTF, T, F, Fa, (int)pl.avg);
-        LAUNCHCHK();
-        rc = launch_transpose<float>(r, ws.dataTF, ws.dataFT, T, Fa, N, N, W);
-        if (rc) return rc;
-    }
-    if (!fused_begin) {
-        rc = launch_transpose<uint8_t>(r, ws.flagsTF, ws.flagsFT, T, Fa, N, N, W);
-        if (rc) return rc;
-    }
-    if (r.ampl_cached && !fused_begin) {
-        hipLaunchKernelGGL(k_zero_flagged4, grid1(N / 4, W), dim3(256), 0, r.st, ws.flagsFT, ws.dataFT, N / 4, N, N);
-        LAUNCHCHK();
-    }
-
-    // flagging.py:944  _time_median: rows of the FT layout are contiguous in time
-    auto time_medians = [&](const float* dataFT, size_t ws_data) {
-        MedianJob j;
-        j.data = dataFT; j.flags = ws.flagsFT; j.med = ws.med; j.WSd = ws_data; j.WSf = N; j.RS = (size_t)T;
-        j.seg_start = ws.segT_start; j.seg_len = ws.segT_len; j.R = Fa; j.G = 1; j.W = W; j.max_len = pl.T;
-        j.rows_aligned = T % 4 == 0; j.segs_aligned = true;
-        return launch_median(r, j);
-    };
-    rc = time_medians(ws.dataFT, N);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_spec_from_med, dim3((unsigned)cdiv((size_t)Fa * Wn, 256)), dim3(256), 0, r.st, ws.med, ws.sdata, ws.sflags, Fa, Wn);
-    LAUNCHCHK();
-
-    // flagging.py:945-952  spectrum background, subtraction, SumThreshold
-    rc = spectrum_background(r);
-    if (rc) return rc;
-    size_t nS = (size_t)Fa * Wn;
-    rc = launch_sub(r, ws.sdata, ws.so, ws.sres, nS, 0, 0, 0, 1);
-    if (rc) return rc;
-    rc = spectrum_medians(r, ws.sres, ws.sflags);
-    if (rc) return rc;
-    rc = launch_colst(r, pl.swF, ws.sres, ws.smed, ws.sout, ws.d_chunk_ends, Fa, Wn, G, 0, 0, 1);
-    if (rc) return rc;
-
-    // flagging.py:954  flags |= spec_flags
-    // With whole 16-byte groups along time the FT copy of the flags is updated
-    // in place (rows of flagged channels only) instead of being transposed again.
-    static const bool no_ft_or = is1(getenv("TRI_NO_FT_SPEC_OR"));
-    const bool ft_current = pl.vec && !no_ft_or && T % 16 == 0;
-    // ... and when the background works from the FT image alone (packed flags), the TF image is
-    // not read before the time flags are OR-ed in: both updates then share one pass.
-    const bool defer_tf = ft_current && bg_flags_packed(T, N);
-    if (pl.vec) {
-        hipLaunchKernelGGL(k_spec_rows, dim3((unsigned)cdiv(nS, 256)), dim3(256), 0, r.st, ws.sout, ws.srows, Fa, Wn);
-        if (!defer_tf)
-            hipLaunchKernelGGL(k_or_spec16, grid1(N / 16, W), dim3(256), 0, r.st, ws.flagsTF, ws.srows, T, Fa / 16);
-        if (ft_current)
-            hipLaunchKernelGGL(k_or_spec_ft16, grid1(N / 16, W), dim3(256), 0, r.st, ws.flagsFT, ws.srows, T / 16, Fa);
-    } else {
-        hipLaunchKernelGGL(k_or_spec, grid1(N, W), dim3(256), 0, r.st, ws.flagsTF, ws.sout, T, Fa, Wn);
-    }
-    LAUNCHCHK();
-
-    // flagging.py:957-962  2-D background (FT layout, ws.Bo), then the residual
-    // (K4x masks rows of the unmasked TF amplitudes with the iteration's input flags: same layout when nothing is averaged)
-    r.data_mask = (r.ampl_cached && Fa == F) ? iter_flags : nullptr;
-    r.data_mask_ws = N;
+enum class Begin {
+    FusedCached,      // cached amplitudes: flagsTF, flagsFT and the masked FT amplitudes in one pass over the running flags
+    Cached,           // cached amplitudes: the running flags copied, transposed, then k_zero_flagged4 on the FT amplitudes
+    Prepare4,         // k_prepare4 (16-byte loads) every iteration, then both transposes
+    Prepare           // k_prepare (any shape, channel averaging), then both transposes
+};
+enum class SpecOr {
+    Scalar,           // k_or_spec into the TF flags; the FT flags are transposed again before the time medians of the residual
+    Rows16,           // k_or_spec16 into the TF flags; the FT flags are transposed again
+    FtInPlace,        // ... and k_or_spec_ft16 updates the FT flags where they lie (rows of flagged channels): no second transpose
+    FtInPlaceDeferTf  // FT in place only: with packed background flags nobody reads the TF flags before the time flags are OR-ed in too
+};
+enum class ChunkFlags {
+    ExtraSources,     // the wave medians take flagsTF, the time flags and the spectral rows as they are: no pass writes the union
+    OrMore16,         // k_or_spec_more16: the deferred spectral rows and the time flags into flagsTF in one pass
+    OrBytes           // launch_u8<1>: the time flags into flagsTF
+};
+enum class Finish {
+    FusedDilate,      // k_combine_dilate16: both smearings in one pass, no intermediate image
+    Combine16Dilate,  // k_combine16, then k_unaverage16<-1, 3>
+    Combine16,        // k_combine16, then k_unaverage (any frequency extents)
+    Combine           // k_combine, then k_unaverage (any shape, channel averaging)
+};
+enum class FinalKernel {
+    NanMask16,        // k_final16, isnan(|vis|) from the cached amplitudes' bit mask: half the bytes of the complex visibilities
+    Vis16,            // k_final16 on the visibilities
+    Scalar            // k_final
+};
+struct IterStep {
+    Begin begin; SpecOr spec_or; ChunkFlags chunk_flags; Finish finish; FinalKernel final_kernel;
     // Column panels for the time-axis SumThreshold (round 4): the TF residual and the time flags as [Fa / 64][T][64], so the
     // column kernel's row walk is one linear stream.  Who else touches the two images reads panels too: the frequency-axis MAD
-    // (wave medians over row segments: an aligned group of four channels is contiguous either way) and the fused combine /
-    // dilate pass.  Only on the route where exactly those kernels run (TRI_ST_NO_PANEL=1: plain rows everywhere).
+    // (ChunkFlags::ExtraSources; an aligned group of four channels is contiguous either way) and Finish::FusedDilate.
+    bool panel;
+    bool fused_resid;       // panel, and the background's final frequency stage is asked to write the panel residual itself
+    int lo, hi, flo, fhi;   // smearing extents along time / frequency
+    bool ft_current() const { return spec_or == SpecOr::FtInPlace || spec_or == SpecOr::FtInPlaceDeferTf; }
+};
+
+// smearing by e samples reaches [-(e // 2), e - e // 2), where // is Python's floor division
+static void smear_extents(int64_t e, int* lo, int* hi) {
+    const int64_t half = e >= 0 ? e / 2 : -((-e + 1) / 2);
+    *lo = (int)-half; *hi = (int)(-half + e);
+}
+// TRI_ST_NO_PANEL=1: the time-axis SumThreshold and whoever shares its images read plain rows, never column panels (A/B runs)
+static bool st_no_panel() { static const bool off = is1(getenv("TRI_ST_NO_PANEL")); return off; }
+
+// Launches nothing.  Reads the plan, the parameters, r.ampl_cached and the alignment of the running flags (r.ws.iter): all
+// constant over the batches and major iterations of a process_windows() call.
+static IterStep pick_iteration(const Run& r) {
+    const Plan& pl = r.pl;
+    const int T = (int)pl.T, F = (int)pl.F, Fa = (int)pl.Fa;
+    const size_t N = (size_t)T * Fa;
+    static const bool no_fused_begin = is1(getenv("TRI_NO_FUSED_BEGIN"));
+    static const bool no_ft_or = is1(getenv("TRI_NO_FT_SPEC_OR"));
     static const bool no_fused_or = is1(getenv("TRI_NO_FUSED_OR"));
     static const bool no_fused_dilate = is1(getenv("TRI_NO_FUSED_DILATE"));
-    const bool panel_t = !st_no_panel() && defer_tf && !no_fused_or && !no_fused_dilate && Fa % 64 == 0 && Fa == F &&
-                         median_takes_extra_flags(pl.maxchunk + 3) && st_use_fused(pl.swT) && st_use_mask(T, Fa) &&
-                         [&] { int64_t e = p->freq_extend; int64_t h = e >= 0 ? e / 2 : -((-e + 1) / 2); return -h == -1 && -h + e == 2; }();
-    // The final frequency stage of the background holds every residual value in a register: where it is the register-ring
-    // kernel (K4r) it writes the panel image itself and the transpose below is not run.  The image lies over byte images that
-    // are dead by then (ws.residP, see carve()): this route never reads ws.comb, and ws.dil is written after the last reader.
-    // Measured on the 252-baseline slab the third store stream costs that kernel as much as the transpose it saves (DESIGN.md
-    // section 4), so the transpose stays the default route: TRI_NO_FUSED_RESID_TF=0 switches the fused write on, unset or 1
-    // keeps the transpose (A/B runs, tests).
+    // Where the background's final frequency stage is the register-ring kernel (K4r) it can write the panel residual itself,
+    // over byte images that are dead by then (ws.residP, see carve()).  Measured on the 252-baseline slab the third store
+    // stream costs that kernel as much as the transpose it saves, so the transpose stays the default:
+    // TRI_NO_FUSED_RESID_TF=0 switches the fused write on, unset or 1 keeps the transpose (A/B runs, tests).
     static const bool no_fused_resid = [] { const char* e = getenv("TRI_NO_FUSED_RESID_TF"); return !(e && e[0] == '0'); }();
+    IterStep s;
+    smear_extents(r.p->time_extend, &s.lo, &s.hi);
+    smear_extents(r.p->freq_extend, &s.flo, &s.fhi);
+    if (!r.ampl_cached) s.begin = pl.vec ? Begin::Prepare4 : Begin::Prepare;
+    else s.begin = (!no_fused_begin && T % 4 == 0 && Fa % 4 == 0 && N % 4 == 0 && (uintptr_t)r.ws.iter % 4 == 0) ? Begin::FusedCached : Begin::Cached;
+    // (in place: whole 16-byte groups along time)
+    if (!pl.vec) s.spec_or = SpecOr::Scalar;
+    else if (no_ft_or || T % 16 != 0) s.spec_or = SpecOr::Rows16;
+    else s.spec_or = bg_flags_packed(T, N) ? SpecOr::FtInPlaceDeferTf : SpecOr::FtInPlace;
+    // (the union is read by the chunk medians only: the next major iteration rebuilds the TF flags)
+    const bool defer_tf = s.spec_or == SpecOr::FtInPlaceDeferTf;
+    if (defer_tf && !no_fused_or && median_takes_extra_flags(pl.maxchunk) && Fa % 4 == 0) s.chunk_flags = ChunkFlags::ExtraSources;
+    else s.chunk_flags = defer_tf ? ChunkFlags::OrMore16 : ChunkFlags::OrBytes;
+    if (!pl.vec) s.finish = Finish::Combine;
+    else if (s.flo != -1 || s.fhi != 2) s.finish = Finish::Combine16;
+    else s.finish = no_fused_dilate ? Finish::Combine16Dilate : Finish::FusedDilate;
+    s.final_kernel = !pl.vec ? FinalKernel::Scalar : r.ampl_cached ? FinalKernel::NanMask16 : FinalKernel::Vis16;
+    // only where exactly the panel-reading kernels run (TRI_ST_NO_PANEL=1: plain rows everywhere), so that no route that reads
+    // rows can meet a panel image
+    s.panel = !st_no_panel() && s.chunk_flags == ChunkFlags::ExtraSources && s.finish == Finish::FusedDilate && Fa % 64 == 0 && Fa == F &&
+              median_takes_extra_flags(pl.maxchunk + 3) && st_use_fused(pl.swT) && st_use_mask(T, Fa);
+    s.fused_resid = s.panel && !no_fused_resid;
+    return s;
+}
+
+// The two launches of an iteration that read the visibilities: the only ones whose kernels depend on the dtype VD.
+template <int VD>
+static int launch_prepare(const Run& r, const IterStep& s, const void* vis) {
+    const Plan& pl = r.pl;
+    const Ws& ws = r.ws;
+    const size_t N = (size_t)pl.T * pl.Fa, W = (size_t)r.Wb;
+    if (s.begin == Begin::Prepare4)
+        hipLaunchKernelGGL(k_prepare4<VD>, dim3((unsigned)cdiv(N * W / 4, 256)), dim3(256), 0, r.st, vis, ws.iter, ws.dataTF, ws.flagsTF, N * W / 4);
+    else
+        hipLaunchKernelGGL(k_prepare<VD>, grid1(N, W), dim3(256), 0, r.st, vis, ws.iter, ws.dataTF, ws.flagsTF, (int)pl.T, (int)pl.F, (int)pl.Fa, (int)pl.avg);
+    LAUNCHCHK();
+    return TRI_OK;
+}
+// flagging.py:910-918 whole-row / whole-column rules; :777-781 NaN OR; :1193
+template <int VD>
+static int launch_final(const Run& r, const IterStep& s, const void* vis, uint8_t* out_flags, bool update_iter) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, F = (int)r.pl.F, upd = update_iter ? 1 : 0;
+    const size_t NF = (size_t)T * F, W = (size_t)r.Wb;
+    const double row_limit = r.p->flag_all_freq_frac * (double)F, col_limit = (double)T * r.p->flag_all_time_frac;
+    if (s.final_kernel == FinalKernel::NanMask16)
+        hipLaunchKernelGGL(k_final16<TRI_VIS_NANMASK>, grid1(NF / 16, W), dim3(256), 0, r.st, ws.dil, ws.rowcnt, ws.colcnt, (const void*)ws.nanmask, out_flags, ws.iter, T, F / 16, row_limit, col_limit, upd);
+    else if (s.final_kernel == FinalKernel::Vis16)
+        hipLaunchKernelGGL(k_final16<VD>, grid1(NF / 16, W), dim3(256), 0, r.st, ws.dil, ws.rowcnt, ws.colcnt, vis, out_flags, ws.iter, T, F / 16, row_limit, col_limit, upd);
+    else
+        hipLaunchKernelGGL(k_final<VD>, grid1(NF, W), dim3(256), 0, r.st, ws.dil, ws.rowcnt, ws.colcnt, vis, out_flags, ws.iter, T, F, row_limit, col_limit, upd);
+    LAUNCHCHK();
+    return TRI_OK;
+}
+// (float32 amplitudes unless the dtype is one of the other two)
+#define BY_VIS_DTYPE(FN, ...) \
+    (vis_dtype == TRI_VIS_C64 ? FN<TRI_VIS_C64>(__VA_ARGS__) : vis_dtype == TRI_VIS_F64 ? FN<TRI_VIS_F64>(__VA_ARGS__) : FN<TRI_VIS_F32>(__VA_ARGS__))
+
+// flagging.py:756  _average_freq: the amplitudes and the iteration's flags, each in the TF and in the FT layout
+static int iter_begin(const Run& r, const IterStep& s, const void* vis, int vis_dtype) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, Fa = (int)r.pl.Fa;
+    const size_t N = (size_t)T * Fa;
+    const int64_t W = r.Wb;
+    int rc = TRI_OK;
+    switch (s.begin) {
+        case Begin::FusedCached:
+            hipLaunchKernelGGL((k_transpose_u8w<true, true>), dim3((unsigned)cdiv(Fa, 64), (unsigned)cdiv(T, 128), (unsigned)W), dim3(256), 0, r.st,
+                               ws.iter, ws.flagsFT, ws.flagsTF, ws.dataFT, T, Fa, N, N, N, N);
+            break;
+        case Begin::Cached:
+            // amplitudes (both layouts) were made once for the batch; this iteration's flags = running flags (NaNs already folded in)
+            rc = launch_u8<0>(r, ws.iter, ws.flagsTF, N, N, N, W);
+            if (!rc) rc = launch_transpose<uint8_t>(r, ws.flagsTF, ws.flagsFT, T, Fa, N, N, W);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_zero_flagged4, grid1(N / 4, W), dim3(256), 0, r.st, ws.flagsFT, ws.dataFT, N / 4, N, N);
+            break;
+        case Begin::Prepare4:
+        case Begin::Prepare:
+            rc = BY_VIS_DTYPE(launch_prepare, r, s, vis);
+            if (!rc) rc = launch_transpose<float>(r, ws.dataTF, ws.dataFT, T, Fa, N, N, W);
+            if (!rc) rc = launch_transpose<uint8_t>(r, ws.flagsTF, ws.flagsFT, T, Fa, N, N, W);
+            return rc;
+    }
+    LAUNCHCHK();
+    return TRI_OK;
+}
+
+// flagging.py:944  _time_median: rows of the FT layout are contiguous in time
+static int time_medians(const Run& r, const float* dataFT, size_t ws_data) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, Fa = (int)r.pl.Fa;
+    MedianJob j;
+    j.data = dataFT; j.flags = ws.flagsFT; j.med = ws.med; j.WSd = ws_data; j.WSf = (size_t)T * Fa; j.RS = (size_t)T;
+    j.seg_start = ws.segT_start; j.seg_len = ws.segT_len; j.R = Fa; j.G = 1; j.W = r.Wb; j.max_len = r.pl.T;
+    j.rows_aligned = T % 4 == 0; j.segs_aligned = true;
+    return launch_median(r, j);
+}
+
+// flagging.py:944-954  the spectrum of time medians, its background, SumThreshold on the residual, flags |= spec_flags
+static int iter_spectrum(const Run& r, const IterStep& s) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, Fa = (int)r.pl.Fa, Wn = (int)r.Wb;
+    const size_t N = (size_t)T * Fa, nS = (size_t)Fa * Wn;
+    const int64_t W = r.Wb;
+    int rc = time_medians(r, ws.dataFT, N);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_spec_from_med, dim3((unsigned)cdiv(nS, 256)), dim3(256), 0, r.st, ws.med, ws.sdata, ws.sflags, Fa, Wn);
+    LAUNCHCHK();
+    rc = spectrum_background(r);
+    if (!rc) rc = launch_sub(r, ws.sdata, ws.so, ws.sres, nS, 0, 0, 0, 1);
+    if (!rc) rc = spectrum_medians(r, ws.sres, ws.sflags);
+    if (!rc) rc = launch_colst(r, r.pl.swF, ws.sres, ws.smed, ws.sout, ws.d_chunk_ends, Fa, Wn, (int)r.pl.G, 0, 0, 1);
+    if (rc) return rc;
+    if (s.spec_or != SpecOr::Scalar)
+        hipLaunchKernelGGL(k_spec_rows, dim3((unsigned)cdiv(nS, 256)), dim3(256), 0, r.st, ws.sout, ws.srows, Fa, Wn);
+    switch (s.spec_or) {
+        case SpecOr::Scalar:
+            hipLaunchKernelGGL(k_or_spec, grid1(N, W), dim3(256), 0, r.st, ws.flagsTF, ws.sout, T, Fa, Wn);
+            break;
+        case SpecOr::Rows16:
+            hipLaunchKernelGGL(k_or_spec16, grid1(N / 16, W), dim3(256), 0, r.st, ws.flagsTF, ws.srows, T, Fa / 16);
+            break;
+        case SpecOr::FtInPlace:
+            hipLaunchKernelGGL(k_or_spec16, grid1(N / 16, W), dim3(256), 0, r.st, ws.flagsTF, ws.srows, T, Fa / 16);
+            hipLaunchKernelGGL(k_or_spec_ft16, grid1(N / 16, W), dim3(256), 0, r.st, ws.flagsFT, ws.srows, T / 16, Fa);
+            break;
+        case SpecOr::FtInPlaceDeferTf:
+            hipLaunchKernelGGL(k_or_spec_ft16, grid1(N / 16, W), dim3(256), 0, r.st, ws.flagsFT, ws.srows, T / 16, Fa);
+            break;
+    }
+    LAUNCHCHK();
+    return TRI_OK;
+}
+
+// flagging.py:957-962  2-D background (FT layout, ws.Bo); the residual data - background was written by its final masked
+// division (and redone by the interpolation pass on repaired lines) into ws.Bw, window stride PF * T.  *residTF: the same
+// in the TF layout, window stride N: ws.residP where the final frequency stage wrote the panels itself, else a transpose
+// into ws.Aw (the time-axis scratch is free again).
+static int iter_residual(const Run& r, const IterStep& s, const float** residTF) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, Fa = (int)r.pl.Fa;
     bool wrote_panel = false;
-    rc = background2d(r, ft_current, (panel_t && !no_fused_resid) ? ws.residP : nullptr, &wrote_panel);
-    if (rc) return rc;
-    if (tap && r.dbg) {
-        HIPCHK(hipMemcpyAsync(r.dbg->f32 + Fa, ws.Bo, N * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-    }
-    // the residual data - background was written by the final masked division
-    // (and redone by the interpolation pass on repaired lines) into ws.Bw
-    float* residFT = ws.Bw;   // window stride wsB
-    float* residTF = wrote_panel ? ws.residP : ws.Aw;   // window stride N (ws.Aw: the time-axis scratch is free again)
-    if (!wrote_panel) {
-        rc = launch_transpose<float>(r, residFT, residTF, Fa, T, wsB, N, W, 0.0f, panel_t);
-        if (rc) return rc;
-    }
+    const int rc = background2d(r, s.ft_current(), s.fused_resid ? ws.residP : nullptr, &wrote_panel);
+    *residTF = wrote_panel ? ws.residP : ws.Aw;
+    if (rc || wrote_panel) return rc;
+    return launch_transpose<float>(r, ws.Bw, ws.Aw, Fa, T, (size_t)r.pl.PF * T, (size_t)T * Fa, r.Wb, 0.0f, s.panel);
+}
 
-    // flagging.py:964  SumThreshold along time.  MAD per channel over time =
-    // contiguous rows of the FT layout; flags = input | spectral flags.
-    if (!ft_current) {
-        rc = launch_transpose<uint8_t>(r, ws.flagsTF, ws.flagsFT, T, Fa, N, N, W);
-        if (rc) return rc;
-    }
-    rc = time_medians(residFT, wsB);
+// flagging.py:964-969  SumThreshold along time, flags |= time_flags, SumThreshold along frequency
+static int iter_sumthreshold(const Run& r, const IterStep& s, const float* residTF) {
+    const Plan& pl = r.pl;
+    const Ws& ws = r.ws;
+    const int T = (int)pl.T, Fa = (int)pl.Fa, G = (int)pl.G;
+    const size_t N = (size_t)T * Fa, wsB = (size_t)pl.PF * T;
+    const int64_t W = r.Wb;
+    // MAD per channel over time = contiguous rows of the FT layout; flags = input | spectral flags
+    int rc = s.ft_current() ? TRI_OK : launch_transpose<uint8_t>(r, ws.flagsTF, ws.flagsFT, T, Fa, N, N, W);
+    if (!rc) rc = time_medians(r, ws.Bw, wsB);
+    if (!rc) rc = launch_colst(r, pl.swT, residTF, ws.med, ws.tflTF, ws.d_tends, T, Fa, 1, N, N, W, s.panel);
     if (rc) return rc;
-    rc = launch_colst(r, pl.swT, residTF, ws.med, ws.tflTF, ws.d_tends, T, Fa, 1, N, N, W, panel_t);
-    if (rc) return rc;
-
-    // flagging.py:967-969  flags |= time_flags; SumThreshold along frequency.
-    // MAD per (time, chunk) = contiguous row segments of the TF layout.
-    // (the union is read by this MAD only -- the next major iteration rebuilds the TF flags -- so when the chunk medians are
-    //  wave medians they take the three sources as they are and no pass writes the union; TRI_NO_FUSED_OR=1: the pass)
+    // MAD per (time, chunk) = contiguous row segments of the TF layout; flags = input | spectral | time flags
     MedianJob cj;
     cj.data = residTF; cj.flags = ws.flagsTF; cj.med = ws.med; cj.WSd = cj.WSf = N; cj.RS = (size_t)Fa;
     cj.seg_start = ws.segC_start; cj.seg_len = ws.segC_len; cj.R = T; cj.G = G; cj.W = W; cj.max_len = pl.maxchunk;
     cj.rows_aligned = Fa % 4 == 0;
-    if (defer_tf && !no_fused_or && median_takes_extra_flags(pl.maxchunk) && Fa % 4 == 0) {
-        cj.flags2 = ws.tflTF; cj.colflags = ws.srows; cj.WScol = (size_t)Fa; cj.panel_rows = panel_t ? T : 0;
-        rc = launch_median(r, cj);
-        if (rc) return rc;
-    } else {
-        if (panel_t) return set_err(TRI_EUNSUPPORTED, "internal: panel images on a route that reads rows");
-        if (defer_tf) {
+    switch (s.chunk_flags) {
+        case ChunkFlags::ExtraSources:
+            cj.flags2 = ws.tflTF; cj.colflags = ws.srows; cj.WScol = (size_t)Fa; cj.panel_rows = s.panel ? T : 0;
+            break;
+        case ChunkFlags::OrMore16:
             hipLaunchKernelGGL(k_or_spec_more16, grid1(N / 16, W), dim3(256), 0, r.st, ws.flagsTF, ws.srows, ws.tflTF, T, Fa / 16);
             LAUNCHCHK();
-        } else {
+            break;
+        case ChunkFlags::OrBytes:
             rc = launch_u8<1>(r, ws.tflTF, ws.flagsTF, N, N, N, W);
-            if (rc) return rc;
-        }
-        rc = launch_median(r, cj);
-        if (rc) return rc;
+            break;
     }
-    rc = launch_colst(r, pl.swF, residFT, ws.med, ws.fflFT, ws.d_chunk_ends, Fa, T, G, wsB, N, W);
-    if (rc) return rc;
-    rc = launch_transpose<uint8_t>(r, ws.fflFT, ws.fflTF, Fa, T, N, N, W);
-    if (rc) return rc;
+    if (!rc) rc = launch_median(r, cj);
+    if (!rc) rc = launch_colst(r, pl.swF, ws.Bw, ws.med, ws.fflFT, ws.d_chunk_ends, Fa, T, G, wsB, N, W);
+    if (!rc) rc = launch_transpose<uint8_t>(r, ws.fflFT, ws.fflTF, Fa, T, N, N, W);
+    return rc;
+}
 
-    if (tap && r.dbg) {
-        hipLaunchKernelGGL(k_gather_col_f32, dim3((unsigned)cdiv(Fa, 256)), dim3(256), 0, r.st, ws.sres, r.dbg->f32, Fa, Wn, 0);
-        hipLaunchKernelGGL(k_gather_col_u8, dim3((unsigned)cdiv(Fa, 256)), dim3(256), 0, r.st, ws.sout, r.dbg->u8, Fa, Wn, 0);
-        LAUNCHCHK();
-        if (panel_t) {
-            hipLaunchKernelGGL(k_unpanel<float>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, r.st, (const float*)residTF, r.dbg->f32 + Fa + N, T, Fa);
-            hipLaunchKernelGGL(k_unpanel<uint8_t>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, r.st, (const uint8_t*)ws.tflTF, r.dbg->u8 + Fa, T, Fa);
-            LAUNCHCHK();
-        } else {
-            HIPCHK(hipMemcpyAsync(r.dbg->f32 + Fa + N, residTF, N * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-            HIPCHK(hipMemcpyAsync(r.dbg->u8 + Fa, ws.tflTF, N, hipMemcpyDeviceToDevice, r.st));
-        }
-        HIPCHK(hipMemcpyAsync(r.dbg->u8 + Fa + N, ws.fflTF, N, hipMemcpyDeviceToDevice, r.st));
+// the six intermediates of window 0 (tests), laid out as Debug says
+static int iter_taps(const Run& r, const IterStep& s, const float* residTF) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, Fa = (int)r.pl.Fa, Wn = (int)r.Wb;
+    const size_t N = (size_t)T * Fa;
+    const Debug& d = *r.dbg;
+    hipLaunchKernelGGL(k_gather_col_f32, dim3((unsigned)cdiv(Fa, 256)), dim3(256), 0, r.st, ws.sres, d.f32, Fa, Wn, 0);
+    hipLaunchKernelGGL(k_gather_col_u8, dim3((unsigned)cdiv(Fa, 256)), dim3(256), 0, r.st, ws.sout, d.u8, Fa, Wn, 0);
+    if (s.panel) {
+        hipLaunchKernelGGL(k_unpanel<float>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, r.st, residTF, d.f32 + Fa + N, T, Fa);
+        hipLaunchKernelGGL(k_unpanel<uint8_t>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, r.st, (const uint8_t*)ws.tflTF, d.u8 + Fa, T, Fa);
+    } else {
+        HIPCHK(hipMemcpyAsync(d.f32 + Fa + N, residTF, N * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+        HIPCHK(hipMemcpyAsync(d.u8 + Fa, ws.tflTF, N, hipMemcpyDeviceToDevice, r.st));
     }
-
-    // flagging.py:973  _combine_flags (time smearing), flagging.py:975  _unaverage_freq
-    // (replication, frequency smearing, counts)
-    {
-        int64_t e = p->time_extend;
-        int64_t half = e >= 0 ? e / 2 : -((-e + 1) / 2);   // Python floor division
-        int lo = (int)-half, hi = (int)(-half + e);
-        int64_t ef = p->freq_extend;
-        int64_t halff = ef >= 0 ? ef / 2 : -((-ef + 1) / 2);
-        int flo = (int)-halff, fhi = (int)(-halff + ef);
-        HIPCHK(hipMemsetAsync(ws.rowcnt, 0, (size_t)W * T * sizeof(int), r.st));
-        if (pl.vec && flo == -1 && fhi == 2 && !no_fused_dilate) {
-            // both smearings in one pass, no intermediate image
-            dim3 grid((unsigned)cdiv(F / 16, 64), (unsigned)T, (unsigned)W);
-            if (panel_t) hipLaunchKernelGGL(k_combine_dilate16<true>, grid, dim3(64), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.dil, ws.rowcnt, T, F / 16, lo, hi);
-            else hipLaunchKernelGGL(k_combine_dilate16<false>, grid, dim3(64), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.dil, ws.rowcnt, T, F / 16, lo, hi);
-            hipLaunchKernelGGL(k_colcount, grid1(F / 4, W), dim3(256), 0, r.st, ws.dil, ws.colcnt, T, F / 4);
-        } else {
-            if (panel_t) return set_err(TRI_EUNSUPPORTED, "internal: panel images on a route that reads rows");
-            if (pl.vec)
-                hipLaunchKernelGGL(k_combine16, grid1(N / 16, W), dim3(256), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.comb, T, Fa / 16, lo, hi);
-            else
-                hipLaunchKernelGGL(k_combine, grid1(N, W), dim3(256), 0, r.st, ws.sout, ws.tflTF, ws.fflTF, ws.comb, T, Fa, Wn, lo, hi);
-            LAUNCHCHK();
-            if (pl.vec && flo == -1 && fhi == 2) {
-                dim3 grid((unsigned)cdiv(F / 16, 64), (unsigned)T, (unsigned)W);
-                hipLaunchKernelGGL((k_unaverage16<-1, 3>), grid, dim3(64), 0, r.st, ws.comb, ws.dil, ws.rowcnt, T, F / 16);
-                hipLaunchKernelGGL(k_colcount, grid1(F / 4, W), dim3(256), 0, r.st, ws.dil, ws.colcnt, T, F / 4);
-            } else {
-                HIPCHK(hipMemsetAsync(ws.colcnt, 0, (size_t)W * F * sizeof(int), r.st));
-                dim3 grid((unsigned)cdiv(F, 256), (unsigned)T, (unsigned)W);
-                hipLaunchKernelGGL(k_unaverage, grid, dim3(256), 0, r.st, ws.comb, ws.dil, ws.rowcnt, ws.colcnt, T, Fa, F, (int)pl.avg, flo, fhi);
-            }
-        }
-        LAUNCHCHK();
-    }
-    // flagging.py:910-918 whole-row / whole-column rules; :777-781 NaN OR; :1193
-    double row_limit = p->flag_all_freq_frac * (double)F;
-    double col_limit = (double)T * p->flag_all_time_frac;
-    if (pl.vec)
-        if (r.ampl_cached)   // isnan(|vis|) from the cached amplitudes: half the bytes of the complex visibilities
-            hipLaunchKernelGGL(k_final16<TRI_VIS_NANMASK>, grid1(NF / 16, W), dim3(256), 0, r.st, ws.dil, ws.rowcnt, ws.colcnt, (const void*)ws.nanmask, out_flags, iter_flags, T, F / 16, row_limit, col_limit, update_iter ? 1 : 0);
-        else
-            hipLaunchKernelGGL(k_final16<VD>, grid1(NF / 16, W), dim3(256), 0, r.st, ws.dil, ws.rowcnt, ws.colcnt, vis, out_flags, iter_flags, T, F / 16, row_limit, col_limit, update_iter ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_final<VD>, grid1(NF, W), dim3(256), 0, r.st, ws.dil, ws.rowcnt, ws.colcnt, vis, out_flags, iter_flags, T, F, row_limit, col_limit, update_iter ? 1 : 0);
     LAUNCHCHK();
+    HIPCHK(hipMemcpyAsync(d.f32 + Fa, ws.Bo, N * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+    HIPCHK(hipMemcpyAsync(d.u8 + Fa + N, ws.fflTF, N, hipMemcpyDeviceToDevice, r.st));
     return TRI_OK;
+}
+
+// flagging.py:973  _combine_flags (time smearing), flagging.py:975  _unaverage_freq (replication, frequency smearing,
+// counts), then the final kernel
+static int iter_finish(const Run& r, const IterStep& s, const void* vis, int vis_dtype, uint8_t* out_flags, bool update_iter) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, F = (int)r.pl.F, Fa = (int)r.pl.Fa, Wn = (int)r.Wb;
+    const size_t N = (size_t)T * Fa;
+    const int64_t W = r.Wb;
+    const dim3 grid16((unsigned)cdiv(F / 16, 64), (unsigned)T, (unsigned)W);
+    HIPCHK(hipMemsetAsync(ws.rowcnt, 0, (size_t)W * T * sizeof(int), r.st));
+    switch (s.finish) {
+        case Finish::FusedDilate:
+            if (s.panel) hipLaunchKernelGGL(k_combine_dilate16<true>, grid16, dim3(64), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.dil, ws.rowcnt, T, F / 16, s.lo, s.hi);
+            else hipLaunchKernelGGL(k_combine_dilate16<false>, grid16, dim3(64), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.dil, ws.rowcnt, T, F / 16, s.lo, s.hi);
+            hipLaunchKernelGGL(k_colcount, grid1(F / 4, W), dim3(256), 0, r.st, ws.dil, ws.colcnt, T, F / 4);
+            break;
+        case Finish::Combine16Dilate:
+            hipLaunchKernelGGL(k_combine16, grid1(N / 16, W), dim3(256), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.comb, T, Fa / 16, s.lo, s.hi);
+            hipLaunchKernelGGL((k_unaverage16<-1, 3>), grid16, dim3(64), 0, r.st, ws.comb, ws.dil, ws.rowcnt, T, F / 16);
+            hipLaunchKernelGGL(k_colcount, grid1(F / 4, W), dim3(256), 0, r.st, ws.dil, ws.colcnt, T, F / 4);
+            break;
+        case Finish::Combine16:
+        case Finish::Combine:
+            if (s.finish == Finish::Combine16)
+                hipLaunchKernelGGL(k_combine16, grid1(N / 16, W), dim3(256), 0, r.st, ws.srows, ws.tflTF, ws.fflTF, ws.comb, T, Fa / 16, s.lo, s.hi);
+            else
+                hipLaunchKernelGGL(k_combine, grid1(N, W), dim3(256), 0, r.st, ws.sout, ws.tflTF, ws.fflTF, ws.comb, T, Fa, Wn, s.lo, s.hi);
+            LAUNCHCHK();
+            HIPCHK(hipMemsetAsync(ws.colcnt, 0, (size_t)W * F * sizeof(int), r.st));
+            hipLaunchKernelGGL(k_unaverage, dim3((unsigned)cdiv(F, 256), (unsigned)T, (unsigned)W), dim3(256), 0, r.st, ws.comb, ws.dil, ws.rowcnt, ws.colcnt,
+                               T, Fa, F, (int)r.pl.avg, s.flo, s.fhi);
+            break;
+    }
+    LAUNCHCHK();
+    return BY_VIS_DTYPE(launch_final, r, s, vis, out_flags, update_iter);
+}
+#undef BY_VIS_DTYPE
+
+// One major iteration (_get_flags_impl, flagging.py:745-781) for a batch: the stages in the order of flagging.py:921-976.
+int run_iteration(const Run& r, const IterStep& s, const void* vis, int vis_dtype, uint8_t* out_flags, bool update_iter, bool tap) {
+    const float* residTF = nullptr;
+    int rc = iter_begin(r, s, vis, vis_dtype);
+    if (!rc) rc = iter_spectrum(r, s);
+    if (!rc) rc = iter_residual(r, s, &residTF);
+    if (!rc) rc = iter_sumthreshold(r, s, residTF);
+    if (!rc && tap && r.dbg) rc = iter_taps(r, s, residTF);
+    if (!rc) rc = iter_finish(r, s, vis, vis_dtype, out_flags, update_iter);
+    return rc;
 }
 
 // All batches of the windows [w_begin, w_end) on r.st with the workspace [wsp, wsp + ws_bytes).
@@ -2039,6 +2127,13 @@ int process_windows(Run& r, const void* vis, int vis_dtype, const uint8_t* flags
     }
     const size_t NF = (size_t)T * F;
     const size_t esz = (vis_dtype == TRI_VIS_C64 || vis_dtype == TRI_VIS_F64) ? 8 : 4;
+    // without channel averaging |vis| is the same in every major iteration:
+    // compute it once per batch, in both layouts (TRI_NO_AMPL_CACHE=1 recomputes it per iteration)
+    static const bool no_cache = is1(getenv("TRI_NO_AMPL_CACHE"));
+    r.ampl_cached = r.pl.vec && !no_cache && p->num_major_iterations > 0;
+    r.data_mask = (r.ampl_cached && r.pl.Fa == F) ? r.ws.iter : nullptr;
+    r.data_mask_ws = (size_t)T * r.pl.Fa;
+    const IterStep step = pick_iteration(r);
     int rc = TRI_OK;
     for (int64_t w0 = w_begin; w0 < w_end; w0 += Wb) {
         r.Wb = std::min(Wb, w_end - w0);
@@ -2047,10 +2142,6 @@ int process_windows(Run& r, const void* vis, int vis_dtype, const uint8_t* flags
         // flagging.py:1182  iter_flags = flags.copy()  (non-zero = flagged)
         rc = launch_u8<2>(r, flags + (size_t)w0 * NF, r.ws.iter, NF, NF, NF, r.Wb);
         if (rc) return rc;
-        // without channel averaging |vis| is the same in every major iteration:
-        // compute it once, in both layouts (TRI_NO_AMPL_CACHE=1 recomputes it per iteration)
-        static const bool no_cache = is1(getenv("TRI_NO_AMPL_CACHE"));
-        r.ampl_cached = r.pl.vec && !no_cache && p->num_major_iterations > 0;
         if (r.ampl_cached) {
             const size_t n4 = (size_t)r.Wb * NF / 4;
             if (vis_dtype == TRI_VIS_C64)
@@ -2064,9 +2155,7 @@ int process_windows(Run& r, const void* vis, int vis_dtype, const uint8_t* flags
         for (int64_t it = 0; it < p->num_major_iterations; it++) {
             bool last = it == p->num_major_iterations - 1;
             bool tap = last && tap_first && w0 == w_begin;
-            if (vis_dtype == TRI_VIS_C64) rc = run_iteration<TRI_VIS_C64>(r, vis_b, r.ws.iter, out_b, !last, tap);
-            else if (vis_dtype == TRI_VIS_F64) rc = run_iteration<TRI_VIS_F64>(r, vis_b, r.ws.iter, out_b, !last, tap);
-            else rc = run_iteration<TRI_VIS_F32>(r, vis_b, r.ws.iter, out_b, !last, tap);
+            rc = run_iteration(r, step, vis_b, vis_dtype, out_b, !last, tap);
             if (rc) return rc;
         }
     }
