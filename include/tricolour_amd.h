@@ -440,6 +440,30 @@ int tri_bench_sumthreshold(const float *data, const double *mad, uint8_t *out,
                            int repeats, float *ms_per_launch, void *stream);
 
 /*
+ * tri_test_sumthreshold: the same launch (one body with
+ * tri_bench_sumthreshold) over CHUNKED lines, as the flagger's frequency-axis
+ * pass runs it: chunk g of every column is the lines
+ * [chunk_ends[g], chunk_ends[g + 1]) with a threshold of its own, thresholded
+ * on its line padded by max(windows) - 1 positions on either side
+ * (flagging.py:610-681).  2 <= n_chunk_ends <= 256; the ends must not decrease
+ * and lie in [0, n_line] (TRI_EINVAL otherwise); empty chunks are legal.
+ *   mad  (n_win, n_col, n_chunk_ends - 1) float64
+ *   out  written inside [chunk_ends[0], chunk_ends[n_chunk_ends - 1]) only
+ * `variant` as above, except that 0 picks what the flagger would for these
+ * windows and chunks (the stage pipeline for a list it takes; the panel form
+ * of the lane-mask cascade with one chunk only), and that variant 5 with more
+ * than one chunk is TRI_EUNSUPPORTED: the flagger never pairs column panels
+ * with chunks.  Windows wider than n_line are not supported (the flagger's
+ * parameter preparation drops them before any kernel sees them).
+ */
+int tri_test_sumthreshold(const float *data, const double *mad, uint8_t *out,
+                          int64_t n_win, int64_t n_line, int64_t n_col,
+                          const int64_t *windows, int64_t n_windows,
+                          double outlier_nsigma, double rho, int variant,
+                          int repeats, float *ms_per_launch, void *stream,
+                          const int64_t *chunk_ends, int64_t n_chunk_ends);
+
+/*
  * tri_bench_boxfilter runs ONE axis stage of masked_gaussian_filter's two box
  * filters (flagging.py:362-419, 469-513) `repeats` times on `stream` in the
  * launch geometry the flagger itself uses, bracketed by HIP events on that

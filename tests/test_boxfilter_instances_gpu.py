@@ -34,7 +34,7 @@ import traceback
 import numpy as np
 import pytest
 
-from test_route_ledger import BOX_KERNELS, box_instances, matches, switch_met_instances
+from test_route_ledger import BOX_KERNELS, matches, switch_met_instances, symbol_instances
 from test_final_pass_routes_gpu import TAP_F32, same_f32
 
 pytestmark = pytest.mark.gpu
@@ -660,7 +660,7 @@ def test_every_listed_box_instantiation_met_a_host_reference(proof):
     equalled its reference" lives in that module, not in this one."""
     for case in CASES:
         proof.ensure(case)
-    listed = {k: box_instances(k, reachable_only=True) for k in BOX_KERNELS}
+    listed = {k: symbol_instances(k, reachable_only=True) for k in BOX_KERNELS}
     elsewhere = switch_met_instances()
     for kernel in sorted(listed):
         print("%s: %s" % (kernel, "; ".join(sorted(m for m in proof.met if matches(kernel, m))) or "-"))

@@ -502,8 +502,9 @@ def test_fused_sumthreshold_kernel_vs_generic_and_oracle(gpu, oracle, shape):
                                            ((1, 2000, 64), (7,))])
 def test_sumthreshold_stage_pipeline_vs_generic_and_oracle(gpu, oracle, shape, windows):
     """K7p (one window per wave, prefix rings in LDS) against the generic global-scratch kernel and the oracle:
-    final_st_very_broad's windows, lists of one to eight windows, windows wider than the line, lines of many
-    blocks, NaN MADs, ragged column counts."""
+    final_st_very_broad's windows, lists of one to eight windows (windows wider than the line are dropped from the
+    list first, as tri_prepare_params drops them before any kernel sees them), lines of many blocks, NaN MADs,
+    ragged column counts."""
     rs = np.random.RandomState(shape[1] + len(windows))
     data = rs.standard_normal(shape).astype(np.float32) * 2.0
     data[:, shape[1] // 3: shape[1] // 3 + 40, :] += 3.0      # broad bump: only the wide windows see it

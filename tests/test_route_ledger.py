@@ -26,13 +26,16 @@ Row of KERNELS
              kernel that is no template).  An entry dict(name="k_x<3>", unreachable="why") is an instantiation no public
              call can reach.  The scans below hold the lists to the launch sites, and
              tests/test_entry_kernels_gpu.py launches every reachable one in a call it compares with a host reference.
-    dict(test=..., instances=[...], flagger=True)   the box-filter kernels (BOX_KERNELS): launched by the flagger -- they
-             count as `flagger` kernels for test_route_matrix_gpu.py (is_flagger) -- and listed by instantiation as
-             well.  They are launched from template functions behind the dispatchers' `switch` statements, which the
-             launch-site scan cannot follow, so these rows are held to the symbol table of the built library instead
-             (one weak __device_stub__ symbol per instantiation: test_box_rows_are_the_library_symbols), and
-             tests/test_boxfilter_instances_gpu.py launches every reachable one in a call it compares with the
-             oracle.  Besides `unreachable`, an entry of these rows may be dict(name=..., switch="TRI_X"): reachable only
+    dict(test=..., instances=[...], flagger=True)   the symbol-held rows (SYMBOL_KERNELS): the box-filter kernels
+             (BOX_KERNELS) and the SumThreshold kernels (ST_KERNELS).  Launched by the flagger -- they count as `flagger`
+             kernels for test_route_matrix_gpu.py (is_flagger) -- and listed by instantiation as well.  The box filters
+             are launched from template functions behind the dispatchers' `switch` statements, which the launch-site scan
+             cannot follow, so these rows are held to the symbol table of the built library instead (one weak
+             __device_stub__ symbol per instantiation: test_box_rows_are_the_library_symbols);
+             tests/test_boxfilter_instances_gpu.py launches every reachable box-filter instantiation in a call it compares
+             with the oracle, tests/test_sumthreshold_kernels_gpu.py every SumThreshold one in calls over chunked lines
+             that it compares with a numpy restatement of flagging.py:610-681.  Besides `unreachable`, an entry
+             of the box-filter rows may be dict(name=..., switch="TRI_X"): reachable only
              under route switches that need a process of their own beyond the three that module starts (one entry:
              TRI_FILTER_DIRECT_FT acts under TRI_NO_PACKED_FLAGS=1 only); the leg of that switch in
              test_route_matrix_gpu.py, compared with the oracle, must then name exactly this instantiation as `new` or
@@ -41,8 +44,8 @@ Row of KERNELS
 Held to the launch sites (test_listed_instances_are_the_launch_sites): the pack / unpack, scan, strategy-step, Stokes and
 window-count rows.  The uv-contsub rows and those of its multi-workgroup median (k_medbig_*) as well: every instantiation behind
 tri_uvcontsub_flagger is met, stage by stage, by tests/test_uvcontsub_kernels_gpu.py (`also` names a second test that runs
-the kernel against a reference).  Held to the symbol table: the rows of BOX_KERNELS.  The open remainder: k_sir (152
-instantiations), the segmented-median, rejection, SumThreshold and line-RMS families keep rows by base name only.
+the kernel against a reference).  Held to the symbol table: the rows of SYMBOL_KERNELS.  The open remainder: k_sir (152
+instantiations), the segmented-median, rejection and line-RMS families keep rows by base name only.
 """
 import glob
 import itertools
@@ -244,6 +247,23 @@ BOX_ROWS = {
 }
 BOX_KERNELS = tuple(BOX_ROWS)
 
+_ST = "test_sumthreshold_kernels_gpu.py::test_every_listed_sumthreshold_instantiation_met_the_reference"
+
+
+def _st(*instances):
+    return dict(test=_ST, instances=list(instances), flagger=True)
+
+
+# the SumThreshold family (st_launch): the two cascades exist for windows (1, 2, 4, 8) only, the lane-mask one on rows
+# and on 64-column panels
+ST_ROWS = {
+    "k_colst_dyn": _st("k_colst_dyn"), "k_colst_pipe": _st("k_colst_pipe"), "k_colst_fused": _st("k_colst_fused<1, 2, 4, 8>"),
+    "k_colst_mask": _st("k_colst_mask<1, 2, 4, 8, false>", "k_colst_mask<1, 2, 4, 8, true>"),
+}
+ST_KERNELS = tuple(ST_ROWS)
+# the rows held to the symbol table of the built library
+SYMBOL_KERNELS = BOX_KERNELS + ST_KERNELS
+
 # "flagger": launched by sum_threshold_flagger on some route -- test_route_matrix_gpu.py must see it in an oracle-checked log
 KERNELS = {
     # kernels_boxexact / boxfilter / boxline / boxpipe / boxweight: BOX_ROWS below (listed by instantiation)
@@ -294,13 +314,13 @@ KERNELS = {
     "k_unpack_scan_rows": _inst(_ROWS + "test_gpu_unpack_scan_rows_matches_unpack_scan", "k_unpack_scan_rows<4>", "k_unpack_scan_rows<0>"),
     # kernels_sir
     "k_sir": "test_sir.py::test_gpu_sir_small_and_odd_shapes",
-    # kernels_sumthreshold
-    "k_colst_dyn": "flagger", "k_colst_pipe": "flagger", "k_colst_fused": "flagger", "k_colst_mask": "flagger",
+    # kernels_sumthreshold: ST_ROWS (listed by instantiation)
     # tricolour_amd.hip
     "k_tables": "flagger", "k_gather_col_f32": "flagger", "k_gather_col_u8": "flagger", "k_normalise_flags": "flagger",
     "k_check_box_divide": _PARITY + "test_division_by_box_denominator",
 }
 KERNELS.update(BOX_ROWS)
+KERNELS.update(ST_ROWS)
 
 
 def matches(fragment, name):
@@ -330,19 +350,19 @@ def named_test(where):
 
 
 def is_flagger(kernel):
-    """Whether sum_threshold_flagger launches the kernel on some route (the rows of BOX_KERNELS say so in a field)."""
+    """Whether sum_threshold_flagger launches the kernel on some route (the rows of SYMBOL_KERNELS say so in a field)."""
     where = KERNELS.get(kernel)
     return where == "flagger" or (isinstance(where, dict) and bool(where.get("flagger")))
 
 
 def instance_rows():
     """{kernel: row} of the KERNELS rows held to the launch sites: those that list their instantiations, the box-filter
-    rows (held to the symbol table) apart."""
+    and SumThreshold rows (held to the symbol table) apart."""
     return {k: w for k, w in KERNELS.items() if isinstance(w, dict) and not w.get("flagger")}
 
 
-def box_instances(kernel, reachable_only=False):
-    """The instantiations a row of BOX_KERNELS lists (`switch` entries count as reachable)."""
+def symbol_instances(kernel, reachable_only=False):
+    """The instantiations a row of SYMBOL_KERNELS lists (`switch` entries count as reachable)."""
     out = []
     for item in KERNELS[kernel]["instances"]:
         if not isinstance(item, dict):
@@ -357,11 +377,11 @@ def switch_met_instances():
     return {item["name"]: item["switch"] for k in BOX_KERNELS for item in KERNELS[k]["instances"] if isinstance(item, dict) and "switch" in item}
 
 
-def box_row_errors(symbols):
-    """What differs between the rows of BOX_KERNELS and a list of the library's kernel instantiations."""
+def symbol_row_errors(symbols):
+    """What differs between the rows of SYMBOL_KERNELS and a list of the library's kernel instantiations."""
     out = []
-    for kernel in BOX_KERNELS:
-        listed, built = set(box_instances(kernel)), {n for n in symbols if base_name(n) == kernel}
+    for kernel in SYMBOL_KERNELS:
+        listed, built = set(symbol_instances(kernel)), {n for n in symbols if base_name(n) == kernel}
         if listed != built:
             out.append("%s: in the library but not listed %s; listed but not in the library %s" % (kernel, sorted(built - listed), sorted(listed - built)))
     return out
@@ -586,15 +606,16 @@ def test_rows_are_well_formed():
     for kernel, where in KERNELS.items():
         if isinstance(where, dict):
             assert set(where) - {"flagger", "also"} == {"test", "instances"} and "::" in where["test"] and where["instances"], kernel
-            assert "also" not in where or ("::" in where["also"] and where["also"] != where["test"] and kernel not in BOX_KERNELS), kernel
-            assert ("flagger" in where) == (kernel in BOX_KERNELS) and where.get("flagger", True) is True, kernel
+            assert "also" not in where or ("::" in where["also"] and where["also"] != where["test"] and kernel not in SYMBOL_KERNELS), kernel
+            assert ("flagger" in where) == (kernel in SYMBOL_KERNELS) and where.get("flagger", True) is True, kernel
+            assert where["test"] == {True: _BOX, False: _ST}[kernel in BOX_KERNELS] or kernel not in SYMBOL_KERNELS, kernel
             for item in where["instances"]:
                 if isinstance(item, dict):
                     assert set(item) in ({"name", "unreachable"}, {"name", "switch"}) and all(item.values()), kernel
                     assert "switch" not in item or kernel in BOX_KERNELS, kernel
                 else:
                     assert isinstance(item, str), kernel
-            names = box_instances(kernel) if kernel in BOX_KERNELS else listed_instances(kernel)
+            names = symbol_instances(kernel) if kernel in SYMBOL_KERNELS else listed_instances(kernel)
             assert all(base_name(n) == kernel and (n == kernel or re.match(r"^%s<[^<>]+>$" % kernel, n)) for n in names), kernel
             assert len(set(names)) == len(names), kernel
         else:
@@ -663,38 +684,69 @@ def test_a_wrong_ledger_row_fails_the_scan(monkeypatch):
 
 
 def test_box_rows_are_the_library_symbols():
-    """The rows of BOX_KERNELS against the symbol table of the built library (built here if it is missing, as for
-    tests/test_abi.py): an instantiation added to a dispatcher, removed or renamed without its row fails here."""
+    """The rows of SYMBOL_KERNELS (box filters and SumThreshold) against the symbol table of the built library (built
+    here if it is missing, as for tests/test_abi.py): an instantiation added to a dispatcher, removed or renamed without
+    its row fails here."""
     from tricolour_amd import _lib
     _lib.build()
     symbols = library_instances(_lib.LIB_PATH)
-    assert len(symbols) > 300 and set(BOX_KERNELS) <= {base_name(n) for n in symbols}, len(symbols)
+    assert len(symbols) > 300 and set(SYMBOL_KERNELS) <= {base_name(n) for n in symbols}, len(symbols)
     # (the log the GPU tests compare with spells the names as the symbol table does)
     assert "k_boxqf<40, 2, 8>" in symbols and "k_boxf<32, true, 2, 1>" in symbols and "k_boxw<110>" in symbols
-    errors = box_row_errors(symbols)
+    assert "k_colst_mask<1, 2, 4, 8, true>" in symbols and "k_colst_dyn" in symbols
+    errors = symbol_row_errors(symbols)
     assert not errors, "\n".join(errors)
 
 
 def test_a_wrong_box_row_fails_against_the_symbols(monkeypatch):
     """A row with a name too many and a row with a name missing both fail against a given symbol list, unreachable
     entries included; so does an instantiation a dispatcher gained."""
-    symbols = [n for k in BOX_KERNELS for n in box_instances(k)] + ["k_sir<4, true>", "k_pack_v<2>"]
-    assert not box_row_errors(symbols)
-    gained = box_row_errors(symbols + ["k_boxqf<88, 1, 8>"])
+    symbols = [n for k in SYMBOL_KERNELS for n in symbol_instances(k)] + ["k_sir<4, true>", "k_pack_v<2>"]
+    assert not symbol_row_errors(symbols)
+    gained = symbol_row_errors(symbols + ["k_boxqf<88, 1, 8>"])
     assert len(gained) == 1 and "not listed ['k_boxqf<88, 1, 8>']" in gained[0], gained
     for lost in ("k_boxw<46>", "k_boxt<16, true, 0>"):                       # a reachable one, an unreachable one
-        errors = box_row_errors([n for n in symbols if n != lost])
+        errors = symbol_row_errors([n for n in symbols if n != lost])
         assert len(errors) == 1 and "not in the library ['%s']" % lost in errors[0], errors
     row = KERNELS["k_boxp_spec"]
     monkeypatch.setitem(KERNELS, "k_boxp_spec", dict(row, instances=row["instances"] + ["k_boxp_spec<4, 16>"]))
-    errors = box_row_errors(symbols)
+    errors = symbol_row_errors(symbols)
     assert len(errors) == 1 and errors[0].startswith("k_boxp_spec:") and "not in the library ['k_boxp_spec<4, 16>']" in errors[0], errors
     monkeypatch.setitem(KERNELS, "k_boxp_spec", dict(row, instances=row["instances"][:1]))
-    errors = box_row_errors(symbols)
+    errors = symbol_row_errors(symbols)
     assert len(errors) == 1 and "not listed ['k_boxp_spec<8, 16>']" in errors[0], errors
     monkeypatch.setitem(KERNELS, "k_boxp_spec", dict(row, instances=[row["instances"][0], _no("k_boxp_spec<8, 16>", "an example")]))
-    assert not box_row_errors(symbols)
-    assert "k_boxp_spec<8, 16>" not in box_instances("k_boxp_spec", reachable_only=True)
+    assert not symbol_row_errors(symbols)
+    assert "k_boxp_spec<8, 16>" not in symbol_instances("k_boxp_spec", reachable_only=True)
+
+
+def test_a_wrong_sumthreshold_row_fails_against_the_symbols(monkeypatch):
+    """The same for the SumThreshold rows: a cascade instantiated for other windows, a lost panel form and a row that
+    lists too much or too little all show, each in its own row only."""
+    symbols = [n for k in SYMBOL_KERNELS for n in symbol_instances(k)] + ["k_sir<4, true>"]
+    assert not symbol_row_errors(symbols)
+    gained = symbol_row_errors(symbols + ["k_colst_mask<1, 2, 4, 4, false>"])
+    assert len(gained) == 1 and gained[0].startswith("k_colst_mask:") and "not listed ['k_colst_mask<1, 2, 4, 4, false>']" in gained[0], gained
+    for lost in ("k_colst_mask<1, 2, 4, 8, true>", "k_colst_dyn"):
+        errors = symbol_row_errors([n for n in symbols if n != lost])
+        assert len(errors) == 1 and "not in the library ['%s']" % lost in errors[0], errors
+    row = KERNELS["k_colst_fused"]
+    monkeypatch.setitem(KERNELS, "k_colst_fused", dict(row, instances=row["instances"] + ["k_colst_fused<1, 2, 2, 4>"]))
+    errors = symbol_row_errors(symbols)
+    assert len(errors) == 1 and errors[0].startswith("k_colst_fused:") and "not in the library ['k_colst_fused<1, 2, 2, 4>']" in errors[0], errors
+    monkeypatch.setitem(KERNELS, "k_colst_mask", dict(KERNELS["k_colst_mask"], instances=["k_colst_mask<1, 2, 4, 8, false>"]))
+    monkeypatch.setitem(KERNELS, "k_colst_fused", row)
+    errors = symbol_row_errors(symbols)
+    assert len(errors) == 1 and "not listed ['k_colst_mask<1, 2, 4, 8, true>']" in errors[0], errors
+
+
+def test_sumthreshold_rows_cover_the_sumthreshold_kernels():
+    """ST_KERNELS are the kernels of kernels_sumthreshold.hpp, all of them; each is still a flagger kernel."""
+    with open(os.path.join(CSRC, "kernels_sumthreshold.hpp"), encoding="utf-8") as fh:
+        found = set(re.findall(r"__global__[\s\S]{0,200}?\b(k_\w+)\s*\(", fh.read()))
+    assert found == set(ST_KERNELS), sorted(found ^ set(ST_KERNELS))
+    assert all(is_flagger(k) for k in ST_KERNELS) and not set(ST_KERNELS) & set(BOX_KERNELS)
+    assert all(base_name(n) == k for k in ST_KERNELS for n in symbol_instances(k, reachable_only=True))
 
 
 def test_box_rows_cover_the_box_filter_kernels():

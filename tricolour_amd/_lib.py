@@ -181,6 +181,11 @@ _SIGNATURES = {
                                          C.c_int64, C.c_int64, C.POINTER(C.c_int64),
                                          C.c_int64, C.c_double, C.c_double, C.c_int,
                                          C.c_int, C.POINTER(C.c_float), C.c_void_p]),
+    "tri_test_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                        C.c_int64, C.c_double, C.c_double, C.c_int,
+                                        C.c_int, C.POINTER(C.c_float), C.c_void_p,
+                                        C.POINTER(C.c_int64), C.c_int64]),
     "tri_bench_boxfilter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_float), C.c_void_p]),

@@ -2600,19 +2600,25 @@ extern "C" int tri_bench_reject(const float* resid, const uint8_t* flags_in, uin
     return TRI_OK;
 }
 
-extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint8_t* out,
-                                      int64_t n_win, int64_t n_line, int64_t n_col,
-                                      const int64_t* windows, int64_t n_windows,
-                                      double outlier_nsigma, double rho, int variant, int repeats,
-                                      float* ms_per_launch, void* stream) {
-    if (!data || !mad || !out || !windows || !ms_per_launch) return set_err(TRI_EINVAL, "NULL pointer argument");
+// The body of tri_bench_sumthreshold ({0, n_line}, the measurement hook's own pick for variant 0) and of
+// tri_test_sumthreshold (the caller's chunks, launch_colst's pick): G = n_chunk_ends - 1 line groups per column.
+static int st_hook(const float* data, const double* mad, uint8_t* out, int64_t n_win, int64_t n_line, int64_t n_col,
+                   const int64_t* windows, int64_t n_windows, double outlier_nsigma, double rho, int variant, int repeats,
+                   float* ms_per_launch, void* stream, const int64_t* chunk_ends, int64_t n_chunk_ends, bool flagger_pick) {
+    if (!data || !mad || !out || !windows || !ms_per_launch || !chunk_ends) return set_err(TRI_EINVAL, "NULL pointer argument");
     if (n_win <= 0 || n_line <= 0 || n_col <= 0 || repeats <= 0 || n_win > 65535) return set_err(TRI_EINVAL, "bad shape");
+    if (n_chunk_ends < 2 || n_chunk_ends > 256) return set_err(TRI_EINVAL, "2 .. 256 chunk ends");
+    for (int64_t g = 0; g < n_chunk_ends; g++)
+        if (chunk_ends[g] < 0 || chunk_ends[g] > n_line || (g > 0 && chunk_ends[g] < chunk_ends[g - 1]))
+            return set_err(TRI_EINVAL, "chunk ends must not decrease and must lie in [0, n_line]");
+    const int G = (int)n_chunk_ends - 1;
+    const int64_t o0 = chunk_ends[0], o1 = chunk_ends[G];     // the lines the kernels write
     hipStream_t st = (hipStream_t)stream;
     StWin sw;
     int rc = make_stwin(windows, n_windows, rho, &sw);
     if (rc) return rc;
     double thr_scale = outlier_nsigma * TRI_MAD_NORMAL;
-    size_t nthreads = (size_t)n_win * n_col;
+    size_t nthreads = (size_t)n_win * n_col * G;             // (k_colst_dyn: one ring per (window, chunk, column))
     int C = (int)n_col, L = (int)n_line;
     bool can_fuse = sw.nw == 4 && sw.w[0] == 1 && sw.w[1] == 2 && sw.w[2] == 4 && sw.w[3] == 8;
     if ((variant == 2 || variant == 3) && !can_fuse) return set_err(TRI_EUNSUPPORTED, "register cascade needs windows (1,2,4,8)");
@@ -2622,7 +2628,9 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     // handed in are re-laid out before the timed region and the flags taken back to rows after it
     if (variant == 5 && !(can_fuse && C % 64 == 0 && (uint64_t)L * (uint64_t)C * 4u < (1ull << 31)))
         return set_err(TRI_EUNSUPPORTED, "panel SumThreshold: windows (1,2,4,8), a multiple of 64 columns, a window below 2^31 bytes");
-    if (variant == 0 && can_fuse) variant = st_use_mask(L, C) ? ((C % 64 == 0 && !st_no_panel()) ? 5 : 3) : 2;
+    if (variant == 5 && G > 1) return set_err(TRI_EUNSUPPORTED, "panel SumThreshold: one chunk only (launch_colst never pairs a panel with chunks)");
+    if (variant == 0 && can_fuse) variant = st_use_mask(L, C) ? ((G == 1 && C % 64 == 0 && !st_no_panel()) ? 5 : 3) : 2;
+    if (variant == 0 && flagger_pick && st_use_pipe(sw)) variant = 4;
     if (variant == 4) {
         if (sw.nw > 8 || stp_lds_bytes(sw) > 160 * 1024) return set_err(TRI_EUNSUPPORTED, "stage pipeline: more than eight windows, or the flag ring does not fit LDS");
         HIPCHK(lds_optin_all(160 * 1024, &k_colst_pipe));
@@ -2632,9 +2640,8 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     DevBuf<int64_t> d_ends;
     HIPCHK(ring.alloc(nthreads * sw.ringtot));
     HIPCHK(acc.alloc(nthreads * sw.acccap));
-    HIPCHK(d_ends.alloc(2));
-    int64_t ends[2] = {0, n_line};
-    HIPCHK(hipMemcpyAsync(d_ends.get(), ends, sizeof(ends), hipMemcpyHostToDevice, st));
+    HIPCHK(d_ends.alloc((size_t)n_chunk_ends));
+    HIPCHK(hipMemcpyAsync(d_ends.get(), chunk_ends, (size_t)n_chunk_ends * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     HipEvent e0, e1;
     HIPCHK(hipEventCreate(e0.out()));
@@ -2657,7 +2664,7 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     uint8_t* kout = variant == 5 ? pout.get() : out;
     HIPCHK(hipEventRecord(e0.get(), st));
     for (int i = 0; i < repeats; i++) {
-        rc = st_launch(st, k, sw, kdata, mad, kout, d_ends.get(), thr_scale, L, C, 1, ws, ws, n_win, ring.get(), acc.get());
+        rc = st_launch(st, k, sw, kdata, mad, kout, d_ends.get(), thr_scale, L, C, G, ws, ws, n_win, ring.get(), acc.get());
         if (rc) return rc;
     }
     HIPCHK(hipEventRecord(e1.get(), st));
@@ -2667,14 +2674,43 @@ extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint
     HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
     *ms_per_launch = ms / repeats;
     if (variant == 5) {
+        // (a chunk short of the line: the rows outside it are not the kernel's to write -- back through a row image, the
+        // chunk's rows alone copied out)
+        const bool whole = o0 == 0 && o1 == n_line;
+        DevBuf<uint8_t> rows;
+        if (!whole) HIPCHK(rows.alloc((size_t)n_win * ws));
+        uint8_t* dst = whole ? out : rows.get();
         {
             ScopedSet<bool> pause(g_klog_on, false);
-            hipLaunchKernelGGL(k_unpanel_w<uint8_t>, dim3((unsigned)cdiv((int64_t)ws, 256), (unsigned)n_win), dim3(256), 0, st, (const uint8_t*)pout.get(), out, L, C, ws);
+            hipLaunchKernelGGL(k_unpanel_w<uint8_t>, dim3((unsigned)cdiv((int64_t)ws, 256), (unsigned)n_win), dim3(256), 0, st, (const uint8_t*)pout.get(), dst, L, C, ws);
         }
         LAUNCHCHK();
+        if (!whole && o1 > o0)
+            for (int64_t w = 0; w < n_win; w++)
+                HIPCHK(hipMemcpyAsync(out + (size_t)w * ws + (size_t)o0 * C, dst + (size_t)w * ws + (size_t)o0 * C, (size_t)(o1 - o0) * C,
+                                      hipMemcpyDeviceToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
     }
     return TRI_OK;
+}
+
+extern "C" int tri_bench_sumthreshold(const float* data, const double* mad, uint8_t* out,
+                                      int64_t n_win, int64_t n_line, int64_t n_col,
+                                      const int64_t* windows, int64_t n_windows,
+                                      double outlier_nsigma, double rho, int variant, int repeats,
+                                      float* ms_per_launch, void* stream) {
+    const int64_t ends[2] = {0, n_line};
+    return st_hook(data, mad, out, n_win, n_line, n_col, windows, n_windows, outlier_nsigma, rho, variant, repeats, ms_per_launch,
+                   stream, ends, 2, false);
+}
+
+extern "C" int tri_test_sumthreshold(const float* data, const double* mad, uint8_t* out,
+                                     int64_t n_win, int64_t n_line, int64_t n_col,
+                                     const int64_t* windows, int64_t n_windows,
+                                     double outlier_nsigma, double rho, int variant, int repeats,
+                                     float* ms_per_launch, void* stream, const int64_t* chunk_ends, int64_t n_chunk_ends) {
+    return st_hook(data, mad, out, n_win, n_line, n_col, windows, n_windows, outlier_nsigma, rho, variant, repeats, ms_per_launch,
+                   stream, chunk_ends, n_chunk_ends, true);
 }
 
 // The thread-local route overrides of the box filters, saved on entry and restored on exit: a hook that switches routes
