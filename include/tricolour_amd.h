@@ -403,6 +403,44 @@ int tri_line_rms_threshold(const void *vis, int vis_dtype, const uint8_t *flags,
                            int flag_low, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/*
+ * Baseline integration (beyond the reference; the model is AOFlagger's
+ * baseline-integrated flagging, the definition is this library's own): the
+ * amplitudes of all baselines averaged into one image of n = ncorr * ntime *
+ * nchan positions, which the ordinary flagger flags, and the detections given
+ * back to every baseline.  vis (nbl, n) complex64 or float32 amplitudes, flags
+ * (nbl, n) uint8 (nonzero = flagged), select[nbl] uint8 on the device
+ * (nonzero = the baseline takes part) or NULL for all:
+ *   a        = +inf if re or im is infinite, else (float)sqrt((double)re * re
+ *              + (double)im * im)   (fabsf(v) for amplitudes); a sample counts
+ *              if its baseline is selected, its flag is 0 and a is not NaN
+ *   tri_baseline_accumulate: for b = 0 .. nbl - 1 in that order and every
+ *              counting sample sum[i] += (double)a, count[i] += 1.  One thread
+ *              per position, no atomics, no re-association: the order over
+ *              baselines is the order in memory.  The call ADDS to sum and
+ *              count (the caller zeroes them first), so the baselines fed in
+ *              several calls in ascending order give the bits of one call.
+ *   tri_baseline_mean: flag[i] = count[i] < min_count;  amp[i] = (float)(sum[i]
+ *              / (double)count[i]) where flag[i] is 0, else 0.  The caller
+ *              computes min_count = max(1, ceil(min_baseline_frac * selected)).
+ *   (the flagger: tri_sum_threshold_flagger on amp / flag as one float32
+ *   block of ncorr windows gives line[n])
+ *   tri_broadcast_or: out[b, i] = (flags[b, i] != 0) | (line[i] != 0) for every
+ *              baseline, the unselected ones included; out may be flags itself.
+ * TRI_EINVAL for NULL pointers (other than select), negative sizes, min_count
+ * < 1, out overlapping line (or overlapping flags without being flags);
+ * TRI_EUNSUPPORTED for dtypes other than complex64 and float32.  No
+ * workspace.  Empty shapes return TRI_OK without a launch.
+ */
+int tri_baseline_accumulate(const void *vis, int vis_dtype, const uint8_t *flags,
+                            const uint8_t *select /* may be NULL */,
+                            int64_t nbl, int64_t n, double *sum, int32_t *count,
+                            void *stream);
+int tri_baseline_mean(const double *sum, const int32_t *count, int64_t n,
+                      int64_t min_count, float *amp, uint8_t *flag, void *stream);
+int tri_broadcast_or(const uint8_t *flags, const uint8_t *line, uint8_t *out,
+                     int64_t nbl, int64_t n, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

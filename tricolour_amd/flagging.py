@@ -859,3 +859,145 @@ def threshold_line_rms(vis, flags, nsigma_time=3.5, nsigma_freq=3.0, flag_low=Tr
                     out.data_ptr() + w0 * per, b, ntime, nchan, nsigma_time, nsigma_freq, 1 if flag_low else 0,
                     ws.data_ptr(), ws.numel(), stream))
     return _like_flags(torch, out, flags, from_numpy)
+
+
+def _bli_inputs(name, vis, flags, select):
+    """Checks of the baseline-integration calls (all before any device work), then the device inputs:
+    (torch, vis, flags uint8, dtype code, from_numpy, device, select uint8 on the device or None)."""
+    shape = tuple(vis.shape)
+    if len(shape) != 4:
+        raise ValueError("vis must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    if tuple(flags.shape) != shape:
+        raise ValueError("vis and flags must have the same shape, got %s and %s" % (shape, tuple(flags.shape)))
+    if str(vis.dtype).replace("torch.", "") not in ("complex64", "float32"):
+        raise TypeError("tricolour_amd.%s: visibilities must be complex64 or float32 (got %s)" % (name, vis.dtype))
+    if select is not None:
+        if not hasattr(select, "shape"):
+            select = np.asarray(select)
+        if tuple(select.shape) != (shape[0],):
+            raise ValueError("select must have one entry per baseline (%d), got shape %s"
+                             % (shape[0], tuple(select.shape)))
+    torch = _require_gpu()
+    v, f8, code, from_numpy, device = _as_device_inputs(torch, vis, flags)
+    sel = None
+    if select is not None:
+        if not torch.is_tensor(select):
+            select = torch.from_numpy(np.ascontiguousarray(select))
+        sel = (select.to(device) != 0).view(torch.uint8)       # a device tensor stays there: no synchronisation
+    return torch, v, f8, code, from_numpy, device, sel
+
+
+def _bli_selected(nbl, sel):
+    """Baselines that take part (the one host read of a selection; the accumulate alone does not need it)."""
+    return nbl if sel is None else int(sel.sum().item())
+
+
+def _bli_min_count(min_baseline_frac, nsel):
+    import math
+    return max(1, int(math.ceil(min_baseline_frac * nsel)))
+
+
+def _bli_fraction(min_baseline_frac):
+    frac = float(min_baseline_frac)
+    if not 0.0 <= frac <= 1.0:                # also rejects NaN
+        raise ValueError("min_baseline_frac must lie in [0, 1], got %r" % (min_baseline_frac,))
+    return frac
+
+
+def _bli_accumulate(torch, lib, device, v, f8, code, sel, acc):
+    """(sum float64, count int32) of shape (corr, time, chan) on the device: new tensors, continued from `acc`."""
+    nbl, img = int(v.shape[0]), tuple(int(s) for s in v.shape[1:])
+    if acc is None:
+        total = torch.zeros(img, dtype=torch.float64, device=device)
+        count = torch.zeros(img, dtype=torch.int32, device=device)
+    else:
+        total, count = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a for a in acc)
+        if tuple(total.shape) != img or tuple(count.shape) != img:
+            raise ValueError("acc must be a (sum, count) pair of shape %s" % (img,))
+        if total.dtype != torch.float64 or count.dtype != torch.int32:
+            raise TypeError("acc must be a (float64 sum, int32 count) pair")
+        total, count = total.to(device).clone().contiguous(), count.to(device).clone().contiguous()
+    if total.numel() > 0 and nbl > 0:
+        _lib.check(lib.tri_baseline_accumulate(
+            v.data_ptr(), code, f8.data_ptr(), sel.data_ptr() if sel is not None else None, nbl, total.numel(),
+            total.data_ptr(), count.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    return total, count
+
+
+def _bli_mean(torch, lib, device, total, count, min_count):
+    amp = torch.empty(total.shape, dtype=torch.float32, device=device)
+    flag = torch.empty(total.shape, dtype=torch.uint8, device=device)
+    if total.numel() > 0:
+        _lib.check(lib.tri_baseline_mean(total.data_ptr(), count.data_ptr(), total.numel(), min_count, amp.data_ptr(),
+                                         flag.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    return amp, flag
+
+
+def baseline_integral(vis, flags, select=None, acc=None):
+    """Sum and count over baselines of the amplitudes of (bl, corr, time, chan)
+    visibilities (complex64: ``|v|`` as the flagger takes it; float32:
+    ``fabs``): for every (corr, time, chan) position and the baselines in
+    ascending order, ``sum += float64(a)`` and ``count += 1`` over the samples
+    whose baseline is selected (``select``, one entry per baseline, nonzero =
+    takes part; None: all), whose flag is 0 and whose amplitude is not NaN.
+    Returns ``(sum float64, count int32)`` of shape (corr, time, chan) --
+    numpy arrays for numpy input, tensors on the device otherwise.  ``acc``:
+    an earlier result to continue from (not modified; the result is a new
+    pair): the baselines fed in several calls in ascending order give the bits
+    of one call.  One thread owns a position and sums in memory order, so the
+    result is reproducible bit for bit.  Inputs are not modified."""
+    torch, v, f8, code, from_numpy, device, sel = _bli_inputs("baseline_integral", vis, flags, select)
+    with torch.cuda.device(device):
+        total, count = _bli_accumulate(torch, _lib.lib(), device, v, f8, code, sel, acc)
+    if from_numpy:
+        return total.cpu().numpy(), count.cpu().numpy()
+    return total, count
+
+
+def baseline_mean_amplitude(vis, flags, select=None, min_baseline_frac=0.0):
+    """Mean amplitude over baselines of (bl, corr, time, chan) visibilities:
+    :func:`baseline_integral`'s ``float32(sum / count)`` per (corr, time, chan)
+    position.  A position that fewer than ``max(1, ceil(min_baseline_frac *
+    selected baselines))`` baselines count at is flagged, with amplitude 0.
+    Returns ``(amp float32, flag bool)`` -- numpy arrays for numpy input,
+    tensors on the device otherwise.  Inputs are not modified."""
+    frac = _bli_fraction(min_baseline_frac)
+    torch, v, f8, code, from_numpy, device, sel = _bli_inputs("baseline_mean_amplitude", vis, flags, select)
+    nsel = _bli_selected(int(v.shape[0]), sel)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        total, count = _bli_accumulate(torch, lib, device, v, f8, code, sel, None)
+        amp, flag = _bli_mean(torch, lib, device, total, count, _bli_min_count(frac, nsel))
+    flag = flag.view(torch.bool)
+    if from_numpy:
+        return amp.cpu().numpy(), flag.cpu().numpy()
+    return amp, flag
+
+
+def baseline_integrated_flagger(vis, flags, select=None, min_baseline_frac=0.25, **sum_threshold_kwargs):
+    """SumThreshold on the baseline-integrated image (after AOFlagger's
+    baseline integration): :func:`baseline_mean_amplitude` of the selected
+    baselines gives one (corr, time, chan) float32 image whose noise falls as
+    1 / sqrt(baselines); :func:`sum_threshold_flagger` (``sum_threshold_kwargs``)
+    flags it as a (1, corr, time, chan) block; its detections are ORed into
+    the flags of EVERY baseline, the unselected ones included:
+    ``out[b] = (flags[b] != 0) | new``.  Finds RFI that is below the threshold
+    of each baseline but present on all.  Returns a new array in the container
+    / dtype of ``flags``; the inputs are not modified.  Parallelism is over the
+    image alone: a short image with many baselines under-fills the device."""
+    frac = _bli_fraction(min_baseline_frac)
+    torch, v, f8, code, from_numpy, device, sel = _bli_inputs("baseline_integrated_flagger", vis, flags, select)
+    nsel = _bli_selected(int(v.shape[0]), sel)
+    lib = _lib.lib()
+    nbl = int(v.shape[0])
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            total, count = _bli_accumulate(torch, lib, device, v, f8, code, sel, None)
+            amp, flag = _bli_mean(torch, lib, device, total, count, _bli_min_count(frac, nsel))
+            del total, count
+            new = sum_threshold_flagger(amp[None], flag[None], **sum_threshold_kwargs)
+            new8 = _flags_u8(torch, new, device)
+            _lib.check(lib.tri_broadcast_or(f8.data_ptr(), new8.data_ptr(), out.data_ptr(), nbl, new8.numel(),
+                                            torch.cuda.current_stream(device).cuda_stream))
+    return _like_flags(torch, out, flags, from_numpy)

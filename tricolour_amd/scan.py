@@ -28,7 +28,11 @@ VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with
                "flag_nans_zeros", "apply_static_mask",          # strat_executor.py:36-83
                "scale_invariant_rank_operator",                 # beyond the reference: flagging.scale_invariant_rank_operator
                "threshold_line_rms",                            # beyond the reference: flagging.threshold_line_rms
-               "mark_missing")                                  # beyond the reference: the missing mask of masked SIR steps
+               "mark_missing",                                  # beyond the reference: the missing mask of masked SIR steps
+               "baseline_integrated_sum_threshold")             # beyond the reference: flagging.baseline_integrated_flagger
+
+# steps that need every baseline of the scan at once: they cannot run per baseline chunk
+WHOLE_SCAN_TASKS = ("baseline_integrated_sum_threshold",)
 
 
 # ---------------------------------------------------------------------------
@@ -102,7 +106,9 @@ def check_strategies(strategies):
     unknown one (strat_executor.py:33-36, 82-83) before any work is done, and
     a ``ValueError`` for a ``scale_invariant_rank_operator`` step whose
     ``missing`` is not ``none`` / ``input`` / ``marked`` or is ``marked`` with
-    no ``mark_missing`` step before it."""
+    no ``mark_missing`` step before it, or for a
+    ``baseline_integrated_sum_threshold`` step whose ``min_baseline_frac`` lies
+    outside [0, 1]."""
     marked = False
     for strategy in strategies:
         try:
@@ -119,6 +125,24 @@ def check_strategies(strategies):
                 raise ValueError("scale_invariant_rank_operator: missing must be 'none', 'input' or 'marked', got %r" % (which,))
             if which == "marked" and not marked:
                 raise ValueError("scale_invariant_rank_operator: missing 'marked' needs an earlier mark_missing")
+        elif task == "baseline_integrated_sum_threshold":
+            frac = (strategy.get('kwargs') or {}).get("min_baseline_frac", 0.25)
+            try:
+                ok = 0.0 <= float(frac) <= 1.0
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("baseline_integrated_sum_threshold: min_baseline_frac must lie in [0, 1], got %r" % (frac,))
+
+
+def _check_whole_scan_tasks(strategies, baseline_chunks):
+    """A step that needs every baseline before it can flag any cannot run per baseline chunk."""
+    if baseline_chunks is None:
+        return
+    for strategy in strategies:
+        if strategy['task'] in WHOLE_SCAN_TASKS:
+            raise ValueError("task '%s' needs every baseline of the scan at once and cannot run with baseline_chunks "
+                             "set: flag the scan whole (baseline_chunks=None)" % strategy['task'])
 
 
 def select_scans(scan_numbers, available):
@@ -225,6 +249,7 @@ def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, stra
         raise ValueError("Invalid flagging strategy '%s'" % flagging_strategy)
     strategies = list(strategies)
     check_strategies(strategies)
+    _check_whole_scan_tasks(strategies, baseline_chunks)
     if len(tuple(data.shape)) != 3:
         raise ValueError("data must have shape (row, chan, corr), got %s" % (tuple(data.shape),))
     nrow, nchan, ncorr = (int(s) for s in data.shape)
@@ -497,6 +522,7 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
     datasets = list(datasets)
     strategies = list(strategies)
     check_strategies(strategies)
+    _check_whole_scan_tasks(strategies, baseline_chunks)
     if fieldnames is None:
         nfield = max([int(ds["FIELD_ID"]) for ds in datasets], default=-1) + 1
         fieldnames = [str(i) for i in range(nfield)]

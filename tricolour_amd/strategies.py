@@ -2,6 +2,8 @@
 ``StrategyExecutor.apply_strategies`` (reference
 ``tricolour/apps/tricolour/strat_executor.py:29-83``) applied to torch tensors
 that stay in HBM between steps."""
+import numpy as np
+
 from tricolour_amd import flagging
 
 
@@ -54,6 +56,17 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
             flag_windows = lor(new_flags, flag_windows)
         elif task == "threshold_line_rms":
             new_flags = flagging.threshold_line_rms(vis_windows, flag_windows, **kw)
+            flag_windows = lor(new_flags, flag_windows)
+        elif task == "baseline_integrated_sum_threshold":
+            kw = dict(kw)
+            select = None
+            if kw.pop("exclude_autos", True):
+                if ubl is None:
+                    raise ValueError("baseline_integrated_sum_threshold: exclude_autos needs ubl")
+                u = np.asarray(ubl)
+                select = u[:, 1] != u[:, 2]
+            # every baseline receives the detections of the integrated image, the unselected ones included
+            new_flags = flagging.baseline_integrated_flagger(vis_windows, flag_windows, select=select, **kw)
             flag_windows = lor(new_flags, flag_windows)
         elif task == "apply_static_mask":
             new_flags = flagging.apply_static_mask(flag_windows, ubl, ant_pos, masked_channels,
