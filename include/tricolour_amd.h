@@ -441,6 +441,66 @@ int tri_baseline_mean(const double *sum, const int32_t *count, int64_t n,
 int tri_broadcast_or(const uint8_t *flags, const uint8_t *line, uint8_t *out,
                      int64_t nbl, int64_t n, void *stream);
 
+/*
+ * Sliding-window complex deviation of (n_win, ntime, nchan) windows and the
+ * thresholding of single samples on it (beyond the reference; the model is
+ * CASA's rflag, the definition is this library's own and identity with rflag
+ * is not claimed).  Every other detector of the library sees the amplitude
+ * alone; this one sees the complex value.  Per window, visibilities v
+ * (complex64, or float32 amplitudes taken as re = a, im = 0) and uint8 flags f
+ * (nonzero = flagged); a sample counts if f == 0 and neither part is NaN.
+ * Time axis, window_time odd in [3, 31], h = (window_time - 1) / 2: for sample
+ * (t, c) walk t' ascending over [max(0, t - h), min(ntime - 1, t + h)], the
+ * counting samples only, all arithmetic in float64 from +0.0 without FMA:
+ *   n  = their number;  sr += (double)re, si += (double)im;
+ *   mr = sr / (double)n, mi = si / (double)n;
+ *   a second walk in the same order: dr = re - mr, di = im - mi,
+ *        acc = acc + dr * dr, then acc = acc + di * di;
+ *   d  = (float)sqrt(acc / (double)n).
+ *   The sample is usable iff it counts itself and n >= 2; an unusable sample
+ *   has d = NaN and is never flagged by the step.  If any counting sample of
+ *   the window has an infinite part, d = +inf.
+ *   A line is one (window, channel); its level med is the median of the finite
+ *   d of its usable samples, m values in all: the middle one for odd m,
+ *   float32(a + b) / 2 of the two middle ones for even m (the sum rounded to
+ *   float32).  The line is live iff m >= 3 and med > 0.
+ *   hit_t = usable && (d == +inf || (live && (double)d > (double)med *
+ *           scale_time)).
+ * Frequency axis: the same with the window sliding along channels
+ * (window_freq, scale_freq) and one level per (window, time row, frequency
+ * chunk k = channels [chunk_ends[k], chunk_ends[k + 1])); chunk_ends is a HOST
+ * array of n_chunk_ends non-decreasing entries from 0 to nchan, read before
+ * the call returns.  The sliding window does not stop at chunk ends, only the
+ * level does; an empty chunk is a no-op.
+ *   out_flags = (f != 0) | hit_t | hit_f   (0/1)
+ * Both axes read the inputs and are not chained; a scale of 0 switches an
+ * axis off; with both off out_flags = (f != 0).  Input buffers are never
+ * written.  No floating-point atomics: the same bits on every run, for every
+ * alignment and for every split of the windows over calls.
+ * tri_local_deviation writes the statistics only: d_time and d_freq,
+ * (n_win, ntime, nchan) float32 images (NaN is 0x7FC00000); either may be
+ * NULL; it needs no workspace.  TRI_EINVAL for NULL pointers (other than
+ * those), negative shapes, a window that is even or outside [3, 31], a scale
+ * that is negative or NaN, chunk ends that do not run from 0 to nchan, and
+ * out_flags overlapping flags; TRI_EUNSUPPORTED for other dtypes and for more
+ * lines than one launch holds (pass fewer windows per call); TRI_EWORKSPACE
+ * when workspace_bytes < tri_local_deviation_workspace_bytes().  Empty shapes
+ * return TRI_OK without a launch.
+ */
+size_t tri_local_deviation_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan,
+                                           int64_t n_chunk_ends);
+int tri_local_deviation(const void *vis, int vis_dtype, const uint8_t *flags,
+                        int64_t n_win, int64_t ntime, int64_t nchan,
+                        int64_t window_time, int64_t window_freq,
+                        float *d_time /* may be NULL */, float *d_freq /* may be NULL */,
+                        void *stream);
+int tri_local_deviation_threshold(const void *vis, int vis_dtype, const uint8_t *flags,
+                                  uint8_t *out_flags, int64_t n_win, int64_t ntime,
+                                  int64_t nchan, int64_t window_time, int64_t window_freq,
+                                  double scale_time, double scale_freq,
+                                  const int64_t *chunk_ends, int64_t n_chunk_ends,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

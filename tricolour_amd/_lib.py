@@ -18,7 +18,7 @@ DEPENDS = [os.path.join(_HERE, "csrc", f) for f in (
     "tri_common.hpp", "kernels_elementwise.hpp", "kernels_median.hpp", "kernels_reject.hpp", "kernels_reject_tile.hpp", "kernels_boxfilter.hpp", "kernels_boxline.hpp", "kernels_boxpipe.hpp",
     "kernels_boxweight.hpp", "kernels_boxexact.hpp",
     "kernels_sumthreshold.hpp", "kernels_scan.hpp", "kernels_sir.hpp", "kernels_linerms.hpp",
-    os.path.join("steps", "kernels_blint.hpp"))]
+    os.path.join("steps", "kernels_blint.hpp"), os.path.join("steps", "ldev", "kernels_ldev.hpp"))]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tricolour_amd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
@@ -180,6 +180,12 @@ _SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "tri_baseline_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tri_broadcast_or": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "tri_local_deviation_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "tri_local_deviation": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tri_local_deviation_threshold": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                C.c_int64, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_int64), C.c_int64,
+                                                C.c_void_p, C.c_size_t, C.c_void_p]),
     "tri_last_error": (C.c_char_p, []),
     "tri_version": (C.c_int, []),
     "tri_bench_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -861,6 +861,129 @@ def threshold_line_rms(vis, flags, nsigma_time=3.5, nsigma_freq=3.0, flag_low=Tr
     return _like_flags(torch, out, flags, from_numpy)
 
 
+def _ldev_window(name, w):
+    """An odd integer in [3, 31], as an int (raises ValueError otherwise; bools and non-integral floats are not integers)."""
+    try:
+        ok = not isinstance(w, bool) and isinstance(w, (int, np.integer, float)) and float(w) == int(w)
+    except (ValueError, OverflowError):       # NaN, infinity
+        ok = False
+    if not ok or int(w) % 2 == 0 or not 3 <= int(w) <= 31:
+        raise ValueError("%s must be an odd integer in [3, 31], got %r" % (name, w))
+    return int(w)
+
+
+def _ldev_scale(name, s):
+    try:
+        ok = float(s) >= 0.0                  # also rejects NaN
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be >= 0, got %r" % (name, s))
+    return float(s)
+
+
+def _ldev_chunks(freq_chunks):
+    ok = not isinstance(freq_chunks, bool) and isinstance(freq_chunks, (int, np.integer)) and int(freq_chunks) >= 1
+    if not ok:
+        raise ValueError("freq_chunks must be an integer >= 1, got %r" % (freq_chunks,))
+    return int(freq_chunks)
+
+
+def check_local_deviation_kwargs(window_time=3, window_freq=3, scale_time=3.5, scale_freq=3.5, freq_chunks=10):
+    """The argument checks of :func:`threshold_local_deviation` (no device work): a window that is even or outside
+    [3, 31], a scale that is negative or NaN and ``freq_chunks < 1`` raise ``ValueError``.  Returns the values."""
+    return (_ldev_window("window_time", window_time), _ldev_window("window_freq", window_freq),
+            _ldev_scale("scale_time", scale_time), _ldev_scale("scale_freq", scale_freq), _ldev_chunks(freq_chunks))
+
+
+def _ldev_batch(torch, lib, device, n_win, ntime, nchan, n_ends, max_windows=None):
+    """Windows per call: as many as the workspace budget and one launch hold (every launch is one-dimensional and
+    holds fewer than 2^31 blocks: one per 8 rows x 1024 channels in the frequency pass, one per 4 (row, chunk) lines
+    in its level pass, one per 256 samples in the scalar apply pass)."""
+    lim = (1 << 31) - 1
+    strips = -(-nchan // 1024)
+    batch = max(1, min(n_win, lim // (ntime * strips), lim // -(-nchan // 32), lim // (ntime * (n_ends - 1)),
+                       lim // -(-(ntime * nchan) // 256)))
+    if max_windows:
+        batch = max(1, min(batch, int(max_windows)))
+    budget = _workspace_budget(torch, device)
+    while batch > 1 and lib.tri_local_deviation_workspace_bytes(batch, ntime, nchan, n_ends) > budget:
+        batch = (batch + 1) // 2
+    return batch, lib.tri_local_deviation_workspace_bytes(batch, ntime, nchan, n_ends)
+
+
+def local_deviation(vis, flags, window_time=3, window_freq=3, _max_windows=None):
+    """Sliding-window complex deviation of (bl, corr, time, chan) windows: for
+    every sample the RMS of the complex deviations from their mean of the
+    unflagged, non-NaN samples among the ``window`` samples around it, along
+    time (``d_time``) and along frequency (``d_freq``), in float64 in a fixed
+    order, stored as float32 (float32 input: amplitudes, ``im = 0``).  NaN
+    where the sample itself does not count or fewer than 2 samples of its
+    window do; ``+inf`` where a counting sample of the window has an infinite
+    part.  Definition: ``include/tricolour_amd.h``.  Returns ``(d_time,
+    d_freq)`` of the shape of ``vis`` -- numpy arrays for numpy input, tensors
+    on the device otherwise.  Inputs are not modified."""
+    window_time, window_freq = _ldev_window("window_time", window_time), _ldev_window("window_freq", window_freq)
+    torch, v, f8, code, from_numpy, device = _line_rms_inputs("local_deviation", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    d_t = torch.empty(v.shape, dtype=torch.float32, device=device)
+    d_f = torch.empty(v.shape, dtype=torch.float32, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, _ = _ldev_batch(torch, lib, device, n_win, ntime, nchan, 2, _max_windows)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_local_deviation(
+                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
+                    window_time, window_freq, d_t.data_ptr() + w0 * per * 4, d_f.data_ptr() + w0 * per * 4, stream))
+    if from_numpy:
+        return d_t.cpu().numpy(), d_f.cpu().numpy()
+    return d_t, d_f
+
+
+def threshold_local_deviation(vis, flags, window_time=3, window_freq=3, scale_time=3.5, scale_freq=3.5, freq_chunks=10,
+                              _max_windows=None):
+    """Flags single samples of (bl, corr, time, chan) windows on the local
+    deviation of the COMPLEX visibility (after CASA's ``rflag``; the definition
+    is this library's own): :func:`local_deviation` gives ``d`` along each
+    axis; per (window, channel) along time, and per (window, time row,
+    frequency chunk) along frequency, the median ``med`` of the finite ``d`` is
+    the level, and a usable sample is flagged when ``d > scale * med`` (or when
+    ``d`` is ``+inf``).  A line with fewer than 3 finite values or ``med == 0``
+    flags nothing else.  ``freq_chunks``: the frequency chunks of
+    :func:`sum_threshold_flagger` (``linspace(0, nchan, freq_chunks + 1)``).
+    Both axes read the inputs: ``out = flags | hit_time | hit_freq``; a scale
+    of 0 switches an axis off.  Finds what the amplitude detectors cannot: a
+    signal that scrambles the phase and leaves ``|v|`` alone.  Returns a new
+    array in the container / dtype of ``flags``; the inputs are not modified."""
+    window_time, window_freq, scale_time, scale_freq, freq_chunks = check_local_deviation_kwargs(
+        window_time, window_freq, scale_time, scale_freq, freq_chunks)
+    torch, v, f8, code, from_numpy, device = _line_rms_inputs("threshold_local_deviation", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    ends = np.linspace(0, nchan, freq_chunks + 1).astype(np.int64)           # as the flagger's chunks (flagging.py:1172)
+    ends_c = (C.c_int64 * len(ends))(*[int(e) for e in ends])
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, nbytes = _ldev_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
+            ws = _workspace(torch, device, nbytes)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_local_deviation_threshold(
+                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per,
+                    out.data_ptr() + w0 * per, b, ntime, nchan, window_time, window_freq, scale_time, scale_freq,
+                    ends_c, len(ends), ws.data_ptr(), ws.numel(), stream))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
 def _bli_inputs(name, vis, flags, select):
     """Checks of the baseline-integration calls (all before any device work), then the device inputs:
     (torch, vis, flags uint8, dtype code, from_numpy, device, select uint8 on the device or None)."""

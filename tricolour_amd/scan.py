@@ -29,7 +29,8 @@ VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with
                "scale_invariant_rank_operator",                 # beyond the reference: flagging.scale_invariant_rank_operator
                "threshold_line_rms",                            # beyond the reference: flagging.threshold_line_rms
                "mark_missing",                                  # beyond the reference: the missing mask of masked SIR steps
-               "baseline_integrated_sum_threshold")             # beyond the reference: flagging.baseline_integrated_flagger
+               "baseline_integrated_sum_threshold",             # beyond the reference: flagging.baseline_integrated_flagger
+               "threshold_local_deviation")                     # beyond the reference: flagging.threshold_local_deviation
 
 # steps that need every baseline of the scan at once: they cannot run per baseline chunk
 WHOLE_SCAN_TASKS = ("baseline_integrated_sum_threshold",)
@@ -108,7 +109,9 @@ def check_strategies(strategies):
     ``missing`` is not ``none`` / ``input`` / ``marked`` or is ``marked`` with
     no ``mark_missing`` step before it, or for a
     ``baseline_integrated_sum_threshold`` step whose ``min_baseline_frac`` lies
-    outside [0, 1]."""
+    outside [0, 1], or for a ``threshold_local_deviation`` step with a window
+    that is even or outside [3, 31], a scale that is negative or NaN, or
+    ``freq_chunks < 1``."""
     marked = False
     for strategy in strategies:
         try:
@@ -133,6 +136,17 @@ def check_strategies(strategies):
                 ok = False
             if not ok:
                 raise ValueError("baseline_integrated_sum_threshold: min_baseline_frac must lie in [0, 1], got %r" % (frac,))
+        elif task == "threshold_local_deviation":
+            from tricolour_amd import flagging
+            kw = strategy.get('kwargs') or {}
+            names = ("window_time", "window_freq", "scale_time", "scale_freq", "freq_chunks")
+            unknown = sorted(set(kw) - set(names))
+            if unknown:
+                raise ValueError("threshold_local_deviation: unknown kwargs %s" % unknown)
+            try:
+                flagging.check_local_deviation_kwargs(**kw)
+            except ValueError as e:
+                raise ValueError("threshold_local_deviation: %s" % e)
 
 
 def _check_whole_scan_tasks(strategies, baseline_chunks):

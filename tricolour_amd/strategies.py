@@ -57,6 +57,9 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
         elif task == "threshold_line_rms":
             new_flags = flagging.threshold_line_rms(vis_windows, flag_windows, **kw)
             flag_windows = lor(new_flags, flag_windows)
+        elif task == "threshold_local_deviation":
+            new_flags = flagging.threshold_local_deviation(vis_windows, flag_windows, **kw)
+            flag_windows = lor(new_flags, flag_windows)
         elif task == "baseline_integrated_sum_threshold":
             kw = dict(kw)
             select = None
