@@ -501,6 +501,100 @@ int tri_local_deviation_threshold(const void *vis, int vis_dtype, const uint8_t 
                                   const int64_t *chunk_ends, int64_t n_chunk_ends,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Sky-subtracted incoherent noise spectrum (beyond the reference; the model is
+ * SSINS, Wilensky et al. 2019; the definition below is this library's own and
+ * identity with SSINS is not claimed: the level of a channel is the median
+ * over time, not the mean, so every time row is judged in the same round, and
+ * matched sums are taken on fixed-point z-scores in integer arithmetic, so
+ * the result has the same bits for every reduction order).  Every baseline's
+ * visibilities are differenced along time: sky and fringe vary slowly and
+ * cancel, noise and whatever changed between two dumps remain.  The amplitudes
+ * of the differences are averaged over baselines; their distribution is a
+ * Rayleigh mixture whose sigma is tied to its mean, so a z-score needs no
+ * background fit.
+ *
+ * Inputs.  vis (nbl, ncorr, ntime, nchan) complex64, or float32 amplitudes
+ * taken as re = a, im = 0; flags uint8 of the same shape, nonzero = flagged;
+ * select[nbl] uint8 on the device (nonzero = the baseline takes part) or NULL
+ * for all.  nd = ntime - 1 difference rows; the image has ncorr * nd * nchan
+ * positions i = (k, t, c).
+ *
+ * 1. Accumulate (tri_ins_accumulate), for the pair (t, t + 1), t in [0, nd):
+ *    dr = re[t+1] - re[t], di = im[t+1] - im[t] in float32;
+ *    d  = the flagger's amplitude of (dr, di): +inf if either part is
+ *         infinite, otherwise (float)sqrt((double)dr * dr + (double)di * di);
+ *    the pair counts if its baseline is selected, both flags are 0 and d is
+ *    not NaN; for b = 0 .. nbl - 1 in that order sum[i] += (double)d,
+ *    count[i] += 1.  The call ADDS to sum (float64) and count (int32), which
+ *    the caller zeroes first: baselines fed over several calls in ascending
+ *    order give the bits of one call.  No atomics; one order per position,
+ *    whatever the grid.
+ * 2. z-score image, given a mask image (ncorr, nd, nchan) uint8 of earlier
+ *    detections (all 0 in the first round):
+ *    usable = count >= min_count (the caller computes min_count = max(1,
+ *             ceil(min_baseline_frac * selected)), as for baseline integration);
+ *    x      = (float)(sum / (double)count);
+ *    the level med of line (k, c) is the median of the finite x over its
+ *    usable, unmasked rows, m values in all: the middle one for odd m,
+ *    float32(a + b) / 2 of the two middle ones for even m (the sum rounded to
+ *    float32).  The line is live iff m >= 3 and med > 0.
+ *    valid  = usable && !mask && live;
+ *    z      = ((double)x / (double)med - 1.0) * sqrt((double)count / C),
+ *             C = 0.2732395447351628 (4 / pi - 1);
+ *    q      = 2^30 if x == +inf, otherwise (int32)rint(clamp(z, -16384, 16384)
+ *             * 65536), ties to even; an invalid position has q = 0 and is
+ *             never summed.
+ *    tri_ins_zscore writes one round's level (ncorr, nchan) float32 (NaN
+ *    0x7FC00000 for a line with m == 0), q int32 and valid uint8 (0/1).
+ *    (sum is a sum of amplitudes and so never negative or NaN.)
+ * 3. Match, per row (k, t), all comparisons strict: for shape i in index order
+ *    with channels [lo_i, hi_i), m = the valid positions in the range; a shape
+ *    with m == 0 is skipped; S = sum of q in int64, r_i = ((double)S / 65536.0)
+ *    / sqrt((double)m) / nsigma_i.  After the shapes, if nsigma_narrow > 0, the
+ *    valid position with the largest q, lowest channel on ties, gives
+ *    r = ((double)q / 65536.0) / nsigma_narrow.  The row's pick is the first
+ *    candidate with the largest r, and only if r > 1; its whole channel range
+ *    (for narrow: the one position) is set in the mask.  One-sided: RFI adds
+ *    power.
+ * 4. Rounds.  tri_ins_match zeroes mask and runs steps 2 and 3 `rounds` times,
+ *    each round on the mask the previous rounds left.  The number is fixed and
+ *    nothing is read back to the host; a round that finds nothing changes
+ *    nothing.  shape_lo / shape_hi / shape_nsigma are HOST arrays of n_shapes
+ *    entries, read before the call returns.
+ * 5. Apply (tri_ins_apply): out[b,k,t,c] = (flags[b,k,t,c] != 0) |
+ *    (mask[k,t-1,c] != 0) | (mask[k,t,c] != 0), rows outside [0, nd) counting
+ *    as 0, for every baseline, the unselected ones included; out may be flags
+ *    itself.  ntime < 2: out = (flags != 0), with no other launch.
+ *
+ * At most 32 shapes, 0 <= lo < hi <= nchan, nsigma_i > 0, nsigma_narrow >= 0
+ * (0 = no narrow candidate), rounds in [1, 16], min_count >= 1.  TRI_EINVAL
+ * for violations, NULL pointers (other than select, and the shape arrays when
+ * n_shapes == 0), negative sizes or overlapping outputs; TRI_EUNSUPPORTED for
+ * dtypes other than complex64 and float32; TRI_EWORKSPACE when
+ * workspace_bytes < tri_ins_workspace_bytes().  Empty shapes (for all but
+ * tri_ins_apply that includes ntime < 2) return TRI_OK without a launch.
+ * Input buffers are never written.  No floating-point atomics.
+ */
+int tri_ins_accumulate(const void *vis, int vis_dtype, const uint8_t *flags,
+                       const uint8_t *select /* may be NULL */, int64_t nbl,
+                       int64_t ncorr, int64_t ntime, int64_t nchan, double *sum,
+                       int32_t *count, void *stream);
+size_t tri_ins_workspace_bytes(int64_t ncorr, int64_t ntime, int64_t nchan);
+int tri_ins_zscore(const double *sum, const int32_t *count, const uint8_t *mask,
+                   int64_t ncorr, int64_t ntime, int64_t nchan, int64_t min_count,
+                   float *level, int32_t *q, uint8_t *valid, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int tri_ins_match(const double *sum, const int32_t *count, int64_t ncorr,
+                  int64_t ntime, int64_t nchan, int64_t min_count,
+                  const int64_t *shape_lo, const int64_t *shape_hi,
+                  const double *shape_nsigma, int64_t n_shapes, double nsigma_narrow,
+                  int64_t rounds, uint8_t *mask, void *workspace,
+                  size_t workspace_bytes, void *stream);
+int tri_ins_apply(const uint8_t *flags, const uint8_t *mask, uint8_t *out,
+                  int64_t nbl, int64_t ncorr, int64_t ntime, int64_t nchan,
+                  void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

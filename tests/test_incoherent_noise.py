@@ -1,0 +1,1111 @@
+"""Sky-subtracted incoherent noise spectrum: the NumPy restatement of the
+definition (``include/tricolour_amd.h``), its properties and the strategy
+plumbing on the CPU, and the device kernels against the restatement.
+
+No tolerance anywhere.  The arithmetic of the device is a float32 subtraction,
+the flagger's amplitude (exact products in float64, one rounding in the sum, a
+correctly rounded square root, one narrowing cast), a float64 sum over
+baselines in memory order -- the restatement's Python loop is that order
+exactly --, float64 divisions, a square root and a round-to-even for the
+fixed-point z-score, and integer sums.  Every step is a correctly rounded IEEE
+operation or exact on both sides, so sum bits, counts, level bits, q, valid,
+masks and flags must all be equal.  A difference means a wrong order, a
+contracted multiply-add or a wrong tie rule.
+
+This module also keeps the kernel table of ``tricolour_amd/csrc/steps/ins/``:
+KERNELS lists every ``__global__`` kernel there with each instantiation a
+launch site can produce; a CPU test holds it to the sources, and the last GPU
+test shows with the library's kernel log that every listed instantiation was
+launched by a call whose result was compared with the restatement."""
+import contextlib
+import ctypes as C
+import glob
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+TASK = "threshold_incoherent_noise_spectrum"
+STRIP = 8          # INS_STRIP of kernels_ins.hpp: difference rows per thread of the accumulate's strip form
+FILL = 131072      # INS_FILL: the strip form runs when ncorr * cdiv(ntime - 1, STRIP) * pieces per row reaches it
+RAYLEIGH_C = 0.2732395447351628
+
+# every __global__ kernel of csrc/steps/ins/ and its instantiations, in the spelling of the kernel log
+# (k_ins_accumulate<VD, VEC, STRIP, BU>: VD 0 = complex64, 1 = float32 amplitudes; <8, 1> strips, <1, 4> single rows)
+KERNELS = {
+    "k_ins_accumulate": {"k_ins_accumulate<%d, %d, %s>" % (vd, vec, form) for vd in (0, 1) for vec in (4, 1)
+                         for form in ("8, 1", "1, 4")},
+    "k_ins_mean": {"k_ins_mean"},
+    "k_ins_level": {"k_ins_level"},
+    "k_ins_zq": {"k_ins_zq"},
+    "k_ins_match": {"k_ins_match"},
+    "k_ins_apply": {"k_ins_apply<true>", "k_ins_apply<false>"},
+}
+MET = set()        # instantiations launched by calls whose results equalled the restatement
+
+
+# ---------------------------------------------------------------------------
+# the definition, restated
+# ---------------------------------------------------------------------------
+def difference_amplitude(vis):
+    """float32 (nbl, ncorr, ntime - 1, nchan): the flagger's amplitude of the float32 difference of rows t + 1 and t."""
+    vis = np.asarray(vis)
+    if np.iscomplexobj(vis):
+        re, im = vis.real.astype(np.float32), vis.imag.astype(np.float32)
+    else:
+        re, im = vis.astype(np.float32), np.zeros(vis.shape, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dr = (re[:, :, 1:] - re[:, :, :-1]).astype(np.float64)
+        di = (im[:, :, 1:] - im[:, :, :-1]).astype(np.float64)
+        d = np.sqrt(dr * dr + di * di).astype(np.float32)
+    d[np.isinf(dr) | np.isinf(di)] = np.inf
+    return d
+
+
+def restate_accumulate(vis, flags, select=None, acc=None):
+    """(sum float64, count int32) of shape (ncorr, ntime - 1, nchan), the baselines in ascending order."""
+    d = difference_amplitude(vis)
+    f = np.asarray(flags) != 0
+    ok = ~f[:, :, 1:] & ~f[:, :, :-1] & ~np.isnan(d)
+    if select is not None:
+        ok &= (np.asarray(select) != 0)[:, None, None, None]
+    s = np.zeros(d.shape[1:], np.float64) if acc is None else acc[0].copy()
+    c = np.zeros(d.shape[1:], np.int32) if acc is None else acc[1].copy()
+    for b in range(d.shape[0]):
+        with np.errstate(invalid="ignore"):
+            s = np.where(ok[b], s + d[b].astype(np.float64), s)
+        c = c + ok[b].astype(np.int32)
+    return s, c
+
+
+def median_rule(values):
+    """The project's median of float32 values (at least one): the middle one, or float32(a + b) / 2."""
+    v = np.sort(np.asarray(values, np.float32))
+    m = v.size
+    if m % 2:
+        return v[m // 2]
+    with np.errstate(over="ignore"):
+        return np.float32(v[m // 2 - 1] + v[m // 2]) / np.float32(2)
+
+
+def restate_zscore(s, c, min_count, mask=None):
+    """(level float32 (ncorr, nchan), q int32, valid bool) of one round."""
+    ncorr, nd, nchan = s.shape
+    mask = np.zeros(s.shape, bool) if mask is None else np.asarray(mask) != 0
+    usable = c >= min_count
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        x = (s / c.astype(np.float64)).astype(np.float32)
+    enters = usable & ~mask & np.isfinite(x)
+    level = np.full((ncorr, nchan), np.nan, np.float32)
+    live = np.zeros((ncorr, nchan), bool)
+    for k in range(ncorr):
+        for ch in range(nchan):
+            vals = x[k, enters[k, :, ch], ch]
+            if vals.size:
+                level[k, ch] = median_rule(vals)
+                live[k, ch] = vals.size >= 3 and level[k, ch] > 0
+    valid = usable & ~mask & live[:, None, :]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        z = (x.astype(np.float64) / level.astype(np.float64)[:, None, :] - 1.0) * np.sqrt(c.astype(np.float64) / RAYLEIGH_C)
+    z = np.where(valid & np.isfinite(x), z, 0.0)
+    q = np.rint(np.clip(z, -16384.0, 16384.0) * 65536.0).astype(np.int32)
+    q[valid & np.isposinf(x)] = 1 << 30
+    q[~valid] = 0
+    return level, q, valid
+
+
+def match_row(q, valid, shapes, nsigma_narrow):
+    """(lo, hi) of the pick of one row, or None."""
+    best, pick = 1.0, None
+    for lo, hi, ns in shapes:
+        m = int(valid[lo:hi].sum())
+        if m == 0:
+            continue
+        total = int(q[lo:hi][valid[lo:hi]].astype(np.int64).sum())
+        r = (float(total) / 65536.0) / math.sqrt(float(m)) / ns
+        if r > best:
+            best, pick = r, (lo, hi)
+    if nsigma_narrow > 0 and valid.any():
+        qv = np.where(valid, q.astype(np.int64), -(1 << 40))
+        ch = int(np.argmax(qv))                               # the first of equal maxima: the lowest channel
+        r = (float(q[ch]) / 65536.0) / nsigma_narrow
+        if r > best:
+            best, pick = r, (ch, ch + 1)
+    return pick
+
+
+def restate_match(s, c, min_count, shapes, nsigma_narrow, rounds):
+    """The mask (ncorr, ntime - 1, nchan) bool after `rounds` rounds; shapes: [(lo, hi, nsigma)]."""
+    mask = np.zeros(s.shape, bool)
+    for _ in range(rounds):
+        _, q, valid = restate_zscore(s, c, min_count, mask)
+        for k in range(s.shape[0]):
+            for t in range(s.shape[1]):
+                pick = match_row(q[k, t], valid[k, t], shapes, nsigma_narrow)
+                if pick:
+                    mask[k, t, pick[0]:pick[1]] = True
+    return mask
+
+
+def restate_apply(flags, mask):
+    out = np.asarray(flags) != 0
+    if mask.shape[1]:
+        out = out.copy()
+        out[:, :, 1:] |= (np.asarray(mask) != 0)[None]        # difference row t - 1
+        out[:, :, :-1] |= (np.asarray(mask) != 0)[None]       # difference row t
+    return out
+
+
+def min_count(frac, n_selected):
+    return max(1, int(math.ceil(frac * n_selected)))
+
+
+def n_selected(nbl, select):
+    return nbl if select is None else int((np.asarray(select) != 0).sum())
+
+
+def step_shapes(nchan, nsigma=5.0, shapes=(), streak=True):
+    out = [(s[0], s[1], float(s[2]) if len(s) == 3 else float(nsigma)) for s in shapes]
+    if streak:
+        out.append((0, nchan, float(nsigma)))
+    return out
+
+
+def restate_step(vis, flags, select=None, min_baseline_frac=0.25, nsigma=5.0, shapes=(), streak=True, narrow=True,
+                 rounds=3, return_mask=False):
+    if vis.shape[2] < 2 or vis.size == 0:
+        out = np.asarray(flags) != 0
+        return (out, np.zeros((vis.shape[1], 0, vis.shape[3]), bool)) if return_mask else out
+    s, c = restate_accumulate(vis, flags, select)
+    mask = restate_match(s, c, min_count(min_baseline_frac, n_selected(vis.shape[0], select)),
+                         step_shapes(vis.shape[3], nsigma, shapes, streak), float(nsigma) if narrow else 0.0, rounds)
+    out = restate_apply(flags, mask)
+    return (out, mask) if return_mask else out
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    view = {8: np.uint64, 4: np.uint32, 1: np.uint8}[a.dtype.itemsize]
+    return np.array_equal(a.view(view), b.view(view))
+
+
+# ---------------------------------------------------------------------------
+# inputs
+# ---------------------------------------------------------------------------
+# the issue's shapes (all of them take the single-row form), one more of 19 difference rows, and the smallest shape
+# that takes the strip form with 4 channels per thread: 25 difference rows -- no multiple of the strip of 8 and more
+# than two strips -- as 4 strips x 32768 pieces
+TALL = (2, 1, 26, 131072)
+SHAPES = [(1, 1, 1, 1), (1, 1, 2, 1), (2, 1, 2, 37), (3, 2, 5, 18), (5, 1, 9, 65), (9, 2, 7, 16), (17, 1, 4, 100),
+          (4, 2, 3, 4096), (3, 2, 20, 12), TALL]
+assert (TALL[2] - 1) % STRIP and TALL[2] - 1 > 2 * STRIP and TALL[1] * -(-(TALL[2] - 1) // STRIP) * (TALL[3] // 4) == FILL
+assert all(s[1] * -(-(s[2] - 1) // STRIP) * s[3] < FILL for s in SHAPES[:-1])
+DENSITIES = [0.0, 0.1, 0.95, 1.0]
+SPECIALS = ["nan_re", "nan_im", "inf", "inf_both"]
+
+
+def make_case(shape, seed, density=0.1, dtype="c64", special=None):
+    rng = np.random.default_rng(seed)
+    if dtype == "c64":
+        vis = np.empty(shape, np.complex64)
+        vis.real = rng.standard_normal(shape, dtype=np.float32)
+        vis.imag = rng.standard_normal(shape, dtype=np.float32)
+    else:
+        vis = rng.standard_normal(shape, dtype=np.float32)
+    # levels over twelve decades per baseline: with these every partial sum rounds, so a changed order shows in the bits
+    vis *= (10.0 ** rng.uniform(-6.0, 6.0, size=(shape[0], 1, 1, 1))).astype(np.float32)
+    flags = rng.uniform(size=shape) < density if density < 1.0 else np.ones(shape, bool)
+    if special is not None:
+        hit = rng.uniform(size=shape) < 0.15
+        hit.reshape(-1)[0] = True
+        if special == "inf_both":                              # both members of a pair: inf - inf
+            hit[:, :, 1:] |= hit[:, :, :-1] & (rng.uniform(size=shape)[:, :, 1:] < 0.5)
+        if dtype == "c64":
+            value = {"nan_re": complex(np.nan, 1.0), "nan_im": complex(1.0, np.nan), "inf": complex(-np.inf, 2.0),
+                     "inf_both": complex(np.inf, 1.0)}[special]
+        else:
+            value = {"nan_re": np.nan, "nan_im": np.nan, "inf": -np.inf, "inf_both": np.inf}[special]
+        vis[hit] = value
+    return vis, flags
+
+
+def accumulate_cases():
+    out = []
+    for i, shape in enumerate(SHAPES):
+        for k, dt in enumerate(("c64", "f32")):
+            out.append(dict(shape=shape, dtype=dt, density=DENSITIES[(i + 2 * k) % 4], seed=100 + 2 * i + k))
+    for i, sp in enumerate(SPECIALS):
+        for k, dt in enumerate(("c64", "f32")):
+            out.append(dict(shape=SHAPES[4 + (i + k) % 2], dtype=dt, density=0.1, special=sp, seed=200 + 2 * i + k))
+    for i, shape in enumerate([(5, 1, 9, 65), (9, 2, 7, 16), (17, 1, 4, 100)]):
+        out.append(dict(shape=shape, dtype=("c64", "f32")[i % 2], density=0.1, select="some", seed=300 + i))
+        out.append(dict(shape=shape, dtype=("f32", "c64")[i % 2], density=0.1, select="none", seed=310 + i))
+    out.append(dict(shape=(3, 1, 4, 8), dtype="c64", density=1.0, seed=320))
+    out.append(dict(shape=(3, 2, 20, 12), dtype="f32", density=0.95, seed=321))
+    out.append(dict(shape=TALL, dtype="c64", density=0.1, special="inf_both", select="some", seed=322))
+    return out
+
+
+def case_id(c):
+    return "-".join(["x".join(map(str, c["shape"])), c["dtype"], "d%g" % c["density"]] +
+                    [str(c[k]) for k in ("special", "select") if c.get(k)])
+
+
+def build(c):
+    vis, flags = make_case(c["shape"], c["seed"], c["density"], c["dtype"], c.get("special"))
+    select = None
+    if c.get("select") == "some":
+        select = np.random.default_rng(c["seed"] + 1).uniform(size=c["shape"][0]) < 0.6
+        select[0], select[-1] = False, True
+    elif c.get("select") == "none":
+        select = np.zeros(c["shape"][0], bool)
+    return vis, flags, select
+
+
+def synthetic_image(shape, seed, nbl=40, noise=0.02):
+    """(sum, count) of an image whose mean amplitudes scatter by `noise` around one level per channel."""
+    rng = np.random.default_rng(seed)
+    c = rng.integers(nbl // 2, nbl + 1, size=shape).astype(np.int32)
+    level = rng.uniform(0.5, 2.0, size=(shape[0], 1, shape[2]))
+    x = level * (1.0 + noise * rng.standard_normal(shape))
+    return x * c, c
+
+
+BURST_SHAPES = [(0, 128), (40, 72), (8, 24)]
+BURST_KW = dict(nsigma=5.0, shapes=BURST_SHAPES, streak=False, narrow=True, rounds=3, min_baseline_frac=0.25)
+BURST_SEEDS = [0, 1, 2, 3, 4, 5]
+_CACHE = {}
+
+
+def burst_input(seed, burst):
+    """45 baselines x 1 x 32 x 128: unit complex Gaussian noise plus a constant of amplitude 3 with one phase per
+    baseline; burst: amplitude 1.0 with a random phase per baseline at time 10 in channels 40..71."""
+    rng = np.random.default_rng(seed)
+    shape = (45, 1, 32, 128)
+    vis = rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+    vis = vis + 3.0 * np.exp(2j * np.pi * rng.uniform(size=45))[:, None, None, None]
+    if burst:
+        vis[:, 0, 10, 40:72] += np.exp(2j * np.pi * rng.uniform(size=45))[:, None]
+    return vis.astype(np.complex64), np.zeros(shape, bool)
+
+
+def burst_expected(seed, burst):
+    """(vis, flags, restated output, restated mask); computed once per process and left unchanged."""
+    key = (seed, burst)
+    if key not in _CACHE:
+        vis, flags = burst_input(seed, burst)
+        s, c = restate_accumulate(vis, flags)
+        mask = restate_match(s, c, min_count(0.25, 45), [(lo, hi, 5.0) for lo, hi in BURST_SHAPES], 5.0, 3)
+        _CACHE[key] = (vis, flags, restate_apply(flags, mask), mask)
+    return _CACHE[key]
+
+
+def small_scan(rs, na=5, ntime=24, nchan=64, ncorr=2):
+    """Rows of a full scan of `na` antennas with autos, in time order; a burst at time 7 in channels 20..35."""
+    a1, a2 = np.triu_indices(na, 0)
+    nbl = len(a1)
+    ant1 = np.tile(a1, ntime).astype(np.int32)
+    ant2 = np.tile(a2, ntime).astype(np.int32)
+    tm = np.repeat(1e9 + 2.0 * np.arange(ntime), nbl)
+    shape = (ant1.size, nchan, ncorr)
+    data = (rs.standard_normal(shape) + 1j * rs.standard_normal(shape)).astype(np.complex64)
+    rows = slice(7 * nbl, 8 * nbl)
+    data[rows, 20:36, :] += np.exp(2j * np.pi * rs.uniform(size=(nbl, 1, 1))).astype(np.complex64) * np.float32(4)
+    flag = rs.uniform(size=shape) < 0.03
+    return data, flag, ant1, ant2, tm, np.linspace(1e9, 1.1e9, nchan), np.full(nchan, 1e5)
+
+
+# ---------------------------------------------------------------------------
+# CPU: the restatement
+# ---------------------------------------------------------------------------
+def hypot_scalar(dr, di):
+    if math.isinf(dr) or math.isinf(di):
+        return np.float32(np.inf)
+    return np.float32(math.sqrt(float(dr) * float(dr) + float(di) * float(di)))
+
+
+def test_restatement_equals_a_per_position_loop():
+    vis, flags = make_case((4, 2, 5, 7), 1, 0.2, special="inf_both")
+    vis[1, 0, 2, 3] = complex(np.nan, 1.0)
+    select = np.array([1, 1, 0, 1], bool)
+    s, c = restate_accumulate(vis, flags, select)
+    nbl, ncorr, ntime, nchan = vis.shape
+    for k in range(ncorr):
+        for t in range(ntime - 1):
+            for ch in range(nchan):
+                es, ec = 0.0, 0
+                for b in range(nbl):
+                    a, z = vis[b, k, t, ch], vis[b, k, t + 1, ch]
+                    with np.errstate(invalid="ignore"):
+                        d = hypot_scalar(np.float32(z.real) - np.float32(a.real), np.float32(z.imag) - np.float32(a.imag))
+                    if select[b] and not flags[b, k, t, ch] and not flags[b, k, t + 1, ch] and not np.isnan(d):
+                        es, ec = es + float(d), ec + 1
+                assert ec == c[k, t, ch] and np.float64(es).tobytes() == s[k, t, ch].tobytes(), (k, t, ch)
+    # one round's image and the match, position by position
+    s, c = synthetic_image((2, 6, 9), 2)
+    s[0, 1, 4] *= 1.5
+    c[1, 2, 3] = 1
+    mask = np.zeros(s.shape, bool)
+    mask[0, 0, 0] = True
+    level, q, valid = restate_zscore(s, c, 5, mask)
+    for k in range(2):
+        for ch in range(9):
+            xs = [np.float32(s[k, t, ch] / float(c[k, t, ch])) for t in range(6) if c[k, t, ch] >= 5 and not mask[k, t, ch]]
+            med = median_rule(xs)
+            assert level[k, ch].tobytes() == med.tobytes()
+            for t in range(6):
+                ok = c[k, t, ch] >= 5 and not mask[k, t, ch] and len(xs) >= 3 and med > 0
+                assert valid[k, t, ch] == ok
+                if ok:
+                    x = np.float32(s[k, t, ch] / float(c[k, t, ch]))
+                    z = (float(x) / float(med) - 1.0) * math.sqrt(float(c[k, t, ch]) / RAYLEIGH_C)
+                    assert q[k, t, ch] == int(np.rint(min(max(z, -16384.0), 16384.0) * 65536.0))
+                else:
+                    assert q[k, t, ch] == 0
+    assert q[0, 1, 4] > 3 * 65536 and not valid[1, 2, 3] and not valid[0, 0, 0]
+
+
+def test_restatement_pieces_equal_the_whole_bit_for_bit():
+    vis, flags = make_case((45, 2, 6, 33), 3, 0.2)
+    whole = restate_accumulate(vis, flags)
+    acc = None
+    for b0 in range(0, 45, 7):
+        acc = restate_accumulate(vis[b0:b0 + 7], flags[b0:b0 + 7], acc=acc)
+    assert same_bits(acc[0], whole[0]) and np.array_equal(acc[1], whole[1])
+    # the order matters: the reversed sum differs somewhere, so the test above is not vacuous
+    back = restate_accumulate(vis[::-1], flags[::-1])
+    assert np.array_equal(back[1], whole[1]) and not same_bits(back[0], whole[0])
+
+
+def test_restatement_select_equals_deleting_baselines():
+    vis, flags = make_case((9, 2, 5, 21), 4, 0.2)
+    select = np.array([1, 0, 1, 1, 0, 0, 1, 0, 1], bool)
+    a = restate_accumulate(vis, flags, select)
+    b = restate_accumulate(vis[select], flags[select])
+    assert same_bits(a[0], b[0]) and np.array_equal(a[1], b[1])
+    kw = dict(min_baseline_frac=0.5, nsigma=3.0, shapes=[(2, 9)])
+    assert np.array_equal(restate_step(vis, flags, select, **kw)[select], restate_step(vis[select], flags[select], **kw))
+
+
+@pytest.mark.parametrize("dtype", ["c64", "f32"])
+def test_restatement_constant_sky_of_any_size_cancels_exactly(dtype):
+    rng = np.random.default_rng(5)
+    shape = (6, 2, 7, 11)
+    sky = (10.0 ** rng.uniform(-20, 20, size=(6, 2, 1, 11))).astype(np.float32)
+    if dtype == "c64":
+        sky = (sky * np.exp(2j * np.pi * rng.uniform(size=sky.shape))).astype(np.complex64)
+    vis = np.broadcast_to(sky, shape).copy()
+    s, c = restate_accumulate(vis, np.zeros(shape, bool))
+    assert not s.any() and (c == 6).all() and same_bits(s, np.zeros(s.shape))
+    level, q, valid = restate_zscore(s, c, 1)
+    assert not level.any() and not valid.any() and not q.any()          # a level of 0: no line is live
+
+
+def test_restatement_flagged_and_nan_members_remove_the_pair():
+    vis, flags = make_case((4, 1, 4, 8), 6, 0.0)
+    flags[1, 0, 1, 2] = True
+    vis[1, 0, 1, 2] = 1e30                      # flagged: must not be seen, in either pair
+    vis[2, 0, 0, 5] = complex(np.nan, 1.0)
+    vis[3, 0, 3, 5] = complex(2.0, np.nan)
+    vis[0, 0, 2, 7] = complex(np.inf, 1.0)      # an infinite difference counts as +inf ...
+    vis[1, 0, 2, 6] = vis[1, 0, 3, 6] = complex(np.inf, 0.0)    # ... but inf - inf is NaN and removes the pair
+    s, c = restate_accumulate(vis, flags)
+    assert c[0, 0, 2] == 3 and c[0, 1, 2] == 3 and c[0, 2, 2] == 4
+    assert c[0, 0, 5] == 3 and c[0, 1, 5] == 4 and c[0, 2, 5] == 3
+    assert c[0, 1, 7] == 4 and c[0, 2, 7] == 4 and np.isposinf(s[0, 1, 7]) and np.isposinf(s[0, 2, 7])
+    assert c[0, 2, 6] == 3 and np.isfinite(s[0, 2, 6]) and np.isposinf(s[0, 1, 6])
+    assert s[0, 0, 2] < 1e20 and np.isfinite(s[0, 0, 5])
+    assert c.sum() == 4 * 24 - 5
+
+
+def test_restatement_rounds_do_something():
+    """A row with a band and a separate spike: one round takes the band, the second the spike."""
+    s, c = synthetic_image((1, 12, 64), 7, noise=0.002)
+    x = s / c
+    x[0, 5, 10:30] *= 1.3
+    x[0, 5, 50] *= 2.0
+    s = x * c
+    shapes = [(10, 30, 5.0), (0, 64, 5.0)]
+    one, two = restate_match(s, c, 1, shapes, 5.0, 1), restate_match(s, c, 1, shapes, 5.0, 2)
+    band = np.zeros(s.shape, bool)
+    band[0, 5, 10:30] = True
+    both = band.copy()
+    both[0, 5, 50] = True
+    assert np.array_equal(one, band) and np.array_equal(two, both)
+    assert np.array_equal(restate_match(s, c, 1, shapes, 5.0, 16), both)      # a round that finds nothing changes nothing
+
+
+def test_min_count_follows_the_formula():
+    assert [min_count(f, n) for f, n in [(0.0, 45), (0.25, 45), (1.0, 45), (0.25, 0), (0.5, 1), (0.25, 4), (0.26, 4)]] == \
+        [1, 12, 45, 1, 1, 1, 2]
+
+
+@pytest.mark.parametrize("seed", BURST_SEEDS)
+def test_behaviour_noise_alone_gives_no_detection(seed):
+    vis, flags, out, mask = burst_expected(seed, False)
+    assert not mask.any() and not out.any()
+
+
+@pytest.mark.parametrize("seed", BURST_SEEDS)
+def test_behaviour_faint_burst_is_found_exactly(seed):
+    """Amplitude 1.0 on unit noise with another phase on every baseline: below any single-baseline threshold."""
+    vis, flags, out, mask = burst_expected(seed, True)
+    exp = np.zeros(mask.shape, bool)
+    exp[0, 9:11, 40:72] = True
+    assert np.array_equal(mask, exp)
+    flagged = np.zeros(vis.shape, bool)
+    flagged[:, 0, 9:12, 40:72] = True
+    assert np.array_equal(out, flagged)
+
+
+# ---------------------------------------------------------------------------
+# CPU: plumbing
+# ---------------------------------------------------------------------------
+def test_the_task_is_valid_and_checked():
+    from tricolour_amd import scan
+    assert TASK in scan.VALID_TASKS and TASK in scan.WHOLE_SCAN_TASKS
+    scan.check_strategies([{"task": "flag_autos"}, {"task": TASK}, {"task": TASK, "kwargs": {}},
+                           {"task": TASK, "kwargs": {"min_baseline_frac": 0.5, "nsigma": 4, "rounds": 16, "streak": False,
+                                                     "narrow": False, "exclude_autos": False,
+                                                     "shapes": [[0, 4], [3, 9, 6.5]], "bands_hz": [[1e9, 1.1e9]]}}])
+    bad = [dict(min_baseline_frac=-0.01), dict(min_baseline_frac=1.01), dict(min_baseline_frac=float("nan")),
+           dict(min_baseline_frac="half"), dict(nsigma=0), dict(nsigma=-1.0), dict(nsigma=float("nan")),
+           dict(nsigma=float("inf")), dict(nsigma="5"), dict(rounds=0), dict(rounds=17), dict(rounds=2.5), dict(rounds=True),
+           dict(streak=1), dict(narrow="yes"), dict(exclude_autos=0), dict(shapes=[[4, 4]]), dict(shapes=[[-1, 4]]),
+           dict(shapes=[[5, 2]]), dict(shapes=[[0, 4, 0.0]]), dict(shapes=[[0.5, 4]]), dict(shapes=[[0]]), dict(shapes=7),
+           dict(shapes=[[0, 1]] * 32), dict(shapes=[[0, 1]] * 33, streak=False), dict(bands_hz=[[2e9, 1e9]]),
+           dict(bands_hz=[[1e9]]), dict(bands_hz=[[1e9, float("nan")]]), dict(bands_hz=5),
+           dict(shapes=[[0, 1]] * 30, bands_hz=[[1e9, 2e9]] * 2), dict(window=3), dict(outlier_nsigma=4.0)]
+    for kw in bad:
+        with pytest.raises(ValueError, match=TASK):
+            scan.check_strategies([{"task": TASK, "kwargs": kw}])
+    scan.check_strategies([{"task": TASK, "kwargs": dict(shapes=[[0, 1]] * 32, streak=False)}])
+
+
+def test_check_kwargs_returns_the_values():
+    from tricolour_amd import flagging
+    assert flagging.check_incoherent_noise_kwargs() == (0.25, 5.0, [], True, True, 3)
+    got = flagging.check_incoherent_noise_kwargs(0.5, 4, [(0, 4), [3, 9, 6.5]], False, False, 1)
+    assert got == (0.5, 4.0, [(0, 4, 4.0), (3, 9, 6.5)], False, False, 1)
+
+
+def test_bands_become_channel_ranges_on_the_host():
+    from tricolour_amd import flagging
+    freq = 1e9 + 1e6 * np.arange(16)
+    bands = [[1.0025e9, 1.0055e9], [1.003e9, 1.003e9], [0.5e9, 0.9e9], [1.0101e9, 1.0109e9], [0.9e9, 2e9], [1.015e9, 3e9]]
+    assert flagging.incoherent_noise_bands(bands, freq) == [(3, 6), (3, 4), (0, 16), (15, 16)]
+    assert flagging.incoherent_noise_bands(bands[:1], freq[::-1]) == [(10, 13)]        # a descending axis
+    assert flagging.incoherent_noise_bands(bands[:1], freq.reshape(1, 16)) == [(3, 6)]
+
+
+def test_apply_strategies_needs_ubl_and_chan_freq():
+    from tricolour_amd.strategies import apply_strategies
+    vis, flags = make_case((3, 1, 4, 8), 8)
+    with pytest.raises(ValueError, match="ubl"):
+        apply_strategies([{"task": TASK}], flags, vis)
+    with pytest.raises(ValueError, match="ubl"):
+        apply_strategies([{"task": TASK, "kwargs": {"exclude_autos": True}}], flags, vis)
+    with pytest.raises(ValueError, match="chan_freq"):
+        apply_strategies([{"task": TASK, "kwargs": {"exclude_autos": False, "bands_hz": [[1e9, 2e9]]}}], flags, vis)
+
+
+def test_flag_scan_with_baseline_chunks_refuses_the_step_before_any_device_work():
+    from tricolour_amd import scan
+    rs = np.random.RandomState(0)
+    args = small_scan(rs, na=3, ntime=8, nchan=40, ncorr=2)
+    strategies = [{"task": "flag_autos"}, {"task": TASK, "kwargs": {"rounds": 1}}]
+    with pytest.raises(ValueError, match=TASK):
+        scan.flag_scan(*args, strategies, baseline_chunks=4)
+    ds = dict(DATA=args[0], FLAG=args[1], ANTENNA1=args[2], ANTENNA2=args[3], TIME=args[4], CHAN_FREQ=args[5],
+              CHAN_WIDTH=args[6], FIELD_ID=0, DATA_DESC_ID=0, SCAN_NUMBER=1)
+    with pytest.raises(ValueError, match=TASK):
+        scan.flag_scans([ds], strategies, baseline_chunks=4)
+    with pytest.raises(ValueError, match="rounds"):                 # the kwargs are checked first
+        scan.flag_scan(*args, [{"task": TASK, "kwargs": {"rounds": 0}}], baseline_chunks=4)
+
+
+ENTRY_POINTS = ("tri_ins_accumulate", "tri_ins_workspace_bytes", "tri_ins_zscore", "tri_ins_match", "tri_ins_apply")
+
+
+def test_header_declares_and_the_binding_exports_the_entry_points():
+    from tricolour_amd import _lib
+    with open(os.path.join(ROOT, "include", "tricolour_amd.h")) as fh:
+        text = fh.read()
+    hdr = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for name in ENTRY_POINTS:
+        assert re.search(r"\b(int|size_t)\s+%s\s*\(" % name, hdr), name
+        assert name in _lib.EXPORTS
+        assert hasattr(_lib.lib(), name)
+    assert _lib.lib().tri_version() >= 105
+    assert os.path.join(ROOT, "tricolour_amd", "csrc", "steps", "ins", "kernels_ins.hpp") in _lib.DEPENDS
+    # the contract is written there: the constant, the fixed point and the median rule
+    for phrase in ("0.2732395447351628", "65536", "float32(a + b) / 2", "identity with SSINS is not claimed"):
+        assert phrase in re.sub(r"\s*\n \*\s*", " ", text), phrase
+
+
+def test_abi_rejects_bad_arguments_without_a_launch():
+    from tricolour_amd import _lib
+    lib = _lib.lib()
+    buf = (C.c_uint8 * 65536)()
+    base = C.addressof(buf)
+    v, f, s, c, m, o = base, base + 8192, base + 16384, base + 24576, base + 32768, base + 40960
+    lv, q, vd = base + 49152, base + 53248, base + 57344
+    lo, hi, ns = (C.c_int64 * 33)(*([0] * 33)), (C.c_int64 * 33)(*([4] * 33)), (C.c_double * 33)(*([5.0] * 33))
+
+    def acc(vis=v, dtype=_lib.TRI_VIS_C64, flags=f, select=None, nbl=2, ncorr=1, ntime=3, nchan=8, sum_=s, count=c):
+        return lib.tri_ins_accumulate(vis, dtype, flags, select, nbl, ncorr, ntime, nchan, sum_, count, None)
+
+    def zs(sum_=s, count=c, mask=m, ncorr=1, ntime=3, nchan=8, mc=1, level=lv, q_=q, valid=vd, ws=o, wsb=0):
+        return lib.tri_ins_zscore(sum_, count, mask, ncorr, ntime, nchan, mc, level, q_, valid, ws, wsb, None)
+
+    def match(sum_=s, count=c, ncorr=1, ntime=3, nchan=8, mc=1, lo_=lo, hi_=hi, ns_=ns, n=2, narrow=5.0, rounds=3, mask=m,
+              ws=o, wsb=0):
+        return lib.tri_ins_match(sum_, count, ncorr, ntime, nchan, mc, lo_, hi_, ns_, n, narrow, rounds, mask, ws, wsb, None)
+
+    def app(flags=f, mask=m, out=o, nbl=2, ncorr=1, ntime=3, nchan=8):
+        return lib.tri_ins_apply(flags, mask, out, nbl, ncorr, ntime, nchan, None)
+
+    for kw in (dict(vis=None), dict(flags=None), dict(sum_=None), dict(count=None), dict(nbl=-1), dict(ncorr=-1),
+               dict(ntime=-1), dict(nchan=-2), dict(count=s + 8), dict(count=s)):
+        assert acc(**kw) == _lib.TRI_EINVAL, kw
+    for dt in (_lib.TRI_VIS_C128, _lib.TRI_VIS_F64, 17, -1):
+        assert acc(dtype=dt) == _lib.TRI_EUNSUPPORTED
+    for kw in (dict(nbl=0), dict(ncorr=0), dict(nchan=0), dict(ntime=0), dict(ntime=1)):       # empty: no launch
+        assert acc(**kw) == _lib.TRI_OK, kw
+    assert lib.tri_ins_workspace_bytes(1, 3, 8) > 0
+    assert [lib.tri_ins_workspace_bytes(*a) for a in ((0, 3, 8), (1, 1, 8), (1, 3, 0), (-1, 3, 8))] == [0, 0, 0, 0]
+    assert lib.tri_ins_workspace_bytes(2, 1024, 4096) >= 2 * 1023 * 4096 * 9
+
+    for kw in (dict(sum_=None), dict(count=None), dict(mask=None), dict(level=None), dict(q_=None), dict(valid=None),
+               dict(ncorr=-1), dict(ntime=-1), dict(nchan=-1), dict(mc=0), dict(mc=-2), dict(q_=s), dict(valid=m),
+               dict(level=q), dict(valid=q + 4)):
+        assert zs(**kw) == _lib.TRI_EINVAL, kw
+    assert zs() == _lib.TRI_EWORKSPACE and zs(ws=None, wsb=1 << 20) == _lib.TRI_EWORKSPACE
+    assert zs(wsb=lib.tri_ins_workspace_bytes(1, 3, 8) - 1) == _lib.TRI_EWORKSPACE
+    for kw in (dict(ncorr=0), dict(nchan=0), dict(ntime=1), dict(ntime=0)):
+        assert zs(**kw) == _lib.TRI_OK, kw
+
+    hi9, lo4, ns0 = (C.c_int64 * 2)(4, 9), (C.c_int64 * 2)(0, 4), (C.c_double * 2)(5.0, 0.0)
+    neg, nan = (C.c_int64 * 2)(0, -1), (C.c_double * 2)(5.0, float("nan"))
+    for kw in (dict(sum_=None), dict(count=None), dict(mask=None), dict(ncorr=-1), dict(ntime=-1), dict(nchan=-1),
+               dict(mc=0), dict(n=33), dict(n=-1), dict(lo_=None), dict(hi_=None), dict(ns_=None), dict(hi_=hi9),
+               dict(lo_=lo4), dict(lo_=neg), dict(ns_=ns0), dict(ns_=nan), dict(narrow=-1.0), dict(narrow=float("nan")),
+               dict(rounds=0), dict(rounds=17), dict(mask=s + 3), dict(mask=c)):
+        assert match(**kw) == _lib.TRI_EINVAL, kw
+    assert match() == _lib.TRI_EWORKSPACE and match(n=0, lo_=None, hi_=None, ns_=None) == _lib.TRI_EWORKSPACE
+    assert match(n=32) == _lib.TRI_EWORKSPACE and match(narrow=0.0, rounds=16) == _lib.TRI_EWORKSPACE
+    for kw in (dict(ncorr=0), dict(nchan=0, hi_=lo, n=0), dict(ntime=1), dict(ntime=0)):
+        assert match(**kw) == _lib.TRI_OK, kw
+
+    for kw in (dict(flags=None), dict(mask=None), dict(out=None), dict(nbl=-1), dict(ncorr=-1), dict(ntime=-1),
+               dict(nchan=-1), dict(out=m), dict(out=m + 8), dict(out=m - 40), dict(out=f + 8), dict(out=f - 8)):
+        assert app(**kw) == _lib.TRI_EINVAL, kw
+    for kw in (dict(nbl=0), dict(ncorr=0), dict(ntime=0), dict(nchan=0)):
+        assert app(**kw) == _lib.TRI_OK, kw
+    assert app(out=m) == _lib.TRI_EINVAL and b"mask" in lib.tri_last_error()
+
+
+def test_python_argument_errors_come_before_any_device_work():
+    from tricolour_amd import flagging
+    vis = np.zeros((3, 1, 4, 8), np.complex64)
+    flags = np.zeros((3, 1, 4, 8), bool)
+    for fn in (flagging.incoherent_noise_spectrum, flagging.threshold_incoherent_noise_spectrum):
+        with pytest.raises(ValueError):
+            fn(vis, flags[:, :, :3])
+        with pytest.raises(ValueError):
+            fn(vis[0], flags[0])
+        with pytest.raises(ValueError):
+            fn(vis, flags, select=np.ones(4, bool))
+        for bad in (np.float64, np.complex128, np.int32):
+            with pytest.raises(TypeError):
+                fn(np.zeros(vis.shape, bad), flags)
+    for acc in ((np.zeros((1, 4, 8)), np.zeros((1, 4, 8), np.int32)), (np.zeros((1, 3, 8)),), 7):
+        with pytest.raises(ValueError):
+            flagging.incoherent_noise_spectrum(vis, flags, acc=acc)
+    with pytest.raises(TypeError):
+        flagging.incoherent_noise_spectrum(vis, flags, acc=(np.zeros((1, 3, 8), np.float32), np.zeros((1, 3, 8), np.int32)))
+    for kw in (dict(min_baseline_frac=1.5), dict(nsigma=0.0), dict(rounds=0), dict(rounds=17), dict(shapes=[(0, 9)]),
+               dict(shapes=[(3, 3)]), dict(shapes=[(0, 1)] * 32), dict(streak=None), dict(narrow=2)):
+        with pytest.raises(ValueError):
+            flagging.threshold_incoherent_noise_spectrum(vis, flags, **kw)
+    s, c = np.zeros((1, 3, 8)), np.zeros((1, 3, 8), np.int32)
+    for args in ((s[0], c[0], 1), (s, c[:, :2], 1), (s, c, 0), (s, c, 1.5), (s, c, 1, np.zeros((1, 3, 7), bool))):
+        with pytest.raises(ValueError):
+            flagging.incoherent_noise_zscore(*args)
+    for args in ((s.astype(np.float32), c, 1), (s, c.astype(np.int64), 1)):
+        with pytest.raises(TypeError):
+            flagging.incoherent_noise_zscore(*args)
+
+
+# ---------------------------------------------------------------------------
+# CPU: the kernel table against the sources
+# ---------------------------------------------------------------------------
+def scan_ins_kernels():
+    found = set()
+    paths = sorted(glob.glob(os.path.join(ROOT, "tricolour_amd", "csrc", "steps", "ins", "*")))
+    assert paths
+    for path in paths:
+        with open(path, encoding="utf-8") as fh:
+            found.update(re.findall(r"__global__[\s\S]{0,200}?\b(k_\w+)\s*\(", fh.read()))
+    return found
+
+
+def test_kernel_table_lists_what_the_sources_hold():
+    from test_route_ledger import scan_instances, scan_kernels
+    assert scan_ins_kernels() == set(KERNELS)
+    assert not set(KERNELS) & scan_kernels()                   # the ledger keeps the kernels directly under csrc/
+    sites = scan_instances()                                   # launch sites of tricolour_amd.hip, macros expanded
+    for kernel, instances in KERNELS.items():
+        assert sites.get(kernel) == instances, kernel
+    with open(os.path.join(ROOT, "tricolour_amd", "csrc", "tricolour_amd.hip"), encoding="utf-8") as fh:
+        assert '#include "steps/ins/kernels_ins.hpp"' in fh.read()
+    with open(os.path.join(ROOT, "tricolour_amd", "csrc", "steps", "ins", "kernels_ins.hpp"), encoding="utf-8") as fh:
+        text = fh.read()
+        assert re.search(r"#define INS_STRIP %d\b" % STRIP, text) and re.search(r"#define INS_FILL %d\b" % FILL, text)
+
+
+# ---------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------
+@contextlib.contextmanager
+def compared():
+    """Yields a dict that receives the kernel log of the block; the step's kernels launched inside count as met if
+    the block's comparisons passed."""
+    import torch
+    from tricolour_amd import _lib
+    log = {}
+    _lib.kernel_log_begin()
+    try:
+        yield log
+        torch.cuda.synchronize()
+    except BaseException:
+        _lib.kernel_log_end()
+        raise
+    log.update(_lib.kernel_log_end())
+    MET.update(k for k in log if k.startswith("k_ins_"))
+
+
+def dev(torch, a, offset=False):
+    """A device copy of `a`; offset: a contiguous view whose base lies one element past an aligned address."""
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    if not offset:
+        return t.cuda()
+    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device="cuda")
+    flat[1:] = t.reshape(-1).cuda()
+    return flat[1:].view(t.shape)
+
+
+def check_accumulate(torch, flagging, vis, flags, select, offset):
+    exp = restate_accumulate(vis, flags, select)
+    v, f = dev(torch, vis, offset), dev(torch, flags, offset)
+    if offset and vis.size:
+        assert v.data_ptr() % 16 != 0
+    s, c = flagging.incoherent_noise_spectrum(v, f, select=select)
+    assert s.is_cuda and s.dtype == torch.float64 and c.dtype == torch.int32
+    assert tuple(s.shape) == (vis.shape[1], vis.shape[2] - 1, vis.shape[3]) == tuple(c.shape)
+    assert same_bits(s.cpu().numpy(), exp[0]), "sum bits differ"
+    assert np.array_equal(c.cpu().numpy(), exp[1]), "counts differ"
+    return exp
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", accumulate_cases(), ids=case_id)
+def test_gpu_accumulate_equals_the_restatement(gpu, c):
+    import torch
+    from tricolour_amd import flagging
+    vis, flags, select = build(c)
+    with compared():
+        exp = check_accumulate(torch, flagging, vis, flags, select, offset=False)
+        check_accumulate(torch, flagging, vis, flags, select, offset=True)       # the scalar form: the same bits
+    if c.get("select") == "none" or c["density"] == 1.0:
+        assert not exp[1].any() and not exp[0].any()
+    if c.get("special") in ("inf", "inf_both"):
+        assert np.isposinf(exp[0]).any()
+    if c["shape"] == TALL and select is None:                  # the strip form continues from acc like the other
+        with compared():
+            first = flagging.incoherent_noise_spectrum(dev(torch, vis[:1]), dev(torch, flags[:1]))
+            both = flagging.incoherent_noise_spectrum(dev(torch, vis[1:]), dev(torch, flags[1:]), acc=first)
+            assert same_bits(both[0].cpu().numpy(), exp[0]) and np.array_equal(both[1].cpu().numpy(), exp[1])
+    if c.get("special") == "inf_both":
+        d = difference_amplitude(vis)
+        both = np.isinf(vis.real[:, :, 1:]) & np.isinf(vis.real[:, :, :-1])
+        assert both.any() and np.isnan(d[both]).all()          # inf - inf: the pair is removed
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["c64", "f32"])
+@pytest.mark.parametrize("shape", [(17, 1, 4, 100), (9, 2, 7, 16), (5, 1, 20, 65)], ids=lambda s: "x".join(map(str, s)))
+def test_gpu_continuing_from_acc_equals_one_call(gpu, shape, dtype):
+    import torch
+    from tricolour_amd import flagging
+    vis, flags = make_case(shape, 400 + shape[0], 0.1, dtype)
+    select = np.random.default_rng(7).uniform(size=shape[0]) < 0.7
+    for sel in (None, select):
+        with compared():
+            exp = restate_accumulate(vis, flags, sel)
+            v, f = dev(torch, vis), dev(torch, flags)
+            acc = None
+            for b0, b1 in ((0, 1), (1, 3), (3, shape[0])):
+                before = None if acc is None else (acc[0].clone(), acc[1].clone())
+                nxt = flagging.incoherent_noise_spectrum(v[b0:b1], f[b0:b1], select=None if sel is None else sel[b0:b1],
+                                                         acc=acc)
+                if before is not None:                         # acc is not modified; the result is a new pair
+                    assert torch.equal(acc[0], before[0]) and torch.equal(acc[1], before[1])
+                    assert nxt[0].data_ptr() != acc[0].data_ptr()
+                acc = nxt
+            assert same_bits(acc[0].cpu().numpy(), exp[0]) and np.array_equal(acc[1].cpu().numpy(), exp[1])
+            # numpy in, numpy out, continued from a numpy pair
+            half = flagging.incoherent_noise_spectrum(vis[:2], flags[:2], select=None if sel is None else sel[:2])
+            assert isinstance(half[0], np.ndarray) and half[0].dtype == np.float64 and half[1].dtype == np.int32
+            full = flagging.incoherent_noise_spectrum(vis[2:], flags[2:], select=None if sel is None else sel[2:], acc=half)
+            assert same_bits(full[0], exp[0]) and np.array_equal(full[1], exp[1])
+
+
+def zscore_cases():
+    """name -> (sum, count, min_count, mask)"""
+    out = {}
+    for i, (shape, dt) in enumerate([((5, 1, 9, 65), "c64"), ((9, 2, 7, 16), "f32"), ((17, 1, 4, 100), "c64"),
+                                     ((3, 2, 20, 12), "c64"), ((2, 1, 2, 37), "f32")]):
+        vis, flags = make_case(shape, 500 + i, 0.3, dt)
+        vis = (vis / np.abs(vis).max(axis=(1, 2, 3), keepdims=True)).astype(vis.dtype)       # one level: a live image
+        s, c = restate_accumulate(vis, flags)
+        mask = np.random.default_rng(510 + i).uniform(size=s.shape) < 0.25
+        out["x".join(map(str, shape)) + "-masked"] = (s, c, 2, mask)
+        out["x".join(map(str, shape))] = (s, c, 1 + i % 3, None)
+    # lines with m = 0 .. 6 finite values, by count, mask and infinity in turn; one line with a level of 0
+    s, c = synthetic_image((2, 6, 40), 520)
+    rng = np.random.default_rng(521)
+    mask = np.zeros(s.shape, bool)
+    for ch in range(40):
+        drop = rng.permutation(6)[:ch % 7]
+        for j, t in enumerate(drop):
+            if (ch + j) % 3 == 0:
+                c[0, t, ch] = 1
+            elif (ch + j) % 3 == 1:
+                mask[0, t, ch] = True
+            else:
+                s[0, t, ch] = np.inf
+    s[1, :, 5] = 0.0
+    s[1, 2, 7] = np.inf                                        # +inf on a live line: q = 2^30
+    s[1, :, 9] *= np.array([1, 1, 1e30, 1, 1e-30, 1])          # clamped at +-16384
+    out["lines-m0-to-6"] = (s, c, 10, mask)
+    out["wide-4096"] = synthetic_image((2, 3, 4096), 522) + (1, None)
+    return out
+
+
+ZSCORE = zscore_cases()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(ZSCORE))
+def test_gpu_zscore_equals_the_restatement(gpu, name):
+    import torch
+    from tricolour_amd import flagging
+    s, c, mc, mask = ZSCORE[name]
+    level, q, valid = restate_zscore(s, c, mc, mask)
+    with compared():
+        got = flagging.incoherent_noise_zscore(dev(torch, s), dev(torch, c), mc, None if mask is None else dev(torch, mask))
+        assert got[0].dtype == torch.float32 and got[1].dtype == torch.int32 and got[2].dtype == torch.bool
+        assert same_bits(got[0].cpu().numpy(), level), "level bits differ"
+        assert np.array_equal(got[2].cpu().numpy(), valid), "valid differs"
+        assert np.array_equal(got[1].cpu().numpy(), q), "q differs"
+    n = flagging.incoherent_noise_zscore(s, c, mc, mask)
+    assert isinstance(n[0], np.ndarray) and same_bits(n[0], level) and np.array_equal(n[1], q) and np.array_equal(n[2], valid)
+    if name == "lines-m0-to-6":
+        finite = (c[0] >= mc) & ~mask[0] & np.isfinite(s[0])
+        assert sorted(set(finite.sum(axis=0))) == [0, 1, 2, 3, 4, 5, 6]
+        assert not valid[0][:, finite.sum(axis=0) < 3].any() and valid[0][:, finite.sum(axis=0) >= 3].any()
+        assert np.isnan(level[0, finite.sum(axis=0) == 0]).all()
+        assert level[1, 5] == 0 and not valid[1, :, 5].any()
+        assert q[1, 2, 7] == 1 << 30 and q[1, 2, 9] == 16384 * 65536 and q[1, 4, 9] < 0 and q.min() >= -16384 * 65536
+
+
+def match_cases():
+    """name -> (sum, count, min_count, shapes, nsigma_narrow, rounds)"""
+    out = {}
+    s, c = synthetic_image((2, 12, 96), 600, noise=0.003)
+    x = s / c
+    x[0, 3, 10:40] *= 1.3
+    x[0, 3, 70] *= 2.0
+    x[0, 7, 50:60] *= 1.6
+    x[0, 7, 20:26] *= 1.8
+    x[1, 5, :] *= 1.2
+    x[1, 9, 95] *= 2.5
+    x[1, 2, 0] *= 2.5
+    s = x * c
+    shapes = [(10, 40, 5.0), (50, 60, 5.0), (20, 26, 4.0), (0, 96, 5.0), (30, 55, 6.0), (70, 71, 5.0)]
+    for rounds in (1, 3, 16):
+        out["six-shapes-r%d" % rounds] = (s, c, 1, shapes, 5.0, rounds)
+    out["no-shapes-narrow"] = (s, c, 1, [], 5.0, 3)
+    out["no-shapes-no-narrow"] = (s, c, 1, [], 0.0, 3)
+    out["whole-band-only"] = (s, c, 1, [(0, 96, 5.0)], 0.0, 2)
+    out["32-shapes"] = (s, c, 1, [(3 * i, 3 * i + 1 + i % 5, 3.0 + 0.1 * i) for i in range(31)] + [(0, 96, 5.0)], 4.0, 3)
+    # equal r: columns 8..15 repeat columns 0..7, so the shapes (0, 8) and (8, 16) tie on every row; the first wins
+    s2, c2 = synthetic_image((1, 10, 16), 601, noise=0.003)
+    x2 = s2 / c2
+    x2[0, 4, 0:8] *= 1.8
+    x2[0, 6, 3] *= 3.0
+    s2 = x2 * c2
+    s2[:, :, 8:], c2[:, :, 8:] = s2[:, :, :8], c2[:, :, :8]
+    out["tie-first-shape"] = (s2, c2, 1, [(0, 8, 5.0), (8, 16, 5.0)], 0.0, 1)
+    out["tie-first-shape-reversed"] = (s2, c2, 1, [(8, 16, 5.0), (0, 8, 5.0)], 0.0, 1)
+    out["tie-lowest-channel"] = (s2, c2, 1, [], 5.0, 1)
+    out["tie-two-rounds"] = (s2, c2, 1, [(0, 8, 5.0), (8, 16, 5.0)], 5.0, 2)
+    vis, flags = burst_input(9, True)
+    sb, cb = restate_accumulate(vis[:, :, 4:15], flags[:, :, 4:15])
+    out["burst-min-count"] = (sb, cb, 12, [(lo, hi, 5.0) for lo, hi in BURST_SHAPES], 5.0, 3)
+    return out
+
+
+MATCH = match_cases()
+
+
+def run_match(torch, s, c, mc, shapes, narrow, rounds):
+    """tri_ins_match through the ABI on device copies; the mask as a numpy bool array."""
+    from tricolour_amd import _lib
+    lib = _lib.lib()
+    ncorr, nd, nchan = s.shape
+    ds, dc = dev(torch, s), dev(torch, c)
+    mask = torch.full(s.shape, 7, dtype=torch.uint8, device="cuda")            # the call zeroes it
+    ws = torch.empty(lib.tri_ins_workspace_bytes(ncorr, nd + 1, nchan), dtype=torch.uint8, device="cuda")
+    n = len(shapes)
+    lo, hi = (C.c_int64 * max(n, 1))(*[x[0] for x in shapes]), (C.c_int64 * max(n, 1))(*[x[1] for x in shapes])
+    ns = (C.c_double * max(n, 1))(*[x[2] for x in shapes])
+    _lib.check(lib.tri_ins_match(ds.data_ptr(), dc.data_ptr(), ncorr, nd + 1, nchan, mc, lo, hi, ns, n, narrow, rounds,
+                                 mask.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+    assert same_bits(ds.cpu().numpy(), s) and np.array_equal(dc.cpu().numpy(), c)        # inputs are never written
+    got = mask.cpu().numpy()
+    assert got.max(initial=0) <= 1
+    return got != 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(MATCH))
+def test_gpu_match_equals_the_restatement(gpu, name):
+    import torch
+    s, c, mc, shapes, narrow, rounds = MATCH[name]
+    exp = restate_match(s, c, mc, shapes, narrow, rounds)
+    with compared():
+        got = run_match(torch, s, c, mc, shapes, narrow, rounds)
+        assert np.array_equal(got, exp), (np.argwhere(got != exp)[:8], name)
+    if name == "six-shapes-r1":
+        assert exp[0, 3, 10:40].all() and not exp[0, 3, 70] and exp[1, 5].all() and exp[1, 9, 95] and exp[1, 2, 0]
+        assert exp[0, 7].sum() in (6, 10)
+    if name == "six-shapes-r3":
+        assert exp[0, 3, 70] and exp[0, 7, 50:60].all() and exp[0, 7, 20:26].all()
+        assert np.array_equal(exp, restate_match(s, c, mc, shapes, narrow, 16))
+    if name == "no-shapes-no-narrow":
+        assert not exp.any()
+    if name == "tie-first-shape":
+        assert exp[0, 4, :8].all() and not exp[0, 4, 8:].any()
+        other = restate_match(*MATCH["tie-first-shape-reversed"])
+        assert other[0, 4, 8:].all() and not other[0, 4, :8].any()
+    if name == "tie-lowest-channel":
+        assert exp[0, 6, 3] and not exp[0, 6, 11] and exp[0, 6].sum() == 1
+    if name == "tie-two-rounds":
+        assert exp[0, 4].all()
+    if name == "burst-min-count":
+        only = np.zeros(exp.shape, bool)
+        only[0, 5:7, 40:72] = True
+        assert np.array_equal(exp, only)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("offset", [False, True], ids=["aligned", "offset"])
+@pytest.mark.parametrize("shape", [(1, 1, 1, 16), (3, 2, 1, 5), (1, 1, 2, 16), (7, 1, 2, 11), (7, 2, 5, 32), (2, 1, 3, 4112),
+                                   (3, 2, 20, 12)], ids=lambda s: "x".join(map(str, s)))
+def test_gpu_apply_pass(gpu, shape, offset):
+    """nchan % 16 == 0 and not, an offset base, ntime of 1 (no difference row), 2 and more; out of place and in place."""
+    import torch
+    from tricolour_amd import _lib
+    nbl, ncorr, ntime, nchan = shape
+    rng = np.random.default_rng(700 + ntime + nchan)
+    f8 = ((rng.uniform(size=shape) < 0.3) * rng.integers(1, 256, size=shape)).astype(np.uint8)      # any nonzero byte is a flag
+    mask = ((rng.uniform(size=(ncorr, ntime - 1, nchan)) < 0.2) * rng.integers(1, 256, size=(ncorr, ntime - 1, nchan)))
+    mask = mask.astype(np.uint8)
+    exp = restate_apply(f8, mask).astype(np.uint8)
+    stream = torch.cuda.current_stream().cuda_stream
+    with compared() as log:
+        src = dev(torch, f8, offset)
+        msk = dev(torch, mask if mask.size else np.zeros(16, np.uint8), offset)
+        out = dev(torch, np.full(shape, 7, np.uint8), offset)
+        args = (nbl, ncorr, ntime, nchan, stream)
+        _lib.check(_lib.lib().tri_ins_apply(src.data_ptr(), msk.data_ptr(), out.data_ptr(), *args))
+        assert np.array_equal(out.cpu().numpy(), exp)
+        assert np.array_equal(src.cpu().numpy(), f8)
+        _lib.check(_lib.lib().tri_ins_apply(src.data_ptr(), msk.data_ptr(), src.data_ptr(), *args))      # in place
+        assert np.array_equal(src.cpu().numpy(), exp)
+    assert set(log) == {"k_ins_apply<true>" if nchan % 16 == 0 and not offset else "k_ins_apply<false>"}, log
+    if ntime == 1:
+        assert np.array_equal(exp, (f8 != 0).astype(np.uint8))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(1, 1, 1, 1), (1, 1, 2, 1), (3, 2, 1, 16), (2, 1, 2, 37), (0, 1, 4, 8), (3, 1, 4, 0)],
+                         ids=lambda s: "x".join(map(str, s)))
+def test_gpu_step_on_the_smallest_shapes(gpu, shape):
+    import torch
+    from tricolour_amd import flagging
+    vis, flags = make_case(shape, 750, 0.3)
+    exp = restate_step(vis, flags, nsigma=2.0)
+    with compared() as log:
+        got = flagging.threshold_incoherent_noise_spectrum(dev(torch, vis), dev(torch, flags), nsigma=2.0)
+        assert got.dtype == torch.bool and tuple(got.shape) == shape and np.array_equal(got.cpu().numpy(), exp)
+    if shape[2] < 2 and min(shape) > 0:
+        assert {k for k in log if k.startswith("k_")} == {"k_ins_apply<true>" if shape[3] % 16 == 0 else "k_ins_apply<false>"}
+    if min(shape) == 0:
+        assert not log
+
+
+@pytest.mark.gpu
+def test_gpu_step_on_the_burst_containers_and_reproducibility(gpu):
+    import torch
+    from tricolour_amd import flagging
+    vis, flags, exp, mask = burst_expected(0, True)
+    kw = dict(BURST_KW)
+    v, f = dev(torch, vis), dev(torch, flags)
+    v0, f0 = v.clone(), f.clone()
+    with compared() as log:
+        got = flagging.threshold_incoherent_noise_spectrum(v, f, **kw)
+        assert torch.is_tensor(got) and got.is_cuda and got.dtype == torch.bool
+        assert np.array_equal(got.cpu().numpy(), exp)
+    assert log["k_ins_match"] == 3 and log["k_ins_level"] == 3 and log["k_ins_mean"] == 1
+    assert torch.equal(v, v0) and torch.equal(f, f0)           # inputs unchanged
+    flagged = np.zeros(vis.shape, bool)
+    flagged[:, 0, 9:12, 40:72] = True
+    assert np.array_equal(exp, flagged)
+    again = flagging.threshold_incoherent_noise_spectrum(v, f, **kw)
+    assert torch.equal(got, again)                             # two runs: identical bits
+    s1, s2 = flagging.incoherent_noise_spectrum(v, f), flagging.incoherent_noise_spectrum(v, f)
+    assert torch.equal(s1[0].view(torch.int64), s2[0].view(torch.int64)) and torch.equal(s1[1], s2[1])
+    # numpy in, numpy out (bool); uint8 tensor in, uint8 tensor out
+    vn, fn = vis.copy(), flags.copy()
+    out = flagging.threshold_incoherent_noise_spectrum(vn, fn, **kw)
+    assert isinstance(out, np.ndarray) and out.dtype == np.bool_ and np.array_equal(out, exp)
+    assert same_bits(vn, vis) and np.array_equal(fn, flags)
+    pre = flags.copy()
+    pre[3, 0, 20, 5] = True
+    f3 = dev(torch, pre.astype(np.uint8) * 3)
+    out = flagging.threshold_incoherent_noise_spectrum(v, f3, **kw)
+    assert out.is_cuda and out.dtype == torch.uint8
+    assert np.array_equal(out.cpu().numpy(), restate_step(vis, pre, **kw).astype(np.uint8))
+    # noise alone: nothing; float32 amplitudes and a selection against the restatement
+    vis0, flags0, exp0, _ = burst_expected(0, False)
+    with compared():
+        assert not flagging.threshold_incoherent_noise_spectrum(dev(torch, vis0), dev(torch, flags0), **kw).any().item()
+    amp = np.abs(vis).astype(np.float32)
+    select = np.arange(45) % 3 != 0
+    kw2 = dict(nsigma=4.0, shapes=[(40, 72, 4.5)], rounds=2, min_baseline_frac=0.5)
+    with compared():
+        got = flagging.threshold_incoherent_noise_spectrum(dev(torch, amp), dev(torch, flags), select=select, **kw2)
+        assert np.array_equal(got.cpu().numpy(), restate_step(amp, flags, select, **kw2))
+
+
+def chain_input():
+    a1, a2 = np.triu_indices(5, 0)
+    ubl = np.stack([np.arange(a1.size), a1, a2], axis=1)
+    shape = (a1.size, 2, 24, 64)
+    rng = np.random.default_rng(21)
+    vis = (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
+    autos = ubl[:, 1] == ubl[:, 2]
+    vis[autos] *= 30                                           # autos: strong; excluded or not, it shows
+    vis[:, :, 11, 20:36] += np.exp(2j * np.pi * rng.uniform(size=(shape[0], 1, 1))).astype(np.complex64) * np.float32(4)
+    flags = rng.uniform(size=shape) < 0.02
+    freq = np.linspace(1e9, 1.063e9, 64)
+    return vis, flags, ubl, autos, freq
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("exclude_autos", [True, False])
+def test_gpu_apply_strategies_with_the_step_in_a_chain(gpu, exclude_autos):
+    import torch
+    from tricolour_amd.strategies import apply_strategies
+    vis, flags, ubl, autos, freq = chain_input()
+    kw = dict(nsigma=4.0, rounds=2, min_baseline_frac=0.3, shapes=[[4, 9, 6.0]],
+              bands_hz=[[1.0195e9, 1.0355e9], [2e9, 3e9], [1.05e9, 1.06e9]])
+    if not exclude_autos:
+        kw["exclude_autos"] = False
+    strategies = [{"task": "flag_autos"}, {"task": TASK, "kwargs": kw}]
+    f = flags | autos[:, None, None, None]
+    shapes = [(4, 9, 6.0), (20, 36), (50, 61)]                 # the second band holds no channel and is dropped
+    exp = f | restate_step(vis, f, ~autos if exclude_autos else None, 0.3, 4.0, shapes, True, True, 2)
+    with compared():
+        got = apply_strategies(strategies, dev(torch, flags), dev(torch, vis), ubl=ubl, chan_freq=freq,
+                               chan_width=np.full(64, 1e6))
+        assert np.array_equal(got.cpu().numpy(), exp)
+    assert exp[autos].all() and not exp.all()
+    if exclude_autos:
+        assert exp[~autos][:, :, 10:13, 20:36].all() and not (exp & ~flags)[~autos][:, :, :9].any()
+
+
+@pytest.mark.gpu
+def test_gpu_flag_scan_whole_scan_with_the_step(gpu):
+    import torch
+    from tricolour_amd import packing, scan
+    rs = np.random.RandomState(31)
+    data, flag, ant1, ant2, tm, freq, width = small_scan(rs)
+    kw = dict(nsigma=4.5, rounds=2, bands_hz=[[freq[20], freq[35]]])
+    strategies = [{"task": "flag_autos"}, {"task": TASK, "kwargs": kw}]
+    with compared():
+        got, _, _ = scan.flag_scan(data, flag, ant1, ant2, tm, freq, width, strategies)
+        ubl = packing.unique_baselines(ant1, ant2)
+        utime, tinv = np.unique(tm, return_inverse=True)
+        tinv = tinv.astype(np.int32)
+        vw, fw = packing.pack_scan(tinv, ubl, ant1, ant2, dev(torch, data), dev(torch, flag), len(utime))
+        vw, fw = vw.cpu().numpy(), fw.cpu().numpy() != 0
+        autos = ubl[:, 1] == ubl[:, 2]
+        f = fw | autos[:, None, None, None]
+        f = f | restate_step(vw, f, ~autos, 0.25, 4.5, [(20, 36)], True, True, 2)
+        exp = packing.unpack_scan(ant1, ant2, tinv, ubl, dev(torch, f), data.shape[2]).cpu().numpy()
+        assert isinstance(got, np.ndarray) and got.dtype == np.bool_ and np.array_equal(got, exp)
+    nbl = 15
+    assert exp[7 * nbl:8 * nbl, 20:36].all() and not exp.all()
+    with pytest.raises(ValueError, match=TASK):
+        scan.flag_scan(data, flag, ant1, ant2, tm, freq, width, strategies, baseline_chunks=4)
+
+
+@pytest.mark.gpu
+def test_gpu_every_listed_kernel_instantiation_was_launched_and_compared(gpu):
+    """One compared call per route (the tests above add theirs when they ran): each launches exactly the instantiation
+    its shape, dtype and alignment select, and together they are the table."""
+    import torch
+    from tricolour_amd import flagging
+    tall = (1,) + TALL[1:]
+    routes = [("c64", (5, 1, 3, 16), False, "k_ins_accumulate<0, 4, 1, 4>"), ("c64", (5, 1, 3, 16), True, "k_ins_accumulate<0, 1, 1, 4>"),
+              ("c64", (6, 1, 3, 5), False, "k_ins_accumulate<0, 1, 1, 4>"), ("f32", (7, 2, 2, 8), False, "k_ins_accumulate<1, 4, 1, 4>"),
+              ("f32", (7, 2, 2, 8), True, "k_ins_accumulate<1, 1, 1, 4>"), ("f32", (3, 1, 11, 7), False, "k_ins_accumulate<1, 1, 1, 4>"),
+              ("c64", tall, False, "k_ins_accumulate<0, 4, 8, 1>"), ("c64", tall, True, "k_ins_accumulate<0, 1, 8, 1>"),
+              ("f32", tall, False, "k_ins_accumulate<1, 4, 8, 1>"), ("f32", tall, True, "k_ins_accumulate<1, 1, 8, 1>"),
+              ("c64", (1, 1, 26, 131068), False, "k_ins_accumulate<0, 4, 1, 4>")]         # one piece short of the strip form
+    for dtype, shape, offset, kernel in routes:
+        vis, flags = make_case(shape, 800 + shape[0], 0.2, dtype)
+        with compared() as log:
+            check_accumulate(torch, flagging, vis, flags, None, offset)
+        assert {k for k in log if k.startswith("k_")} == {kernel}, (dtype, shape, offset, log)
+    s, c = synthetic_image((1, 5, 8), 810)
+    level, q, valid = restate_zscore(s, c, 1)
+    with compared() as log:
+        got = flagging.incoherent_noise_zscore(dev(torch, s), dev(torch, c), 1)
+        assert same_bits(got[0].cpu().numpy(), level) and np.array_equal(got[1].cpu().numpy(), q)
+        assert np.array_equal(got[2].cpu().numpy(), valid)
+    assert {k for k in log if k.startswith("k_ins_")} == {"k_ins_mean", "k_ins_level", "k_ins_zq"}, log
+    for shape, offset, kernel in (((3, 1, 4, 16), False, "k_ins_apply<true>"), ((3, 1, 4, 16), True, "k_ins_apply<false>"),
+                                  ((3, 1, 4, 9), False, "k_ins_apply<false>")):
+        vis, flags = make_case(shape, 820, 0.2)
+        vis = (vis / np.abs(vis).max(axis=(1, 2, 3), keepdims=True)).astype(np.complex64)
+        exp = restate_step(vis, flags, nsigma=1.5, rounds=2)
+        with compared() as log:
+            got = flagging.threshold_incoherent_noise_spectrum(dev(torch, vis, offset), dev(torch, flags, offset),
+                                                               nsigma=1.5, rounds=2)
+            assert np.array_equal(got.cpu().numpy(), exp)
+        mine = {k for k in log if k.startswith("k_ins_")}
+        assert kernel in mine and {"k_ins_mean", "k_ins_level", "k_ins_zq", "k_ins_match"} <= mine and len(mine) == 6, log
+        assert log["k_ins_match"] == 2
+    listed = set().union(*KERNELS.values())
+    assert MET == listed, (sorted(listed - MET), sorted(MET - listed))

@@ -18,7 +18,8 @@ DEPENDS = [os.path.join(_HERE, "csrc", f) for f in (
     "tri_common.hpp", "kernels_elementwise.hpp", "kernels_median.hpp", "kernels_reject.hpp", "kernels_reject_tile.hpp", "kernels_boxfilter.hpp", "kernels_boxline.hpp", "kernels_boxpipe.hpp",
     "kernels_boxweight.hpp", "kernels_boxexact.hpp",
     "kernels_sumthreshold.hpp", "kernels_scan.hpp", "kernels_sir.hpp", "kernels_linerms.hpp",
-    os.path.join("steps", "kernels_blint.hpp"), os.path.join("steps", "ldev", "kernels_ldev.hpp"))]
+    os.path.join("steps", "kernels_blint.hpp"), os.path.join("steps", "ldev", "kernels_ldev.hpp"),
+    os.path.join("steps", "ins", "kernels_ins.hpp"))]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tricolour_amd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
@@ -186,6 +187,15 @@ _SIGNATURES = {
     "tri_local_deviation_threshold": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                 C.c_int64, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_int64), C.c_int64,
                                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tri_ins_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tri_ins_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "tri_ins_zscore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tri_ins_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int64, C.c_double, C.c_int64, C.c_void_p,
+                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tri_ins_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "tri_last_error": (C.c_char_p, []),
     "tri_version": (C.c_int, []),
     "tri_bench_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

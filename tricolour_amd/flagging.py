@@ -1124,3 +1124,277 @@ def baseline_integrated_flagger(vis, flags, select=None, min_baseline_frac=0.25,
             _lib.check(lib.tri_broadcast_or(f8.data_ptr(), new8.data_ptr(), out.data_ptr(), nbl, new8.numel(),
                                             torch.cuda.current_stream(device).cuda_stream))
     return _like_flags(torch, out, flags, from_numpy)
+
+
+INS_MAX_SHAPES = 32
+
+
+def _ins_number(name, v, lo, what):
+    try:
+        ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and float(v) > lo   # also rejects NaN
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or float(v) == float("inf"):
+        raise ValueError("%s must be %s, got %r" % (name, what, v))
+    return float(v)
+
+
+def _ins_index(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError("%s must be an integer, got %r" % (name, v))
+    return int(v)
+
+
+def check_incoherent_noise_kwargs(min_baseline_frac=0.25, nsigma=5.0, shapes=(), streak=True, narrow=True, rounds=3):
+    """The argument checks of :func:`threshold_incoherent_noise_spectrum` that
+    need no data (no device work): ``min_baseline_frac`` outside [0, 1], an
+    ``nsigma`` that is not a finite number > 0, ``shapes`` entries that are not
+    ``(lo, hi)`` or ``(lo, hi, nsigma)`` with integers ``0 <= lo < hi``, more
+    than 32 shapes (the streak included), ``streak`` / ``narrow`` that are not
+    booleans and ``rounds`` outside [1, 16] raise ``ValueError``.  Returns
+    ``(frac, nsigma, [(lo, hi, nsigma), ...], streak, narrow, rounds)``."""
+    try:
+        frac = _bli_fraction(min_baseline_frac)
+    except (TypeError, ValueError):
+        raise ValueError("min_baseline_frac must lie in [0, 1], got %r" % (min_baseline_frac,))
+    nsigma = _ins_number("nsigma", nsigma, 0.0, "a finite number > 0")
+    for name, v in (("streak", streak), ("narrow", narrow)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("%s must be True or False, got %r" % (name, v))
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= int(rounds) <= 16:
+        raise ValueError("rounds must be an integer in [1, 16], got %r" % (rounds,))
+    try:
+        entries = [tuple(s) for s in shapes]
+    except TypeError:
+        raise ValueError("shapes must be a sequence of (lo_chan, hi_chan) or (lo_chan, hi_chan, nsigma), got %r" % (shapes,))
+    out = []
+    for s in entries:
+        if len(s) not in (2, 3):
+            raise ValueError("a shape must be (lo_chan, hi_chan) or (lo_chan, hi_chan, nsigma), got %r" % (s,))
+        lo, hi = _ins_index("shape lo_chan", s[0]), _ins_index("shape hi_chan", s[1])
+        if not 0 <= lo < hi:
+            raise ValueError("a shape needs 0 <= lo_chan < hi_chan, got %r" % (s,))
+        out.append((lo, hi, _ins_number("shape nsigma", s[2], 0.0, "a finite number > 0") if len(s) == 3 else nsigma))
+    if len(out) + (1 if streak else 0) > INS_MAX_SHAPES:
+        raise ValueError("at most %d shapes (the streak included), got %d" % (INS_MAX_SHAPES, len(out) + (1 if streak else 0)))
+    return frac, nsigma, out, bool(streak), bool(narrow), int(rounds)
+
+
+def _ins_image_shape(shape):
+    return (int(shape[1]), max(int(shape[2]) - 1, 0), int(shape[3]))
+
+
+def _ins_accumulate(torch, lib, device, v, f8, code, sel, acc):
+    """(sum float64, count int32) of shape (corr, time - 1, chan) on the device: new tensors, continued from `acc`."""
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    img = _ins_image_shape(v.shape)
+    if acc is None:
+        total = torch.zeros(img, dtype=torch.float64, device=device)
+        count = torch.zeros(img, dtype=torch.int32, device=device)
+    else:
+        total, count = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a for a in acc)
+        total, count = total.to(device).clone().contiguous(), count.to(device).clone().contiguous()
+    if total.numel() > 0 and nbl > 0:
+        _lib.check(lib.tri_ins_accumulate(
+            v.data_ptr(), code, f8.data_ptr(), sel.data_ptr() if sel is not None else None, nbl, ncorr, ntime, nchan,
+            total.data_ptr(), count.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    return total, count
+
+
+def _ins_check_acc(acc, img):
+    if acc is None:
+        return
+    try:
+        total, count = acc
+    except (TypeError, ValueError):
+        raise ValueError("acc must be a (sum, count) pair of shape %s" % (img,))
+    if tuple(total.shape) != img or tuple(count.shape) != img:
+        raise ValueError("acc must be a (sum, count) pair of shape %s" % (img,))
+    if str(total.dtype).replace("torch.", "") != "float64" or str(count.dtype).replace("torch.", "") != "int32":
+        raise TypeError("acc must be a (float64 sum, int32 count) pair")
+
+
+def incoherent_noise_spectrum(vis, flags, select=None, acc=None):
+    """Sum and count over baselines of the amplitudes of the time differences
+    of (bl, corr, time, chan) visibilities (float32 input: amplitudes, ``im =
+    0``): for every pair of rows ``(t, t + 1)`` and the baselines in ascending
+    order, ``sum += float64(|v[t + 1] - v[t]|)`` (the difference in float32,
+    its amplitude as the flagger takes it) and ``count += 1`` over the pairs
+    whose baseline is selected (``select``, one entry per baseline, nonzero =
+    takes part; None: all), whose two flags are 0 and whose amplitude is not
+    NaN.  Sky and fringe vary slowly and cancel in the difference; noise and
+    whatever changed between two dumps remain.  Returns ``(sum float64, count
+    int32)`` of shape (corr, time - 1, chan) -- numpy arrays for numpy input,
+    tensors on the device otherwise.  ``acc``: an earlier result to continue
+    from (not modified; the result is a new pair): the baselines fed in
+    several calls in ascending order give the bits of one call.  One thread
+    owns a position and sums in memory order, so the result is reproducible
+    bit for bit.  Definition: ``include/tricolour_amd.h``.  Inputs are not
+    modified."""
+    if len(tuple(vis.shape)) == 4:
+        _ins_check_acc(acc, _ins_image_shape(vis.shape))
+    torch, v, f8, code, from_numpy, device, sel = _bli_inputs("incoherent_noise_spectrum", vis, flags, select)
+    with torch.cuda.device(device):
+        total, count = _ins_accumulate(torch, _lib.lib(), device, v, f8, code, sel, acc)
+    if from_numpy:
+        return total.cpu().numpy(), count.cpu().numpy()
+    return total, count
+
+
+def _ins_workspace(torch, lib, device, ncorr, ntime, nchan):
+    nbytes = lib.tri_ins_workspace_bytes(ncorr, ntime, nchan)
+    if nbytes == 0:
+        raise NotImplementedError("incoherent noise spectrum: an image of (%d, %d, %d) is too large" % (ncorr, ntime - 1, nchan))
+    return _workspace(torch, device, nbytes)
+
+
+def incoherent_noise_zscore(sum, count, min_count, mask=None):
+    """One round's z-score image of an :func:`incoherent_noise_spectrum`
+    result ``(sum, count)`` of shape (corr, time - 1, chan): the level of each
+    (corr, chan) line -- the median over time of the mean amplitudes
+    ``float32(sum / count)`` of the usable (``count >= min_count``), unmasked
+    positions --, the fixed-point z-score ``q`` (int32, units of 2**-16) and
+    which positions are valid.  ``mask``: earlier detections of the same shape
+    (None: none).  Returns ``(level float32 (corr, chan), q int32, valid
+    bool)`` -- numpy arrays for numpy input, tensors on the device otherwise.
+    Definition: ``include/tricolour_amd.h``.  Inputs are not modified."""
+    img = tuple(sum.shape)
+    if len(img) != 3:
+        raise ValueError("sum must be 3-D (corr, time - 1, chan), got shape %s" % (img,))
+    if tuple(count.shape) != img or (mask is not None and tuple(mask.shape) != img):
+        raise ValueError("sum, count and mask must have the same shape, got %s, %s and %s"
+                         % (img, tuple(count.shape), None if mask is None else tuple(mask.shape)))
+    if str(sum.dtype).replace("torch.", "") != "float64" or str(count.dtype).replace("torch.", "") != "int32":
+        raise TypeError("sum must be float64 and count int32, got %s and %s" % (sum.dtype, count.dtype))
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or int(min_count) < 1:
+        raise ValueError("min_count must be an integer >= 1, got %r" % (min_count,))
+    torch = _require_gpu()
+    from_numpy = not torch.is_tensor(sum)
+    if from_numpy:
+        device = torch.device("cuda", torch.cuda.current_device())
+        s = torch.from_numpy(np.ascontiguousarray(sum)).to(device)
+    else:
+        if not sum.is_cuda:
+            raise ValueError("tensors must live on the device")
+        device = sum.device
+        s = sum.contiguous()
+    c = (torch.from_numpy(np.ascontiguousarray(count)) if not torch.is_tensor(count) else count).to(device).contiguous()
+    if mask is None:
+        m8 = torch.zeros(img, dtype=torch.uint8, device=device)
+    else:
+        m8 = _flags_u8(torch, torch.from_numpy(np.ascontiguousarray(mask)) if not torch.is_tensor(mask) else mask, device)
+    ncorr, nd, nchan = (int(x) for x in img)
+    level = torch.empty((ncorr, nchan), dtype=torch.float32, device=device)
+    q = torch.empty(img, dtype=torch.int32, device=device)
+    valid = torch.empty(img, dtype=torch.uint8, device=device)
+    if s.numel() > 0:
+        lib = _lib.lib()
+        with torch.cuda.device(device):
+            ws = _ins_workspace(torch, lib, device, ncorr, nd + 1, nchan)
+            _lib.check(lib.tri_ins_zscore(s.data_ptr(), c.data_ptr(), m8.data_ptr(), ncorr, nd + 1, nchan, int(min_count),
+                                          level.data_ptr(), q.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          torch.cuda.current_stream(device).cuda_stream))
+    else:
+        level.fill_(float("nan"))
+    valid = valid.view(torch.bool)
+    if from_numpy:
+        return level.cpu().numpy(), q.cpu().numpy(), valid.cpu().numpy()
+    return level, q, valid
+
+
+def _ins_match(torch, lib, device, total, count, min_count, shapes, nsigma_narrow, rounds):
+    """The mask (corr, time - 1, chan) uint8 after `rounds` rounds; shapes: [(lo, hi, nsigma)]."""
+    ncorr, nd, nchan = (int(x) for x in total.shape)
+    mask = torch.empty(total.shape, dtype=torch.uint8, device=device)
+    if total.numel() > 0:
+        n = len(shapes)
+        lo = (C.c_int64 * max(n, 1))(*[s[0] for s in shapes])
+        hi = (C.c_int64 * max(n, 1))(*[s[1] for s in shapes])
+        ns = (C.c_double * max(n, 1))(*[s[2] for s in shapes])
+        ws = _ins_workspace(torch, lib, device, ncorr, nd + 1, nchan)
+        _lib.check(lib.tri_ins_match(total.data_ptr(), count.data_ptr(), ncorr, nd + 1, nchan, min_count, lo, hi, ns, n,
+                                     nsigma_narrow, rounds, mask.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     torch.cuda.current_stream(device).cuda_stream))
+    return mask
+
+
+def _ins_shapes(shapes, streak, nchan):
+    """The step's shape list for `nchan` channels (raises ValueError for a shape beyond the band)."""
+    for lo, hi, _ in shapes:
+        if hi > nchan:
+            raise ValueError("shape (%d, %d) does not lie within the %d channels" % (lo, hi, nchan))
+    return list(shapes)
+
+
+def threshold_incoherent_noise_spectrum(vis, flags, select=None, min_baseline_frac=0.25, nsigma=5.0, shapes=(),
+                                        streak=True, narrow=True, rounds=3):
+    """Flags (bl, corr, time, chan) windows on the sky-subtracted incoherent
+    noise spectrum (after SSINS, Wilensky et al. 2019; the definition is this
+    library's own, ``include/tricolour_amd.h``, and identity with SSINS is not
+    claimed): :func:`incoherent_noise_spectrum` of the selected baselines
+    gives the mean amplitude of the time differences per (corr, time pair,
+    chan), whose noise falls as 1 / sqrt(baselines) and whose sigma is tied to
+    its mean, so the z-score against the channel's median over time needs no
+    background fit.  Per time pair, the matched sums of the z-scores over the
+    channel ranges ``shapes`` -- entries ``(lo_chan, hi_chan)`` or ``(lo_chan,
+    hi_chan, nsigma)``; ``streak`` appends the whole band ``(0, nchan)`` -- and,
+    with ``narrow``, the largest single z-score are compared with ``nsigma``;
+    the strongest candidate above it is flagged, and ``rounds`` rounds repeat
+    this on what the earlier rounds left (a band and then a spike, or two
+    bands, in one row).  A detection in the pair ``(t, t + 1)`` flags both
+    times of its channels on EVERY baseline, the unselected ones included:
+    ``out = (flags != 0) | mask[t - 1] | mask[t]``.  A position counts with at
+    least ``max(1, ceil(min_baseline_frac * selected baselines))`` baselines.
+    Finds faint RFI that is present on all baselines without fitting a
+    background.  Returns a new array in the container / dtype of ``flags``; the
+    inputs are not modified."""
+    frac, nsigma, shapes, streak, narrow, rounds = check_incoherent_noise_kwargs(
+        min_baseline_frac, nsigma, shapes, streak, narrow, rounds)
+    if len(tuple(vis.shape)) == 4:
+        nchan = int(vis.shape[3])
+        shapes = _ins_shapes(shapes, streak, nchan)
+        if streak and nchan > 0:
+            shapes.append((0, nchan, nsigma))
+    torch, v, f8, code, from_numpy, device, sel = _bli_inputs("threshold_incoherent_noise_spectrum", vis, flags, select)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    lib = _lib.lib()
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            nsel = _bli_selected(nbl, sel)
+            total, count = _ins_accumulate(torch, lib, device, v, f8, code, sel, None)
+            mask = _ins_match(torch, lib, device, total, count, _bli_min_count(frac, nsel), shapes,
+                              nsigma if narrow else 0.0, rounds)
+            del total, count
+            if mask.numel() == 0:
+                mask = torch.zeros(16, dtype=torch.uint8, device=device)     # ntime < 2: never read
+            _lib.check(lib.tri_ins_apply(f8.data_ptr(), mask.data_ptr(), out.data_ptr(), nbl, ncorr, ntime, nchan,
+                                         torch.cuda.current_stream(device).cuda_stream))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
+def incoherent_noise_bands(bands_hz, chan_freq):
+    """Channel ranges ``[(lo_chan, hi_chan), ...]`` of the frequency bands
+    ``[[f_lo, f_hi], ...]``: a channel belongs to a band if its centre
+    ``chan_freq[c]`` lies in ``[f_lo, f_hi]``; the range runs from the first to
+    the last such channel, and a band without channels is dropped."""
+    freq = np.asarray(chan_freq, np.float64).reshape(-1)
+    out = []
+    for f_lo, f_hi in bands_hz:
+        inside = np.flatnonzero((freq >= float(f_lo)) & (freq <= float(f_hi)))
+        if inside.size:
+            out.append((int(inside[0]), int(inside[-1]) + 1))
+    return out
+
+
+def check_incoherent_noise_bands(bands_hz):
+    """``bands_hz`` must be a sequence of ``[f_lo, f_hi]`` pairs of finite numbers with ``f_lo <= f_hi``."""
+    try:
+        pairs = [tuple(b) for b in bands_hz]
+        ok = all(len(p) == 2 and not isinstance(p[0], bool) and not isinstance(p[1], bool)
+                 and np.isfinite(float(p[0])) and np.isfinite(float(p[1])) and float(p[0]) <= float(p[1]) for p in pairs)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("bands_hz must be a list of [f_lo, f_hi] pairs of finite numbers with f_lo <= f_hi, got %r" % (bands_hz,))
+    return [(float(a), float(b)) for a, b in pairs]

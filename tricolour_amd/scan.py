@@ -30,10 +30,11 @@ VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with
                "threshold_line_rms",                            # beyond the reference: flagging.threshold_line_rms
                "mark_missing",                                  # beyond the reference: the missing mask of masked SIR steps
                "baseline_integrated_sum_threshold",             # beyond the reference: flagging.baseline_integrated_flagger
-               "threshold_local_deviation")                     # beyond the reference: flagging.threshold_local_deviation
+               "threshold_local_deviation",                     # beyond the reference: flagging.threshold_local_deviation
+               "threshold_incoherent_noise_spectrum")           # beyond the reference: flagging.threshold_incoherent_noise_spectrum
 
 # steps that need every baseline of the scan at once: they cannot run per baseline chunk
-WHOLE_SCAN_TASKS = ("baseline_integrated_sum_threshold",)
+WHOLE_SCAN_TASKS = ("baseline_integrated_sum_threshold", "threshold_incoherent_noise_spectrum")
 
 
 # ---------------------------------------------------------------------------
@@ -111,7 +112,10 @@ def check_strategies(strategies):
     ``baseline_integrated_sum_threshold`` step whose ``min_baseline_frac`` lies
     outside [0, 1], or for a ``threshold_local_deviation`` step with a window
     that is even or outside [3, 31], a scale that is negative or NaN, or
-    ``freq_chunks < 1``."""
+    ``freq_chunks < 1``, or for a ``threshold_incoherent_noise_spectrum`` step
+    with an unknown kwarg or one out of range
+    (``flagging.check_incoherent_noise_kwargs``, ``bands_hz``,
+    ``exclude_autos``)."""
     marked = False
     for strategy in strategies:
         try:
@@ -147,6 +151,25 @@ def check_strategies(strategies):
                 flagging.check_local_deviation_kwargs(**kw)
             except ValueError as e:
                 raise ValueError("threshold_local_deviation: %s" % e)
+        elif task == "threshold_incoherent_noise_spectrum":
+            from tricolour_amd import flagging
+            kw = dict(strategy.get('kwargs') or {})
+            names = ("min_baseline_frac", "nsigma", "shapes", "streak", "narrow", "rounds", "exclude_autos", "bands_hz")
+            unknown = sorted(set(kw) - set(names))
+            if unknown:
+                raise ValueError("threshold_incoherent_noise_spectrum: unknown kwargs %s" % unknown)
+            try:
+                autos = kw.pop("exclude_autos", True)
+                if not isinstance(autos, (bool, np.bool_)):
+                    raise ValueError("exclude_autos must be True or False, got %r" % (autos,))
+                bands = kw.pop("bands_hz", None)
+                if bands is not None:
+                    bands = flagging.check_incoherent_noise_bands(bands)
+                checked = flagging.check_incoherent_noise_kwargs(**kw)
+                if len(checked[2]) + (1 if checked[3] else 0) + len(bands or ()) > flagging.INS_MAX_SHAPES:
+                    raise ValueError("at most %d shapes (bands and the streak included)" % flagging.INS_MAX_SHAPES)
+            except ValueError as e:
+                raise ValueError("threshold_incoherent_noise_spectrum: %s" % e)
 
 
 def _check_whole_scan_tasks(strategies, baseline_chunks):

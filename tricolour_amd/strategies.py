@@ -71,6 +71,24 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
             # every baseline receives the detections of the integrated image, the unselected ones included
             new_flags = flagging.baseline_integrated_flagger(vis_windows, flag_windows, select=select, **kw)
             flag_windows = lor(new_flags, flag_windows)
+        elif task == "threshold_incoherent_noise_spectrum":
+            kw = dict(kw)
+            select = None
+            if kw.pop("exclude_autos", True):
+                if ubl is None:
+                    raise ValueError("threshold_incoherent_noise_spectrum: exclude_autos needs ubl")
+                u = np.asarray(ubl)
+                select = u[:, 1] != u[:, 2]
+            bands = kw.pop("bands_hz", None)
+            if bands is not None:
+                if chan_freq is None:
+                    raise ValueError("threshold_incoherent_noise_spectrum: bands_hz needs chan_freq")
+                # on the host: a channel belongs to a band if its centre lies in it; an empty band is dropped
+                kw["shapes"] = list(kw.get("shapes", ())) + flagging.incoherent_noise_bands(
+                    flagging.check_incoherent_noise_bands(bands), chan_freq)
+            # every baseline receives the detections, the unselected ones included
+            new_flags = flagging.threshold_incoherent_noise_spectrum(vis_windows, flag_windows, select=select, **kw)
+            flag_windows = lor(new_flags, flag_windows)
         elif task == "apply_static_mask":
             new_flags = flagging.apply_static_mask(flag_windows, ubl, ant_pos, masked_channels,
                                                    chan_freq, chan_width, **kw)
