@@ -595,6 +595,93 @@ int tri_ins_apply(const uint8_t *flags, const uint8_t *mask, uint8_t *out,
                   int64_t nbl, int64_t ncorr, int64_t ntime, int64_t nchan,
                   void *stream);
 
+/*
+ * Value-driven hysteresis growth of the flags of (n_win, ntime, nchan) windows
+ * (beyond the reference; the model is the watershed of HERA's xrfi, the same
+ * idea as Canny's edge linking; the definition below is this library's own
+ * and identity with xrfi is not claimed).  What is flagged is a seed; an
+ * unflagged neighbour joins it if it clears a threshold much lower than a
+ * detection needs.  Per window, visibilities v[t, c] (complex64, or float32)
+ * and uint8 flags f[t, c] (nonzero = flagged).
+ *
+ * 1. Amplitude, the flagger's own.  complex64: a = +inf if either part is
+ *    infinite, otherwise (float)sqrt((double)re * re + (double)im * im);
+ *    float32: a = fabsf(v).  A sample counts iff f == 0 and a is not NaN.
+ * 2. Levels.  A time line is one (window, channel) over all rows; a frequency
+ *    line is one (window, time row, frequency chunk k = channels
+ *    [chunk_ends[k], chunk_ends[k + 1])); chunk_ends is a HOST array of
+ *    n_chunk_ends non-decreasing entries from 0 to nchan, read before the call
+ *    returns; an empty chunk is a no-op.  Over the m counting samples of a
+ *    line with finite a: med is their median (the middle one for odd m,
+ *    float32(x + y) / 2 of the two middle ones for even m, the sum rounded to
+ *    float32); dev_i = fabsf(a_i - med), one float32 subtraction; mad is the
+ *    median of the dev_i by the same rule.  The line is live iff m >= 3, med
+ *    and mad are finite and mad > 0.
+ * 3. Eligibility, per axis, with thr = (double)med + (nsigma_axis * 1.4826) *
+ *    (double)mad in float64 without FMA (the product is rounded before the
+ *    sum):
+ *      e_axis = counts && (a == +inf || (live && (double)a > thr));
+ *    nsigma_axis == 0 switches the axis off: e_axis = 0 everywhere.  The test
+ *    is one-sided: RFI adds power.
+ * 4. Seeds.  G_0 = (f != 0) & ~(missing != 0); missing is a uint8 image of the
+ *    shape of f or NULL (nothing is missing).  A flagged sample that is no
+ *    seed does not count: it is never eligible, blocks growth and starts none.
+ * 5. Growth, `reach` synchronous rounds, neighbours outside the window are 0:
+ *      G_{k+1}[t,c] = G_k[t,c] | (e_time[t,c] & (G_k[t-1,c] | G_k[t+1,c]))
+ *                              | (e_freq[t,c] & (G_k[t,c-1] | G_k[t,c+1]))
+ *    Growth along frequency does not stop at chunk ends; only the levels do.
+ *      out_flags = (f != 0) | G_reach   (0/1)
+ * A sample joins iff a path of at most `reach` steps leads to it from a seed
+ * through cells that are each eligible on the axis of the step taken.  Every
+ * round reads only the previous one: the result does not depend on tile shape,
+ * batch size or schedule.  No floating-point atomics; input buffers are never
+ * written.
+ *
+ * tri_hyst_levels writes the four level arrays, float32: med_time / mad_time
+ * (n_win, nchan), med_freq / mad_freq (n_win, ntime, n_chunk_ends - 1); both
+ * values of a line that is not live are NaN (0x7FC00000).  tri_hyst_eligible
+ * writes e_time and e_freq as (n_win, ntime, nchan) uint8 0/1 images.
+ * tri_hyst_grow is stage 5 alone on any three uint8 images (nonzero = set):
+ * out = G_reach with G_0 = (seeds != 0).  tri_hysteresis_growth is the whole
+ * step.
+ *
+ * Workspace (tri_hyst_workspace_bytes; the same size serves all four calls;
+ * tri_hyst_grow needs that of n_chunk_ends = 2): three bit planes of 32-channel
+ * words, rows padded to whole words, and the level arrays -- 3 / 8 byte per
+ * sample, plus 8 bytes per time line and per frequency line, each array
+ * rounded up to 256 bytes: 0.40 byte per sample at 1024 x 4096 and 10 chunks.
+ *
+ * TRI_EINVAL for NULL pointers (other than missing), negative shapes, an
+ * nsigma that is negative or NaN, a reach outside [1, 32], chunk ends that do
+ * not run from 0 to nchan, and outputs overlapping inputs; TRI_EUNSUPPORTED
+ * for dtypes other than complex64 and float32 and for more lines than one
+ * launch holds (pass fewer windows per call); TRI_EWORKSPACE when
+ * workspace_bytes < tri_hyst_workspace_bytes().  Empty shapes return TRI_OK
+ * without a launch.
+ */
+size_t tri_hyst_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan,
+                                int64_t n_chunk_ends);
+int tri_hyst_levels(const void *vis, int vis_dtype, const uint8_t *flags,
+                    int64_t n_win, int64_t ntime, int64_t nchan,
+                    const int64_t *chunk_ends, int64_t n_chunk_ends,
+                    float *med_time, float *mad_time, float *med_freq, float *mad_freq,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int tri_hyst_eligible(const void *vis, int vis_dtype, const uint8_t *flags,
+                      int64_t n_win, int64_t ntime, int64_t nchan,
+                      double nsigma_time, double nsigma_freq,
+                      const int64_t *chunk_ends, int64_t n_chunk_ends,
+                      uint8_t *e_time, uint8_t *e_freq,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int tri_hyst_grow(const uint8_t *seeds, const uint8_t *e_time, const uint8_t *e_freq,
+                  uint8_t *out, int64_t n_win, int64_t ntime, int64_t nchan,
+                  int64_t reach, void *workspace, size_t workspace_bytes, void *stream);
+int tri_hysteresis_growth(const void *vis, int vis_dtype, const uint8_t *flags,
+                          const uint8_t *missing /* may be NULL */, uint8_t *out_flags,
+                          int64_t n_win, int64_t ntime, int64_t nchan,
+                          double nsigma_time, double nsigma_freq, int64_t reach,
+                          const int64_t *chunk_ends, int64_t n_chunk_ends,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

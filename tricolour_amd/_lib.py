@@ -19,7 +19,7 @@ DEPENDS = [os.path.join(_HERE, "csrc", f) for f in (
     "kernels_boxweight.hpp", "kernels_boxexact.hpp",
     "kernels_sumthreshold.hpp", "kernels_scan.hpp", "kernels_sir.hpp", "kernels_linerms.hpp",
     os.path.join("steps", "kernels_blint.hpp"), os.path.join("steps", "ldev", "kernels_ldev.hpp"),
-    os.path.join("steps", "ins", "kernels_ins.hpp"))]
+    os.path.join("steps", "ins", "kernels_ins.hpp"), os.path.join("steps", "hyst", "kernels_hyst.hpp"))]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tricolour_amd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
@@ -196,6 +196,18 @@ _SIGNATURES = {
                                 C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int64, C.c_double, C.c_int64, C.c_void_p,
                                 C.c_void_p, C.c_size_t, C.c_void_p]),
     "tri_ins_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "tri_hyst_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "tri_hyst_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
+    "tri_hyst_eligible": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double,
+                                    C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
+    "tri_hyst_grow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tri_hysteresis_growth": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                        C.c_int64, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "tri_last_error": (C.c_char_p, []),
     "tri_version": (C.c_int, []),
     "tri_bench_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

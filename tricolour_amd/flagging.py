@@ -984,6 +984,198 @@ def threshold_local_deviation(vis, flags, window_time=3, window_freq=3, scale_ti
     return _like_flags(torch, out, flags, from_numpy)
 
 
+HYST_MISSING = ("none", "input", "marked")     # the `missing` vocabulary of the strategy step (as the masked SIR step's)
+
+
+def _hyst_reach(reach):
+    ok = not isinstance(reach, bool) and isinstance(reach, (int, np.integer)) and 1 <= int(reach) <= 32
+    if not ok:
+        raise ValueError("reach must be an integer in [1, 32], got %r" % (reach,))
+    return int(reach)
+
+
+def check_hysteresis_kwargs(nsigma_time=2.5, nsigma_freq=2.5, reach=8, freq_chunks=10, missing="none"):
+    """The argument checks of the ``hysteresis_growth`` step (no device work): an ``nsigma`` that is negative or NaN, a
+    ``reach`` that is no integer in [1, 32], ``freq_chunks < 1`` and a ``missing`` other than ``none`` / ``input`` /
+    ``marked`` raise ``ValueError``.  Returns the values."""
+    if not isinstance(missing, str) or missing not in HYST_MISSING:
+        raise ValueError("missing must be 'none', 'input' or 'marked', got %r" % (missing,))
+    return (_ldev_scale("nsigma_time", nsigma_time), _ldev_scale("nsigma_freq", nsigma_freq), _hyst_reach(reach),
+            _ldev_chunks(freq_chunks), missing)
+
+
+def _hyst_ends(nchan, freq_chunks):
+    ends = np.linspace(0, nchan, freq_chunks + 1).astype(np.int64)           # as the flagger's chunks
+    return ends, (C.c_int64 * len(ends))(*[int(e) for e in ends])
+
+
+def _hyst_batch(torch, lib, device, n_win, ntime, nchan, n_ends, max_windows=None):
+    """Windows per call: as many as the workspace budget and one launch hold (every launch is one-dimensional and
+    holds fewer than 2^31 blocks: one per 8 channels and one per 4 (row, chunk) lines in the level passes, one per
+    8 rows x 256 channels in the eligibility pass)."""
+    lim = (1 << 31) - 1
+    batch = max(1, min(n_win, lim // -(-nchan // 8), (4 * lim) // (ntime * (n_ends - 1)) - 1,
+                       lim // (-(-ntime // 8) * -(-nchan // 256))))
+    if max_windows:
+        batch = max(1, min(batch, int(max_windows)))
+    budget = _workspace_budget(torch, device)
+    while batch > 1 and lib.tri_hyst_workspace_bytes(batch, ntime, nchan, n_ends) > budget:
+        batch = (batch + 1) // 2
+    return batch, lib.tri_hyst_workspace_bytes(batch, ntime, nchan, n_ends)
+
+
+def robust_line_levels(vis, flags, freq_chunks=10, _max_windows=None):
+    """Median and median absolute deviation of the amplitudes of every line of
+    (bl, corr, time, chan) windows, over the unflagged samples with a finite
+    amplitude: ``(med_t, mad_t)`` of shape (bl, corr, chan) for the lines along
+    time, ``(med_f, mad_f)`` of shape (bl, corr, time, freq_chunks) for every
+    time row's frequency chunks (``linspace(0, nchan, freq_chunks + 1)``).
+    float32; ``mad`` is the median of ``fabsf(a - med)``; both are NaN where the
+    line is not live (fewer than 3 samples, or a ``mad`` of 0).  The levels of
+    :func:`hysteresis_growth`.  Returns numpy arrays for numpy input, tensors
+    on the device otherwise.  Inputs are not modified."""
+    freq_chunks = _ldev_chunks(freq_chunks)
+    torch, v, f8, code, from_numpy, device = _line_rms_inputs("robust_line_levels", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    ends, ends_c = _hyst_ends(nchan, freq_chunks)
+    nan = float("nan")
+    lev = [torch.full((nbl, ncorr, nchan), nan, dtype=torch.float32, device=device) for _ in range(2)] + \
+          [torch.full((nbl, ncorr, ntime, freq_chunks), nan, dtype=torch.float32, device=device) for _ in range(2)]
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
+            ws = _workspace(torch, device, nbytes)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_hyst_levels(
+                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
+                    ends_c, len(ends), lev[0].data_ptr() + w0 * nchan * 4, lev[1].data_ptr() + w0 * nchan * 4,
+                    lev[2].data_ptr() + w0 * ntime * freq_chunks * 4, lev[3].data_ptr() + w0 * ntime * freq_chunks * 4,
+                    ws.data_ptr(), ws.numel(), stream))
+    if from_numpy:
+        return tuple(a.cpu().numpy() for a in lev)
+    return tuple(lev)
+
+
+def growth_eligibility(vis, flags, nsigma_time=2.5, nsigma_freq=2.5, freq_chunks=10, _max_windows=None):
+    """The two eligibility images of :func:`hysteresis_growth`, bool, of the
+    shape of ``vis``: ``e_time`` is set where an unflagged sample's amplitude
+    exceeds ``med + nsigma_time * 1.4826 * mad`` of its (window, channel) line,
+    ``e_freq`` the same with the levels of its (window, time row, frequency
+    chunk); an unflagged ``+inf`` amplitude is eligible on every axis that is
+    on, a NaN never.  ``nsigma = 0`` switches an axis off."""
+    nsigma_time, nsigma_freq = _ldev_scale("nsigma_time", nsigma_time), _ldev_scale("nsigma_freq", nsigma_freq)
+    freq_chunks = _ldev_chunks(freq_chunks)
+    torch, v, f8, code, from_numpy, device = _line_rms_inputs("growth_eligibility", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    ends, ends_c = _hyst_ends(nchan, freq_chunks)
+    e_t = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    e_f = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
+            ws = _workspace(torch, device, nbytes)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_hyst_eligible(
+                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
+                    nsigma_time, nsigma_freq, ends_c, len(ends), e_t.data_ptr() + w0 * per, e_f.data_ptr() + w0 * per,
+                    ws.data_ptr(), ws.numel(), stream))
+    e_t, e_f = e_t.view(torch.bool), e_f.view(torch.bool)
+    if from_numpy:
+        return e_t.cpu().numpy(), e_f.cpu().numpy()
+    return e_t, e_f
+
+
+def grow_flags(seeds, e_time, e_freq, reach=8, _max_windows=None):
+    """The growth rounds of :func:`hysteresis_growth` on any three images of
+    shape (bl, corr, time, chan) (nonzero = set): ``G_0 = seeds`` and, ``reach``
+    times, ``G |= (e_time & (G[t - 1] | G[t + 1])) | (e_freq & (G[c - 1] | G[c +
+    1]))`` with every round reading the previous one and nothing beyond the
+    window's edges.  A sample joins iff a path of at most ``reach`` steps leads
+    to it from a seed through cells that are each eligible on the axis of the
+    step taken.  Returns ``G_reach`` in the container / dtype of ``seeds``; the
+    inputs are not modified."""
+    reach = _hyst_reach(reach)
+    shape = tuple(seeds.shape)
+    if len(shape) != 4:
+        raise ValueError("seeds must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    for name, e in (("e_time", e_time), ("e_freq", e_freq)):
+        if tuple(e.shape) != shape:
+            raise ValueError("seeds and %s must have the same shape, got %s and %s" % (name, shape, tuple(e.shape)))
+    torch = _require_gpu()
+    from_numpy = isinstance(seeds, np.ndarray)
+    device = seeds.device if (torch.is_tensor(seeds) and seeds.is_cuda) else \
+        torch.device("cuda", torch.cuda.current_device())
+    s8, t8, f8 = (_flags_u8(torch, a, device) for a in (seeds, e_time, e_freq))
+    nbl, ncorr, ntime, nchan = (int(s) for s in shape)
+    n_win = nbl * ncorr
+    out = torch.empty(s8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, 2, _max_windows)
+            ws = _workspace(torch, device, nbytes)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_hyst_grow(
+                    s8.data_ptr() + w0 * per, t8.data_ptr() + w0 * per, f8.data_ptr() + w0 * per,
+                    out.data_ptr() + w0 * per, b, ntime, nchan, reach, ws.data_ptr(), ws.numel(), stream))
+    return _like_flags(torch, out, seeds, from_numpy)
+
+
+def hysteresis_growth(vis, flags, missing=None, nsigma_time=2.5, nsigma_freq=2.5, reach=8, freq_chunks=10,
+                      _max_windows=None):
+    """Value-driven growth of the flags of (bl, corr, time, chan) windows by
+    two-level (hysteresis) thresholding (after the watershed of HERA's
+    ``xrfi``; the definition is this library's own): what is flagged is a seed,
+    and an unflagged neighbour along time (frequency) joins when its amplitude
+    exceeds ``med + nsigma * 1.4826 * mad`` of its (window, channel) line (its
+    (window, time row, frequency chunk) line) -- see :func:`robust_line_levels`
+    and :func:`growth_eligibility`.  ``reach`` synchronous rounds
+    (:func:`grow_flags`): a sample joins iff a path of at most ``reach`` steps
+    leads to it from a seed through cells that are each eligible on the axis of
+    the step taken.  ``missing`` (shape of ``flags``, nonzero = missing, or
+    None): flagged samples that are no detections; they seed nothing and, being
+    flagged, block growth.  ``nsigma = 0`` switches an axis off.  ``out = flags
+    | G_reach``.  Definition: ``include/tricolour_amd.h``.  Returns a new array
+    in the container / dtype of ``flags``; the inputs are not modified."""
+    nsigma_time, nsigma_freq, reach, freq_chunks, _ = check_hysteresis_kwargs(nsigma_time, nsigma_freq, reach, freq_chunks)
+    if missing is not None and tuple(missing.shape) != tuple(flags.shape):
+        raise ValueError("flags and missing must have the same shape, got %s and %s"
+                         % (tuple(flags.shape), tuple(missing.shape)))
+    torch, v, f8, code, from_numpy, device = _line_rms_inputs("hysteresis_growth", vis, flags)
+    m8 = _flags_u8(torch, missing, device) if missing is not None else None
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    ends, ends_c = _hyst_ends(nchan, freq_chunks)
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
+            ws = _workspace(torch, device, nbytes)
+            per = ntime * nchan
+            for w0 in range(0, n_win, batch):
+                b = min(batch, n_win - w0)
+                _lib.check(lib.tri_hysteresis_growth(
+                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per,
+                    m8.data_ptr() + w0 * per if m8 is not None else None, out.data_ptr() + w0 * per, b, ntime, nchan,
+                    nsigma_time, nsigma_freq, reach, ends_c, len(ends), ws.data_ptr(), ws.numel(), stream))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
 def _bli_inputs(name, vis, flags, select):
     """Checks of the baseline-integration calls (all before any device work), then the device inputs:
     (torch, vis, flags uint8, dtype code, from_numpy, device, select uint8 on the device or None)."""

@@ -31,7 +31,8 @@ VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with
                "mark_missing",                                  # beyond the reference: the missing mask of masked SIR steps
                "baseline_integrated_sum_threshold",             # beyond the reference: flagging.baseline_integrated_flagger
                "threshold_local_deviation",                     # beyond the reference: flagging.threshold_local_deviation
-               "threshold_incoherent_noise_spectrum")           # beyond the reference: flagging.threshold_incoherent_noise_spectrum
+               "threshold_incoherent_noise_spectrum",           # beyond the reference: flagging.threshold_incoherent_noise_spectrum
+               "hysteresis_growth")                             # beyond the reference: flagging.hysteresis_growth
 
 # steps that need every baseline of the scan at once: they cannot run per baseline chunk
 WHOLE_SCAN_TASKS = ("baseline_integrated_sum_threshold", "threshold_incoherent_noise_spectrum")
@@ -115,7 +116,9 @@ def check_strategies(strategies):
     ``freq_chunks < 1``, or for a ``threshold_incoherent_noise_spectrum`` step
     with an unknown kwarg or one out of range
     (``flagging.check_incoherent_noise_kwargs``, ``bands_hz``,
-    ``exclude_autos``)."""
+    ``exclude_autos``), or for a ``hysteresis_growth`` step with an unknown
+    kwarg, one out of range (``flagging.check_hysteresis_kwargs``) or
+    ``missing: marked`` with no ``mark_missing`` step before it."""
     marked = False
     for strategy in strategies:
         try:
@@ -151,6 +154,19 @@ def check_strategies(strategies):
                 flagging.check_local_deviation_kwargs(**kw)
             except ValueError as e:
                 raise ValueError("threshold_local_deviation: %s" % e)
+        elif task == "hysteresis_growth":
+            from tricolour_amd import flagging
+            kw = strategy.get('kwargs') or {}
+            names = ("nsigma_time", "nsigma_freq", "reach", "freq_chunks", "missing")
+            unknown = sorted(set(kw) - set(names))
+            if unknown:
+                raise ValueError("hysteresis_growth: unknown kwargs %s" % unknown)
+            try:
+                which = flagging.check_hysteresis_kwargs(**kw)[4]
+            except ValueError as e:
+                raise ValueError("hysteresis_growth: %s" % e)
+            if which == "marked" and not marked:
+                raise ValueError("hysteresis_growth: missing 'marked' needs an earlier mark_missing")
         elif task == "threshold_incoherent_noise_spectrum":
             from tricolour_amd import flagging
             kw = dict(strategy.get('kwargs') or {})

@@ -60,6 +60,16 @@ def apply_strategies(strategies, flag_windows, vis_windows, ubl=None, ant_pos=No
         elif task == "threshold_local_deviation":
             new_flags = flagging.threshold_local_deviation(vis_windows, flag_windows, **kw)
             flag_windows = lor(new_flags, flag_windows)
+        elif task == "hysteresis_growth":
+            kw = dict(kw)
+            which = kw.pop("missing", "none")
+            if which not in flagging.HYST_MISSING:
+                raise ValueError("hysteresis_growth: missing must be 'none', 'input' or 'marked', got %r" % (which,))
+            if which == "marked" and marked is None:
+                raise ValueError("hysteresis_growth: missing 'marked' needs an earlier mark_missing")
+            mask = {"none": None, "input": original, "marked": marked}[which]
+            new_flags = flagging.hysteresis_growth(vis_windows, flag_windows, missing=mask, **kw)
+            flag_windows = lor(new_flags, flag_windows)
         elif task == "baseline_integrated_sum_threshold":
             kw = dict(kw)
             select = None
