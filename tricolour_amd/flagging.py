@@ -14,6 +14,7 @@ call raises ``RuntimeError``.
 """
 import ctypes as C
 import collections
+import functools
 import os
 import threading
 import time
@@ -177,6 +178,46 @@ def _pick_batch(lib, p, n_cp, T, F, budget):
         else:
             hi = mid - 1
     return lo, lib.tri_workspace_bytes(lo, T, F, C.byref(p))
+
+
+def _window_batch(n_win, ws_bytes, budget, launch_cap=None, max_windows=None):
+    """``(batch, nbytes)``: windows per library call of a strategy step and the workspace they need.  All ``n_win``,
+    capped by what one launch holds (``launch_cap``, each family's own figure) and by ``max_windows`` (how tests force
+    batches), then halved until ``ws_bytes(batch)`` fits ``budget``: an int, or a callable asked only if a workspace is
+    needed at all.  At least one window.  Pure arithmetic."""
+    batch = n_win if launch_cap is None else max(1, min(n_win, launch_cap))
+    if max_windows:
+        batch = max(1, min(batch, int(max_windows)))
+    nbytes = ws_bytes(batch)
+    if nbytes > 0:
+        if callable(budget):
+            budget = budget()
+        while batch > 1 and ws_bytes(batch) > budget:
+            batch = (batch + 1) // 2
+        nbytes = ws_bytes(batch)
+    return batch, nbytes
+
+
+def _batches(n_win, batch):
+    """``(w0, b)``: the first window and the number of windows of every batch."""
+    for w0 in range(0, n_win, batch):
+        yield w0, min(batch, n_win - w0)
+
+
+def _at(t, n_win, w0):
+    """Address of window ``w0`` of a contiguous tensor that holds ``n_win`` windows (None stays None)."""
+    return None if t is None else t.data_ptr() + w0 * (t.numel() // n_win) * t.element_size()
+
+
+def _window_launches(torch, device, n_win, ws_bytes, launch_cap=None, max_windows=None, workspace=True):
+    """The frame of a batched step on the current device: its batches, sized against this call's budget, as ``(at, b)``
+    -- ``at(t)``: :func:`_at` of the batch's first window, ``b``: its windows -- and the ``(workspace, its bytes, stream)``
+    that end a batched entry point's arguments: this thread's workspace, or ``None, 0`` if none is needed or taken."""
+    batch, nbytes = _window_batch(n_win, ws_bytes, lambda: _workspace_budget(torch, device), launch_cap, max_windows)
+    ws = _workspace(torch, device, nbytes) if nbytes > 0 and workspace else None
+    stream = torch.cuda.current_stream(device).cuda_stream
+    launches = ((functools.partial(_at, n_win=n_win, w0=w0), b) for w0, b in _batches(n_win, batch))
+    return launches, ((ws.data_ptr(), ws.numel(), stream) if ws is not None else (None, 0, stream))
 
 
 def _host_call_stream(torch, vis, flags):
@@ -573,6 +614,11 @@ def _like_flags(torch, out_u8, like, from_numpy):
     return out_u8.view(torch.bool)
 
 
+def _like_input(from_numpy, *tensors):
+    """Device results -> what the caller gets: numpy arrays for numpy input, the tensors otherwise (a tuple)."""
+    return tuple(t.cpu().numpy() for t in tensors) if from_numpy else tensors
+
+
 def _apply_bl_chan(torch, flags, bl_sel, chan_masks, mode):
     from_numpy = isinstance(flags, np.ndarray)
     device = flags.device if (torch.is_tensor(flags) and flags.is_cuda) else \
@@ -668,11 +714,9 @@ def uvcontsub_flagger(vis, flags, major_cycles=5, or_original_from_cycle=1,
     n_cp = nbl * ncorr
     with torch.cuda.device(device):
         if n_cp > 0 and ntime > 0 and nchan > 0:
-            budget = _workspace_budget(torch, device)
-            batch = max(1, min(n_cp, 4096))
-            while batch > 1 and lib.tri_uvcontsub_workspace_bytes(batch, ntime, nchan) > budget:
-                batch = (batch + 1) // 2
-            nbytes = lib.tri_uvcontsub_workspace_bytes(batch, ntime, nchan)
+            # all windows go in one call: the library batches them itself, within the workspace it is handed
+            _, nbytes = _window_batch(n_cp, lambda b: lib.tri_uvcontsub_workspace_bytes(b, ntime, nchan),
+                                      lambda: _workspace_budget(torch, device), launch_cap=4096)
             ws = _workspace(torch, device, nbytes)
             _lib.check(lib.tri_uvcontsub_flagger(
                 v.data_ptr(), f8.data_ptr(), out.data_ptr(), n_cp, ntime, nchan,
@@ -711,29 +755,15 @@ def _sir(flags, missing, eta_time, eta_freq, penalty):
     ws_bytes = lib.tri_sir_workspace_bytes if m8 is None else lib.tri_sir_masked_workspace_bytes
     with torch.cuda.device(device):
         if out.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
             # the workspace holds per-segment aggregates of lines longer than one workgroup; batch the windows
-            # when even that does not fit
-            batch = n_win
-            nbytes = ws_bytes(batch, ntime, nchan)
-            if nbytes > 0:
-                budget = _workspace_budget(torch, device)
-                while batch > 1 and ws_bytes(batch, ntime, nchan) > budget:
-                    batch = (batch + 1) // 2
-                nbytes = ws_bytes(batch, ntime, nchan)
-            ws = _workspace(torch, device, nbytes) if nbytes > 0 else None
-            wsp, wsn = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
+            # when even that does not fit (the only family without a launch cap)
+            launches, tail = _window_launches(torch, device, n_win, lambda b: ws_bytes(b, ntime, nchan))
+            for at, b in launches:
                 if m8 is None:
-                    _lib.check(lib.tri_scale_invariant_rank(
-                        f8.data_ptr() + w0 * per, out.data_ptr() + w0 * per, b, ntime, nchan,
-                        eta_time, eta_freq, wsp, wsn, stream))
+                    _lib.check(lib.tri_scale_invariant_rank(at(f8), at(out), b, ntime, nchan, eta_time, eta_freq, *tail))
                 else:
-                    _lib.check(lib.tri_scale_invariant_rank_masked(
-                        f8.data_ptr() + w0 * per, m8.data_ptr() + w0 * per, out.data_ptr() + w0 * per, b, ntime, nchan,
-                        eta_time, eta_freq, penalty, wsp, wsn, stream))
+                    _lib.check(lib.tri_scale_invariant_rank_masked(at(f8), at(m8), at(out), b, ntime, nchan,
+                                                                   eta_time, eta_freq, penalty, *tail))
     return _like_flags(torch, out, flags, from_numpy)
 
 
@@ -781,17 +811,11 @@ def _line_rms_inputs(name, vis, flags):
     return torch, v, _flags_u8(torch, flags, device), code, from_numpy, device
 
 
-def _line_rms_batch(torch, lib, device, n_win, ntime, nchan, max_windows=None):
-    """Windows per call: as many as the workspace budget and one launch hold (a launch holds 2^24 blocks: one per
-    time row in the apply pass, one per 64 x 1024 tile in the power pass)."""
+def _line_rms_cap(ntime, nchan):
+    """Windows one launch of the line-RMS family holds (a launch holds 2^24 blocks: one per time row in the apply
+    pass, one per 64 x 1024 tile in the power pass)."""
     tiles = -(-ntime // 64) * -(-nchan // 1024)
-    batch = max(1, min(n_win, ((1 << 24) - 1) // max(ntime, tiles), ((1 << 31) - 1) // (ntime + nchan)))
-    if max_windows:
-        batch = max(1, min(batch, int(max_windows)))
-    budget = _workspace_budget(torch, device)
-    while batch > 1 and lib.tri_line_rms_workspace_bytes(batch, ntime, nchan) > budget:
-        batch = (batch + 1) // 2
-    return batch, lib.tri_line_rms_workspace_bytes(batch, ntime, nchan)
+    return min(((1 << 24) - 1) // max(ntime, tiles), ((1 << 31) - 1) // (ntime + nchan))
 
 
 def line_rms(vis, flags, _max_windows=None):
@@ -810,19 +834,12 @@ def line_rms(vis, flags, _max_windows=None):
     lib = _lib.lib()
     with torch.cuda.device(device):
         if v.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, nbytes = _line_rms_batch(torch, lib, device, n_win, ntime, nchan, _max_windows)
-            ws = _workspace(torch, device, nbytes)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_line_rms(
-                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
-                    rms_t.data_ptr() + w0 * ntime * 8, rms_c.data_ptr() + w0 * nchan * 8, None, None,
-                    ws.data_ptr(), ws.numel(), stream))
-    if from_numpy:
-        return rms_t.cpu().numpy(), rms_c.cpu().numpy()
-    return rms_t, rms_c
+            launches, tail = _window_launches(
+                torch, device, n_win, lambda b: lib.tri_line_rms_workspace_bytes(b, ntime, nchan),
+                _line_rms_cap(ntime, nchan), _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_line_rms(at(v), code, at(f8), b, ntime, nchan, at(rms_t), at(rms_c), None, None, *tail))
+    return _like_input(from_numpy, rms_t, rms_c)
 
 
 def threshold_line_rms(vis, flags, nsigma_time=3.5, nsigma_freq=3.0, flag_low=True):
@@ -848,16 +865,12 @@ def threshold_line_rms(vis, flags, nsigma_time=3.5, nsigma_freq=3.0, flag_low=Tr
     lib = _lib.lib()
     with torch.cuda.device(device):
         if out.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, nbytes = _line_rms_batch(torch, lib, device, n_win, ntime, nchan)
-            ws = _workspace(torch, device, nbytes)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_line_rms_threshold(
-                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per,
-                    out.data_ptr() + w0 * per, b, ntime, nchan, nsigma_time, nsigma_freq, 1 if flag_low else 0,
-                    ws.data_ptr(), ws.numel(), stream))
+            launches, tail = _window_launches(
+                torch, device, n_win, lambda b: lib.tri_line_rms_workspace_bytes(b, ntime, nchan),
+                _line_rms_cap(ntime, nchan))
+            for at, b in launches:
+                _lib.check(lib.tri_line_rms_threshold(at(v), code, at(f8), at(out), b, ntime, nchan,
+                                                      nsigma_time, nsigma_freq, 1 if flag_low else 0, *tail))
     return _like_flags(torch, out, flags, from_numpy)
 
 
@@ -896,20 +909,20 @@ def check_local_deviation_kwargs(window_time=3, window_freq=3, scale_time=3.5, s
             _ldev_scale("scale_time", scale_time), _ldev_scale("scale_freq", scale_freq), _ldev_chunks(freq_chunks))
 
 
-def _ldev_batch(torch, lib, device, n_win, ntime, nchan, n_ends, max_windows=None):
-    """Windows per call: as many as the workspace budget and one launch hold (every launch is one-dimensional and
-    holds fewer than 2^31 blocks: one per 8 rows x 1024 channels in the frequency pass, one per 4 (row, chunk) lines
-    in its level pass, one per 256 samples in the scalar apply pass)."""
+def _chunk_ends(nchan, freq_chunks):
+    """The frequency chunk ends of the flagger (flagging.py:1172), as an array and as the library's int64 argument."""
+    ends = np.linspace(0, nchan, freq_chunks + 1).astype(np.int64)
+    return ends, (C.c_int64 * len(ends))(*[int(e) for e in ends])
+
+
+def _ldev_cap(ntime, nchan, n_ends):
+    """Windows one launch of the local-deviation family holds (every launch is one-dimensional and holds fewer than
+    2^31 blocks: one per 8 rows x 1024 channels in the frequency pass, one per 4 (row, chunk) lines in its level
+    pass, one per 256 samples in the scalar apply pass)."""
     lim = (1 << 31) - 1
     strips = -(-nchan // 1024)
-    batch = max(1, min(n_win, lim // (ntime * strips), lim // -(-nchan // 32), lim // (ntime * (n_ends - 1)),
-                       lim // -(-(ntime * nchan) // 256)))
-    if max_windows:
-        batch = max(1, min(batch, int(max_windows)))
-    budget = _workspace_budget(torch, device)
-    while batch > 1 and lib.tri_local_deviation_workspace_bytes(batch, ntime, nchan, n_ends) > budget:
-        batch = (batch + 1) // 2
-    return batch, lib.tri_local_deviation_workspace_bytes(batch, ntime, nchan, n_ends)
+    return min(lim // (ntime * strips), lim // -(-nchan // 32), lim // (ntime * (n_ends - 1)),
+               lim // -(-(ntime * nchan) // 256))
 
 
 def local_deviation(vis, flags, window_time=3, window_freq=3, _max_windows=None):
@@ -932,17 +945,14 @@ def local_deviation(vis, flags, window_time=3, window_freq=3, _max_windows=None)
     lib = _lib.lib()
     with torch.cuda.device(device):
         if v.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, _ = _ldev_batch(torch, lib, device, n_win, ntime, nchan, 2, _max_windows)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_local_deviation(
-                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
-                    window_time, window_freq, d_t.data_ptr() + w0 * per * 4, d_f.data_ptr() + w0 * per * 4, stream))
-    if from_numpy:
-        return d_t.cpu().numpy(), d_f.cpu().numpy()
-    return d_t, d_f
+            # batched as the thresholding call with one chunk (n_ends = 2), but the deviations alone take no workspace
+            launches, (_, _, stream) = _window_launches(
+                torch, device, n_win, lambda b: lib.tri_local_deviation_workspace_bytes(b, ntime, nchan, 2),
+                _ldev_cap(ntime, nchan, 2), _max_windows, workspace=False)
+            for at, b in launches:
+                _lib.check(lib.tri_local_deviation(at(v), code, at(f8), b, ntime, nchan, window_time, window_freq,
+                                                   at(d_t), at(d_f), stream))
+    return _like_input(from_numpy, d_t, d_f)
 
 
 def threshold_local_deviation(vis, flags, window_time=3, window_freq=3, scale_time=3.5, scale_freq=3.5, freq_chunks=10,
@@ -965,22 +975,18 @@ def threshold_local_deviation(vis, flags, window_time=3, window_freq=3, scale_ti
     torch, v, f8, code, from_numpy, device = _line_rms_inputs("threshold_local_deviation", vis, flags)
     nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
     n_win = nbl * ncorr
-    ends = np.linspace(0, nchan, freq_chunks + 1).astype(np.int64)           # as the flagger's chunks (flagging.py:1172)
-    ends_c = (C.c_int64 * len(ends))(*[int(e) for e in ends])
+    ends, ends_c = _chunk_ends(nchan, freq_chunks)
     out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
     lib = _lib.lib()
     with torch.cuda.device(device):
         if out.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, nbytes = _ldev_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
-            ws = _workspace(torch, device, nbytes)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
+            launches, tail = _window_launches(
+                torch, device, n_win, lambda b: lib.tri_local_deviation_workspace_bytes(b, ntime, nchan, len(ends)),
+                _ldev_cap(ntime, nchan, len(ends)), _max_windows)
+            for at, b in launches:
                 _lib.check(lib.tri_local_deviation_threshold(
-                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per,
-                    out.data_ptr() + w0 * per, b, ntime, nchan, window_time, window_freq, scale_time, scale_freq,
-                    ends_c, len(ends), ws.data_ptr(), ws.numel(), stream))
+                    at(v), code, at(f8), at(out), b, ntime, nchan, window_time, window_freq, scale_time, scale_freq,
+                    ends_c, len(ends), *tail))
     return _like_flags(torch, out, flags, from_numpy)
 
 
@@ -1004,24 +1010,17 @@ def check_hysteresis_kwargs(nsigma_time=2.5, nsigma_freq=2.5, reach=8, freq_chun
             _ldev_chunks(freq_chunks), missing)
 
 
-def _hyst_ends(nchan, freq_chunks):
-    ends = np.linspace(0, nchan, freq_chunks + 1).astype(np.int64)           # as the flagger's chunks
-    return ends, (C.c_int64 * len(ends))(*[int(e) for e in ends])
-
-
-def _hyst_batch(torch, lib, device, n_win, ntime, nchan, n_ends, max_windows=None):
-    """Windows per call: as many as the workspace budget and one launch hold (every launch is one-dimensional and
-    holds fewer than 2^31 blocks: one per 8 channels and one per 4 (row, chunk) lines in the level passes, one per
-    8 rows x 256 channels in the eligibility pass)."""
+def _hyst_cap(ntime, nchan, n_ends):
+    """Windows one launch of the hysteresis family holds (every launch is one-dimensional and holds fewer than 2^31
+    blocks: one per 8 channels and one per 4 (row, chunk) lines in the level passes, one per 8 rows x 256 channels in
+    the eligibility pass)."""
     lim = (1 << 31) - 1
-    batch = max(1, min(n_win, lim // -(-nchan // 8), (4 * lim) // (ntime * (n_ends - 1)) - 1,
-                       lim // (-(-ntime // 8) * -(-nchan // 256))))
-    if max_windows:
-        batch = max(1, min(batch, int(max_windows)))
-    budget = _workspace_budget(torch, device)
-    while batch > 1 and lib.tri_hyst_workspace_bytes(batch, ntime, nchan, n_ends) > budget:
-        batch = (batch + 1) // 2
-    return batch, lib.tri_hyst_workspace_bytes(batch, ntime, nchan, n_ends)
+    return min(lim // -(-nchan // 8), (4 * lim) // (ntime * (n_ends - 1)) - 1, lim // (-(-ntime // 8) * -(-nchan // 256)))
+
+
+def _hyst_launches(torch, lib, device, n_win, ntime, nchan, n_ends, max_windows):
+    return _window_launches(torch, device, n_win, lambda b: lib.tri_hyst_workspace_bytes(b, ntime, nchan, n_ends),
+                            _hyst_cap(ntime, nchan, n_ends), max_windows)
 
 
 def robust_line_levels(vis, flags, freq_chunks=10, _max_windows=None):
@@ -1038,27 +1037,18 @@ def robust_line_levels(vis, flags, freq_chunks=10, _max_windows=None):
     torch, v, f8, code, from_numpy, device = _line_rms_inputs("robust_line_levels", vis, flags)
     nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
     n_win = nbl * ncorr
-    ends, ends_c = _hyst_ends(nchan, freq_chunks)
+    ends, ends_c = _chunk_ends(nchan, freq_chunks)
     nan = float("nan")
     lev = [torch.full((nbl, ncorr, nchan), nan, dtype=torch.float32, device=device) for _ in range(2)] + \
           [torch.full((nbl, ncorr, ntime, freq_chunks), nan, dtype=torch.float32, device=device) for _ in range(2)]
     lib = _lib.lib()
     with torch.cuda.device(device):
         if v.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
-            ws = _workspace(torch, device, nbytes)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_hyst_levels(
-                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
-                    ends_c, len(ends), lev[0].data_ptr() + w0 * nchan * 4, lev[1].data_ptr() + w0 * nchan * 4,
-                    lev[2].data_ptr() + w0 * ntime * freq_chunks * 4, lev[3].data_ptr() + w0 * ntime * freq_chunks * 4,
-                    ws.data_ptr(), ws.numel(), stream))
-    if from_numpy:
-        return tuple(a.cpu().numpy() for a in lev)
-    return tuple(lev)
+            launches, tail = _hyst_launches(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_hyst_levels(at(v), code, at(f8), b, ntime, nchan, ends_c, len(ends),
+                                               *(at(a) for a in lev), *tail))
+    return _like_input(from_numpy, *lev)
 
 
 def growth_eligibility(vis, flags, nsigma_time=2.5, nsigma_freq=2.5, freq_chunks=10, _max_windows=None):
@@ -1073,26 +1063,18 @@ def growth_eligibility(vis, flags, nsigma_time=2.5, nsigma_freq=2.5, freq_chunks
     torch, v, f8, code, from_numpy, device = _line_rms_inputs("growth_eligibility", vis, flags)
     nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
     n_win = nbl * ncorr
-    ends, ends_c = _hyst_ends(nchan, freq_chunks)
+    ends, ends_c = _chunk_ends(nchan, freq_chunks)
     e_t = torch.empty(f8.shape, dtype=torch.uint8, device=device)
     e_f = torch.empty(f8.shape, dtype=torch.uint8, device=device)
     lib = _lib.lib()
     with torch.cuda.device(device):
         if v.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
-            ws = _workspace(torch, device, nbytes)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_hyst_eligible(
-                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per, b, ntime, nchan,
-                    nsigma_time, nsigma_freq, ends_c, len(ends), e_t.data_ptr() + w0 * per, e_f.data_ptr() + w0 * per,
-                    ws.data_ptr(), ws.numel(), stream))
+            launches, tail = _hyst_launches(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_hyst_eligible(at(v), code, at(f8), b, ntime, nchan, nsigma_time, nsigma_freq,
+                                                 ends_c, len(ends), at(e_t), at(e_f), *tail))
     e_t, e_f = e_t.view(torch.bool), e_f.view(torch.bool)
-    if from_numpy:
-        return e_t.cpu().numpy(), e_f.cpu().numpy()
-    return e_t, e_f
+    return _like_input(from_numpy, e_t, e_f)
 
 
 def grow_flags(seeds, e_time, e_freq, reach=8, _max_windows=None):
@@ -1122,15 +1104,9 @@ def grow_flags(seeds, e_time, e_freq, reach=8, _max_windows=None):
     lib = _lib.lib()
     with torch.cuda.device(device):
         if out.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, 2, _max_windows)
-            ws = _workspace(torch, device, nbytes)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_hyst_grow(
-                    s8.data_ptr() + w0 * per, t8.data_ptr() + w0 * per, f8.data_ptr() + w0 * per,
-                    out.data_ptr() + w0 * per, b, ntime, nchan, reach, ws.data_ptr(), ws.numel(), stream))
+            launches, tail = _hyst_launches(torch, lib, device, n_win, ntime, nchan, 2, _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_hyst_grow(at(s8), at(t8), at(f8), at(out), b, ntime, nchan, reach, *tail))
     return _like_flags(torch, out, seeds, from_numpy)
 
 
@@ -1158,21 +1134,15 @@ def hysteresis_growth(vis, flags, missing=None, nsigma_time=2.5, nsigma_freq=2.5
     m8 = _flags_u8(torch, missing, device) if missing is not None else None
     nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
     n_win = nbl * ncorr
-    ends, ends_c = _hyst_ends(nchan, freq_chunks)
+    ends, ends_c = _chunk_ends(nchan, freq_chunks)
     out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
     lib = _lib.lib()
     with torch.cuda.device(device):
         if out.numel() > 0:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            batch, nbytes = _hyst_batch(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
-            ws = _workspace(torch, device, nbytes)
-            per = ntime * nchan
-            for w0 in range(0, n_win, batch):
-                b = min(batch, n_win - w0)
-                _lib.check(lib.tri_hysteresis_growth(
-                    v.data_ptr() + w0 * per * v.element_size(), code, f8.data_ptr() + w0 * per,
-                    m8.data_ptr() + w0 * per if m8 is not None else None, out.data_ptr() + w0 * per, b, ntime, nchan,
-                    nsigma_time, nsigma_freq, reach, ends_c, len(ends), ws.data_ptr(), ws.numel(), stream))
+            launches, tail = _hyst_launches(torch, lib, device, n_win, ntime, nchan, len(ends), _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_hysteresis_growth(at(v), code, at(f8), at(m8), at(out), b, ntime, nchan,
+                                                     nsigma_time, nsigma_freq, reach, ends_c, len(ends), *tail))
     return _like_flags(torch, out, flags, from_numpy)
 
 
@@ -1219,19 +1189,23 @@ def _bli_fraction(min_baseline_frac):
     return frac
 
 
+def _acc_pair(torch, device, img, acc):
+    """The accumulator of an integration over baselines: new (sum float64, count int32) tensors of shape `img` on the
+    device -- zeros, or a copy of the pair `acc` to continue from (raises for a pair of another shape or dtype)."""
+    if acc is None:
+        return torch.zeros(img, dtype=torch.float64, device=device), torch.zeros(img, dtype=torch.int32, device=device)
+    total, count = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a for a in acc)
+    if tuple(total.shape) != img or tuple(count.shape) != img:
+        raise ValueError("acc must be a (sum, count) pair of shape %s" % (img,))
+    if total.dtype != torch.float64 or count.dtype != torch.int32:
+        raise TypeError("acc must be a (float64 sum, int32 count) pair")
+    return total.to(device).clone().contiguous(), count.to(device).clone().contiguous()
+
+
 def _bli_accumulate(torch, lib, device, v, f8, code, sel, acc):
     """(sum float64, count int32) of shape (corr, time, chan) on the device: new tensors, continued from `acc`."""
     nbl, img = int(v.shape[0]), tuple(int(s) for s in v.shape[1:])
-    if acc is None:
-        total = torch.zeros(img, dtype=torch.float64, device=device)
-        count = torch.zeros(img, dtype=torch.int32, device=device)
-    else:
-        total, count = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a for a in acc)
-        if tuple(total.shape) != img or tuple(count.shape) != img:
-            raise ValueError("acc must be a (sum, count) pair of shape %s" % (img,))
-        if total.dtype != torch.float64 or count.dtype != torch.int32:
-            raise TypeError("acc must be a (float64 sum, int32 count) pair")
-        total, count = total.to(device).clone().contiguous(), count.to(device).clone().contiguous()
+    total, count = _acc_pair(torch, device, img, acc)
     if total.numel() > 0 and nbl > 0:
         _lib.check(lib.tri_baseline_accumulate(
             v.data_ptr(), code, f8.data_ptr(), sel.data_ptr() if sel is not None else None, nbl, total.numel(),
@@ -1264,9 +1238,7 @@ def baseline_integral(vis, flags, select=None, acc=None):
     torch, v, f8, code, from_numpy, device, sel = _bli_inputs("baseline_integral", vis, flags, select)
     with torch.cuda.device(device):
         total, count = _bli_accumulate(torch, _lib.lib(), device, v, f8, code, sel, acc)
-    if from_numpy:
-        return total.cpu().numpy(), count.cpu().numpy()
-    return total, count
+    return _like_input(from_numpy, total, count)
 
 
 def baseline_mean_amplitude(vis, flags, select=None, min_baseline_frac=0.0):
@@ -1284,9 +1256,7 @@ def baseline_mean_amplitude(vis, flags, select=None, min_baseline_frac=0.0):
         total, count = _bli_accumulate(torch, lib, device, v, f8, code, sel, None)
         amp, flag = _bli_mean(torch, lib, device, total, count, _bli_min_count(frac, nsel))
     flag = flag.view(torch.bool)
-    if from_numpy:
-        return amp.cpu().numpy(), flag.cpu().numpy()
-    return amp, flag
+    return _like_input(from_numpy, amp, flag)
 
 
 def baseline_integrated_flagger(vis, flags, select=None, min_baseline_frac=0.25, **sum_threshold_kwargs):
@@ -1379,13 +1349,7 @@ def _ins_image_shape(shape):
 def _ins_accumulate(torch, lib, device, v, f8, code, sel, acc):
     """(sum float64, count int32) of shape (corr, time - 1, chan) on the device: new tensors, continued from `acc`."""
     nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
-    img = _ins_image_shape(v.shape)
-    if acc is None:
-        total = torch.zeros(img, dtype=torch.float64, device=device)
-        count = torch.zeros(img, dtype=torch.int32, device=device)
-    else:
-        total, count = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a for a in acc)
-        total, count = total.to(device).clone().contiguous(), count.to(device).clone().contiguous()
+    total, count = _acc_pair(torch, device, _ins_image_shape(v.shape), acc)
     if total.numel() > 0 and nbl > 0:
         _lib.check(lib.tri_ins_accumulate(
             v.data_ptr(), code, f8.data_ptr(), sel.data_ptr() if sel is not None else None, nbl, ncorr, ntime, nchan,
@@ -1428,9 +1392,7 @@ def incoherent_noise_spectrum(vis, flags, select=None, acc=None):
     torch, v, f8, code, from_numpy, device, sel = _bli_inputs("incoherent_noise_spectrum", vis, flags, select)
     with torch.cuda.device(device):
         total, count = _ins_accumulate(torch, _lib.lib(), device, v, f8, code, sel, acc)
-    if from_numpy:
-        return total.cpu().numpy(), count.cpu().numpy()
-    return total, count
+    return _like_input(from_numpy, total, count)
 
 
 def _ins_workspace(torch, lib, device, ncorr, ntime, nchan):
@@ -1489,9 +1451,7 @@ def incoherent_noise_zscore(sum, count, min_count, mask=None):
     else:
         level.fill_(float("nan"))
     valid = valid.view(torch.bool)
-    if from_numpy:
-        return level.cpu().numpy(), q.cpu().numpy(), valid.cpu().numpy()
-    return level, q, valid
+    return _like_input(from_numpy, level, q, valid)
 
 
 def _ins_match(torch, lib, device, total, count, min_count, shapes, nsigma_narrow, rounds):

@@ -20,22 +20,14 @@ import numpy as np
 
 from tricolour_amd import packing
 from tricolour_amd.stokes import STOKES_TYPES, stokes_corr_map
+from tricolour_amd.strategies import STEPS, strategy_task
 
 log = logging.getLogger(__name__)
 _tls = threading.local()
 
-VALID_TASKS = ("sum_threshold", "uvcontsub_flagger", "flag_autos", "combine_with_input_flags", "unflag",
-               "flag_nans_zeros", "apply_static_mask",          # strat_executor.py:36-83
-               "scale_invariant_rank_operator",                 # beyond the reference: flagging.scale_invariant_rank_operator
-               "threshold_line_rms",                            # beyond the reference: flagging.threshold_line_rms
-               "mark_missing",                                  # beyond the reference: the missing mask of masked SIR steps
-               "baseline_integrated_sum_threshold",             # beyond the reference: flagging.baseline_integrated_flagger
-               "threshold_local_deviation",                     # beyond the reference: flagging.threshold_local_deviation
-               "threshold_incoherent_noise_spectrum",           # beyond the reference: flagging.threshold_incoherent_noise_spectrum
-               "hysteresis_growth")                             # beyond the reference: flagging.hysteresis_growth
-
+VALID_TASKS = tuple(STEPS)         # the tasks of a strategy chain: one row each in strategies.STEPS
 # steps that need every baseline of the scan at once: they cannot run per baseline chunk
-WHOLE_SCAN_TASKS = ("baseline_integrated_sum_threshold", "threshold_incoherent_noise_spectrum")
+WHOLE_SCAN_TASKS = tuple(t for t in STEPS if STEPS[t].whole_scan)
 
 
 # ---------------------------------------------------------------------------
@@ -105,87 +97,16 @@ def load_strategies(path):
 
 
 def check_strategies(strategies):
-    """Raises the reference's errors for a strategy without a task or with an
-    unknown one (strat_executor.py:33-36, 82-83) before any work is done, and
-    a ``ValueError`` for a ``scale_invariant_rank_operator`` step whose
-    ``missing`` is not ``none`` / ``input`` / ``marked`` or is ``marked`` with
-    no ``mark_missing`` step before it, or for a
-    ``baseline_integrated_sum_threshold`` step whose ``min_baseline_frac`` lies
-    outside [0, 1], or for a ``threshold_local_deviation`` step with a window
-    that is even or outside [3, 31], a scale that is negative or NaN, or
-    ``freq_chunks < 1``, or for a ``threshold_incoherent_noise_spectrum`` step
-    with an unknown kwarg or one out of range
-    (``flagging.check_incoherent_noise_kwargs``, ``bands_hz``,
-    ``exclude_autos``), or for a ``hysteresis_growth`` step with an unknown
-    kwarg, one out of range (``flagging.check_hysteresis_kwargs``) or
-    ``missing: marked`` with no ``mark_missing`` step before it."""
+    """Raises, before any work is done, the reference's errors for a strategy
+    without a task or with an unknown one (strat_executor.py:33-36, 82-83), and
+    the ``ValueError`` of each step's own pre-flight rules: its ``check`` in
+    ``strategies.STEPS``, told whether a ``mark_missing`` step came before it."""
     marked = False
     for strategy in strategies:
-        try:
-            task = strategy['task']
-        except KeyError:
-            raise ValueError("strategy has no 'task': %s" % strategy)
-        if task not in VALID_TASKS:
-            raise ValueError("Task '%s' does not name a valid task", task)
-        if task == "mark_missing":
-            marked = True
-        elif task == "scale_invariant_rank_operator":
-            which = (strategy.get('kwargs') or {}).get("missing", "none")
-            if which not in ("none", "input", "marked"):
-                raise ValueError("scale_invariant_rank_operator: missing must be 'none', 'input' or 'marked', got %r" % (which,))
-            if which == "marked" and not marked:
-                raise ValueError("scale_invariant_rank_operator: missing 'marked' needs an earlier mark_missing")
-        elif task == "baseline_integrated_sum_threshold":
-            frac = (strategy.get('kwargs') or {}).get("min_baseline_frac", 0.25)
-            try:
-                ok = 0.0 <= float(frac) <= 1.0
-            except (TypeError, ValueError):
-                ok = False
-            if not ok:
-                raise ValueError("baseline_integrated_sum_threshold: min_baseline_frac must lie in [0, 1], got %r" % (frac,))
-        elif task == "threshold_local_deviation":
-            from tricolour_amd import flagging
-            kw = strategy.get('kwargs') or {}
-            names = ("window_time", "window_freq", "scale_time", "scale_freq", "freq_chunks")
-            unknown = sorted(set(kw) - set(names))
-            if unknown:
-                raise ValueError("threshold_local_deviation: unknown kwargs %s" % unknown)
-            try:
-                flagging.check_local_deviation_kwargs(**kw)
-            except ValueError as e:
-                raise ValueError("threshold_local_deviation: %s" % e)
-        elif task == "hysteresis_growth":
-            from tricolour_amd import flagging
-            kw = strategy.get('kwargs') or {}
-            names = ("nsigma_time", "nsigma_freq", "reach", "freq_chunks", "missing")
-            unknown = sorted(set(kw) - set(names))
-            if unknown:
-                raise ValueError("hysteresis_growth: unknown kwargs %s" % unknown)
-            try:
-                which = flagging.check_hysteresis_kwargs(**kw)[4]
-            except ValueError as e:
-                raise ValueError("hysteresis_growth: %s" % e)
-            if which == "marked" and not marked:
-                raise ValueError("hysteresis_growth: missing 'marked' needs an earlier mark_missing")
-        elif task == "threshold_incoherent_noise_spectrum":
-            from tricolour_amd import flagging
-            kw = dict(strategy.get('kwargs') or {})
-            names = ("min_baseline_frac", "nsigma", "shapes", "streak", "narrow", "rounds", "exclude_autos", "bands_hz")
-            unknown = sorted(set(kw) - set(names))
-            if unknown:
-                raise ValueError("threshold_incoherent_noise_spectrum: unknown kwargs %s" % unknown)
-            try:
-                autos = kw.pop("exclude_autos", True)
-                if not isinstance(autos, (bool, np.bool_)):
-                    raise ValueError("exclude_autos must be True or False, got %r" % (autos,))
-                bands = kw.pop("bands_hz", None)
-                if bands is not None:
-                    bands = flagging.check_incoherent_noise_bands(bands)
-                checked = flagging.check_incoherent_noise_kwargs(**kw)
-                if len(checked[2]) + (1 if checked[3] else 0) + len(bands or ()) > flagging.INS_MAX_SHAPES:
-                    raise ValueError("at most %d shapes (bands and the streak included)" % flagging.INS_MAX_SHAPES)
-            except ValueError as e:
-                raise ValueError("threshold_incoherent_noise_spectrum: %s" % e)
+        step = STEPS[strategy_task(strategy)]
+        if step.check is not None:
+            step.check(dict(strategy.get('kwargs') or {}), marked)
+        marked = marked or step.marks
 
 
 def _check_whole_scan_tasks(strategies, baseline_chunks):
