@@ -682,6 +682,59 @@ int tri_hysteresis_growth(const void *vis, int vis_dtype, const uint8_t *flags,
                           const int64_t *chunk_ends, int64_t n_chunk_ends,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Quality statistics of the unflagged samples: a measurement beside the
+ * strategy chain, not a strategy step (after AOFlagger's quality statistics;
+ * the definition is this library's own).
+ *
+ * vis (n_bl, n_corr, ntime, nchan) complex64, or float32 amplitudes whose
+ * imaginary part is 0; flags of the same shape, uint8, nonzero = flagged.
+ * A sample is valid iff it is unflagged and both parts are finite; in float64,
+ * with the parts converted exactly, p = re * re + im * im.  A pair (t, c),
+ * 0 <= c < nchan - 1, is valid iff samples (t, c) and (t, c + 1) are:
+ * dre = re[c + 1] - re[c], dim likewise, dp = dre * dre + dim * dim (every
+ * operation rounded on its own, no FMA).  The pair belongs to channel c.
+ *
+ * Six numbers per cell -- n (valid samples), sum_re, sum_im, sum_p, dn (valid
+ * pairs), dsum_p -- for the cells of three groupings:
+ *   bl    (n_bl, n_corr)   over time and chan
+ *   time  (n_corr, ntime)  over bl and chan
+ *   chan  (n_corr, nchan)  over bl and time
+ * With N the grouping's cell count in that order, counts_* is int64 [2][N] =
+ * (n, dn) and sums_* is float64 [4][N] = (sum_re, sum_im, sum_p, dsum_p).
+ * All accumulation is in float64 and int64.
+ *
+ * Order contract.  A window's contribution to each of its cells is reduced in
+ * an order that depends on (ntime, nchan) alone, never on the number of
+ * windows of the call or the window's place in it.  The time and chan cells
+ * add the windows' contributions sequentially in ascending baseline order,
+ * acc = acc + contribution[b], from 0 -- or, with accumulate != 0, from the
+ * values the arrays hold.  So one call over all baselines, one call per
+ * baseline and any split into consecutive baseline ranges continued with
+ * accumulate give the same bits, and so does every run.  bl cells are always
+ * written, never accumulated.  No floating-point atomics; the inputs are never
+ * written.
+ *
+ * Workspace (tri_quality_workspace_bytes; 0 for an empty shape or one beyond
+ * the launch geometry): 40 bytes per (window, strip of 256 channels, time row)
+ * and 48 bytes per (window, channel) and per (window, time row), each array
+ * rounded up to 256 bytes -- 2.7 % of a complex64 window at 1024 x 4096.
+ *
+ * TRI_EINVAL for NULL pointers, negative sizes, a dtype other than complex64
+ * and float32, and outputs that overlap the inputs or each other;
+ * TRI_EWORKSPACE for a missing or short workspace; TRI_EUNSUPPORTED for more
+ * windows, rows or channels than one launch holds (pass fewer baselines per
+ * call).  A shape with a zero extent writes zeros (time and chan cells stay
+ * as they are under accumulate) and returns TRI_OK without a launch.
+ */
+size_t tri_quality_workspace_bytes(int64_t n_bl, int64_t n_corr, int64_t ntime, int64_t nchan);
+int tri_window_quality(const void *vis, int vis_dtype, const uint8_t *flags,
+                       int64_t n_bl, int64_t n_corr, int64_t ntime, int64_t nchan,
+                       int64_t *counts_bl, double *sums_bl,
+                       int64_t *counts_time, double *sums_time,
+                       int64_t *counts_chan, double *sums_chan, int accumulate,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

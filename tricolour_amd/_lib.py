@@ -19,7 +19,8 @@ DEPENDS = [os.path.join(_HERE, "csrc", f) for f in (
     "kernels_boxweight.hpp", "kernels_boxexact.hpp",
     "kernels_sumthreshold.hpp", "kernels_scan.hpp", "kernels_sir.hpp", "kernels_linerms.hpp",
     os.path.join("steps", "kernels_blint.hpp"), os.path.join("steps", "ldev", "kernels_ldev.hpp"),
-    os.path.join("steps", "ins", "kernels_ins.hpp"), os.path.join("steps", "hyst", "kernels_hyst.hpp"))]
+    os.path.join("steps", "ins", "kernels_ins.hpp"), os.path.join("steps", "hyst", "kernels_hyst.hpp"),
+    os.path.join("steps", "quality", "kernels_quality.hpp"))]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tricolour_amd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
@@ -208,6 +209,10 @@ _SIGNATURES = {
     "tri_hysteresis_growth": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                         C.c_int64, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tri_quality_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "tri_window_quality": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "tri_last_error": (C.c_char_p, []),
     "tri_version": (C.c_int, []),
     "tri_bench_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -189,7 +189,8 @@ def _check_baseline_chunks(baseline_chunks):
 
 def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, strategies, *, model=None,
               flagging_strategy="standard", corr_type=None, ignore_flags=False, antenna_positions=None,
-              masked_channels=(), antenna_names=None, scan_no=0, field_name="", ddid=0, baseline_chunks=None):
+              masked_channels=(), antenna_names=None, scan_no=0, field_name="", ddid=0, baseline_chunks=None,
+              quality=None):
     """Flags one (field, ddid, scan) dataset as the tricolour application does
     (app.py:370-486).
 
@@ -213,12 +214,18 @@ def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, stra
     flags and tallies.  Then only one chunk's rows, windows and row flags
     (and the next chunk's rows, in flight) are held on the device besides
     the caller's own device tensors, and host ``data`` (numpy or a CPU
-    tensor) gives a numpy result."""
+    tensor) gives a numpy result.
+
+    ``quality``: None, or a :class:`tricolour_amd.quality.ScanQuality` that is
+    filled in place with the quality statistics of the packed windows (in the
+    Stokes modes the residual or Stokes windows the strategies see) under the
+    flags before and after the chain -- the same bits whole and streamed."""
     import torch
     from tricolour_amd.strategies import apply_strategies
     from tricolour_amd.window_statistics import window_stats_block
 
     baseline_chunks = _check_baseline_chunks(baseline_chunks)
+    _check_quality(quality)
     if flagging_strategy not in packing.SCAN_MODES:
         raise ValueError("Invalid flagging strategy '%s'" % flagging_strategy)
     strategies = list(strategies)
@@ -275,18 +282,44 @@ def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, stra
             data, None if ignore_flags else flags, model, a1, a2, time_inv, ntime, ubl, baseline_chunks,
             flagging_strategy, terms, strategies,
             dict(ant_pos=ant_pos, chan_freq=chan_freq, chan_width=chan_width, masked_channels=list(masked_channels)),
-            (chan_freq, antenna_names, scan_no, field_name, ddid))
+            (chan_freq, antenna_names, scan_no, field_name, ddid), _quality_begin(quality, ubl, chan_freq, utime))
     vis_w, flag_w = packing.pack_scan(time_inv, ubl, a1, a2, data, None if ignore_flags else flags, ntime,
                                       model=model, flagging_strategy=flagging_strategy, stokes_terms=terms)
     original = window_stats_block(flag_w, ubl, chan_freq, antenna_names, scan_no, field_name, ddid)
+    quality = _quality_begin(quality, ubl, chan_freq, utime)
+    _quality_add(quality, "original", vis_w, flag_w)
     flag_w = apply_strategies(strategies, flag_w, vis_w, ubl=ubl,
                               ant_pos=None if antenna_positions is None else _host(antenna_positions),
                               chan_freq=chan_freq, chan_width=chan_width, masked_channels=list(masked_channels))
     final = window_stats_block(flag_w, ubl, chan_freq, antenna_names, scan_no, field_name, ddid)
+    _quality_add(quality, "final", vis_w, flag_w)
     row_flags = packing.unpack_scan(a1, a2, time_inv, ubl, flag_w, ncorr)     # :475-480
     if from_numpy:
         row_flags = row_flags.cpu().numpy()
     return row_flags, original, final
+
+
+def _check_quality(quality):
+    if quality is None:
+        return
+    from tricolour_amd.quality import ScanQuality
+    if not isinstance(quality, ScanQuality):
+        raise ValueError("quality must be None or a tricolour_amd.quality.ScanQuality, got %r" % (type(quality).__name__,))
+
+
+def _quality_begin(quality, ubl, chan_freq, utime):
+    """An emptied ``quality`` that knows its scan (None stays None)."""
+    if quality is not None:
+        quality.original = quality.final = None
+        quality.ubl, quality.chan_freq, quality.times = ubl, chan_freq, utime
+    return quality
+
+
+def _quality_add(quality, which, vis_w, flag_w):
+    """The statistics of these windows, the scan's next baselines, onto ``quality.original`` or ``quality.final``."""
+    if quality is not None:
+        from tricolour_amd.quality import window_quality
+        setattr(quality, which, window_quality(vis_w, flag_w, accumulate_into=getattr(quality, which)))
 
 
 def last_stream_stats():
@@ -312,7 +345,7 @@ def _host_rows(torch, a, dtype):
 
 
 def _flag_scan_streamed(data, flags, model, a1, a2, time_inv, ntime, ubl, baseline_chunks, flagging_strategy, terms,
-                        strategies, strategy_args, stats_args):
+                        strategies, strategy_args, stats_args, quality=None):
     """:func:`flag_scan` one baseline chunk at a time.  For each chunk of
     :func:`~tricolour_amd.packing.scan_chunks`: its rows onto the device
     (device inputs: read in place through ``src_row``; host inputs: the
@@ -320,7 +353,8 @@ def _flag_scan_streamed(data, flags, model, a1, a2, time_inv, ntime, ubl, baseli
     worker thread while the previous chunk is flagged), ``tri_fill_windows``
     + ``tri_pack_scan_rows``, the window statistics, the strategies on
     ``ubl[b0:b1]``, the statistics again and ``tri_unpack_scan_rows``.  The
-    chunks' tallies are summed in baseline order."""
+    chunks' tallies are summed in baseline order, and so are the quality
+    statistics if ``quality`` is given."""
     import contextlib
     from concurrent.futures import ThreadPoolExecutor
 
@@ -424,8 +458,10 @@ def _flag_scan_streamed(data, flags, model, a1, a2, time_inv, ntime, ubl, baseli
                 flag_w = flag_w.view(torch.bool)
                 ubl_c = ubl[c.b0:c.b1]
                 originals.append(window_stats_block(flag_w, ubl_c, *stats_args))
+                _quality_add(quality, "original", vis_w, flag_w)
                 flag_w = apply_strategies(strategies, flag_w, vis_w, ubl=ubl_c, **strategy_args)
                 finals.append(window_stats_block(flag_w, ubl_c, *stats_args))
+                _quality_add(quality, "final", vis_w, flag_w)
                 del vis_w
                 fw8 = flag_w.view(torch.uint8) if flag_w.dtype == torch.bool else (flag_w != 0).view(torch.uint8)
                 ub, ut = idx(c.bl, np.int32), idx(c.time, np.int32)
@@ -478,7 +514,7 @@ def _chunk_to_host(torch, flagging, link, main, out, rows, result, times):
 # ---------------------------------------------------------------------------
 def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fieldnames=None, ms_name="",
                flagging_strategy="standard", ignore_flags=False, antenna_positions=None, masked_channels=(),
-               antenna_names=None, baseline_chunks=None):
+               antenna_names=None, baseline_chunks=None, quality=None):
     """The dataset loop of the application (app.py:327-486) over datasets
     already loaded, one dict per (field, ddid, scan) with the keys
     ``DATA``, ``FLAG``, ``ANTENNA1``, ``ANTENNA2``, ``TIME``, ``FIELD_ID``,
@@ -489,7 +525,10 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
     Returns ``(row_flags, summary)``: a list with the row flags of each
     dataset (None for datasets the field / scan selection skips) and the
     lines of ``summarise_stats`` over all flagged datasets (an empty list if
-    none was flagged).  ``baseline_chunks``: as for :func:`flag_scan`."""
+    none was flagged).  ``baseline_chunks``: as for :func:`flag_scan`.
+    ``quality``: None, or a list to which one
+    :class:`tricolour_amd.quality.ScanQuality` per flagged dataset is
+    appended."""
     from tricolour_amd.window_statistics import summarise_stats
 
     baseline_chunks = _check_baseline_chunks(baseline_chunks)
@@ -497,6 +536,8 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
     strategies = list(strategies)
     check_strategies(strategies)
     _check_whole_scan_tasks(strategies, baseline_chunks)
+    if quality is not None and not isinstance(quality, list):
+        raise ValueError("quality must be None or a list, got %r" % (type(quality).__name__,))
     if fieldnames is None:
         nfield = max([int(ds["FIELD_ID"]) for ds in datasets], default=-1) + 1
         fieldnames = [str(i) for i in range(nfield)]
@@ -513,12 +554,19 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
             out.append(None)
             continue
         log.info("Flagging field '{0:s}' scan {1:d}".format(field_dict[field_id], scan_no))
+        one = None
+        if quality is not None:
+            from tricolour_amd.quality import ScanQuality
+            one = ScanQuality()
         row_flags, original, final = flag_scan(
             ds["DATA"], ds.get("FLAG"), ds["ANTENNA1"], ds["ANTENNA2"], ds["TIME"], ds["CHAN_FREQ"],
             ds["CHAN_WIDTH"], strategies, model=ds.get("MODEL"), flagging_strategy=flagging_strategy,
             corr_type=ds.get("CORR_TYPE"), ignore_flags=ignore_flags, antenna_positions=antenna_positions,
             masked_channels=masked_channels, antenna_names=antenna_names, scan_no=scan_no,
-            field_name=field_dict[field_id], ddid=int(ds["DATA_DESC_ID"]), baseline_chunks=baseline_chunks)
+            field_name=field_dict[field_id], ddid=int(ds["DATA_DESC_ID"]), baseline_chunks=baseline_chunks,
+            quality=one)
+        if one is not None:
+            quality.append(one)
         out.append(row_flags)
         original_stats.append(original)
         final_stats.append(final)
