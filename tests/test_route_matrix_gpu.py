@@ -6,6 +6,12 @@ intermediates of window 0 must equal the oracle's bit for bit, and the kernel lo
 log of the row's base setting exactly as the row says (`gone`, `new`, `present`).  One child with nothing set gives
 the default logs.  The union of all logs must contain every kernel KERNELS marks `flagger`.
 
+After each case the same child flags it again through the C ABI with poisoned scratch (tests/scratch_poison.py): a workspace
+of exactly tri_workspace_bytes() between guard bands that holds zeros, then the leavings of a call on other inputs, then
+0xFF, and a pre-filled, guarded output; the default child also flags the two-window cases in a workspace for one window,
+the second batch in the leavings of the first.  The flags must be those of the first call, no guard byte may change and
+the kernels must be the same (test_no_leg_depends_on_scratch_contents).
+
 The cases are derived from the conditions of the route picks (pick_iteration, pick_bg_step, pick_freq_stage) and of the
 launch functions in tricolour_amd.hip (radii: box_radius(sigma) = floor(sqrt(3 sigma^2 + 1) / 2); W windows, T times,
 F channels, G chunks):
@@ -53,6 +59,7 @@ import sys
 import numpy as np
 import pytest
 
+import scratch_poison
 from test_route_ledger import KERNELS, SWITCHES, base_name, is_flagger, launches
 from test_final_pass_routes_gpu import TAP_F32, TAP_U8, same_f32
 
@@ -88,12 +95,13 @@ def box_radius(sigma):
     return int(0.5 * np.sqrt(12.0 * sigma * sigma / 4.0 + 1.0))
 
 
-def make_inputs(name):
+def make_inputs(name, other=False):
     """Noise with bad channels, bad times, a raised patch, outliers and NaN samples; pre-flagged channels and a
-    pre-flagged stretch of times (as test_final_pass_routes_gpu.make_inputs)."""
+    pre-flagged stretch of times (as test_final_pass_routes_gpu.make_inputs).  `other`: another seed and the pre-flags
+    inverted -- what a workspace is left stale by before a poisoned run."""
     shape, _, recipe = CASES[name]
     nbl, ncorr, T, F = shape
-    rng = np.random.default_rng(sorted(CASES).index(name) + 97)
+    rng = np.random.default_rng(sorted(CASES).index(name) + (1097 if other else 97))
     vis = np.empty(shape, np.complex64)
     vis.real = rng.standard_normal(shape, dtype=np.float32)
     vis.imag = rng.standard_normal(shape, dtype=np.float32)
@@ -112,7 +120,7 @@ def make_inputs(name):
         # and a run that starts the line (extrapolation, window 1)
         flags[0, 0, :, 470:560] = True
         flags[0, ncorr - 1, :, 0:45] = True
-    return vis, flags
+    return vis, (~flags if other else flags)
 
 
 def run_case(name):
@@ -134,9 +142,71 @@ def run_case(name):
     return out.cpu().numpy(), dbg, log, np.array(list(stats), np.int64)
 
 
+TWO_BATCHES = "stale, two batches"      # the default child's extra run: a workspace for one window under two
+
+
+def is_default_child():
+    """Whether this process runs with no switch of the ledger set."""
+    return not any(name in os.environ for name in SWITCHES)
+
+
+def poisoned_flagger_call(name, inputs, ws, log=False):
+    """tri_sum_threshold_flagger through the C ABI on the current stream: `inputs` (vis, flags) of case `name`, the
+    workspace `ws` (a guarded interior) exactly as it is, the flags into a guarded, pre-filled output.  Returns the
+    Output and the kernel log."""
+    import ctypes as C
+    import torch
+    from tricolour_amd import _lib, flagging
+    nbl, ncorr, T, F = CASES[name][0]
+    p = flagging.prepare_params(T, F, **case_kwargs(name))
+    v = torch.from_numpy(inputs[0]).cuda()
+    f = torch.from_numpy(inputs[1]).cuda().view(torch.uint8)
+    out = scratch_poison.Output((nbl, ncorr, T, F), torch.uint8, "cuda")
+    if log:
+        _lib.kernel_log_begin()
+    try:
+        _lib.check(_lib.lib().tri_sum_threshold_flagger(v.data_ptr(), _lib.TRI_VIS_C64, f.data_ptr(), out.ptr, nbl * ncorr, T, F, C.byref(p),
+                                                        ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+    finally:
+        names = _lib.kernel_log_end() if log else {}
+    return out, names
+
+
+def poison_case(name, want, default_child):
+    """The poisoned runs of one case: per pattern the flags, the damaged guard bytes of workspace and output and the
+    kernel log, until the first pattern whose flags are not `want` (run_case's) or that damages a guard."""
+    import ctypes as C
+    from tricolour_amd import _lib, flagging
+    nbl, ncorr, T, F = CASES[name][0]
+    n_cp = nbl * ncorr
+    p = flagging.prepare_params(T, F, **case_kwargs(name))
+    size = {pattern: _lib.lib().tri_workspace_bytes(n_cp, T, F, C.byref(p)) for pattern in scratch_poison.PATTERNS}
+    if default_child and n_cp == 2:
+        size[TWO_BATCHES] = _lib.lib().tri_workspace_bytes(1, T, F, C.byref(p))
+    assert all(n > 0 for n in size.values()), size
+    mine, other = make_inputs(name), make_inputs(name, other=True)
+
+    def run(pattern):
+        ws, whole = scratch_poison.guarded(size[pattern], scratch_poison.FILL.get(pattern, 0x00), "cuda")
+        if pattern in ("stale", TWO_BATCHES):
+            poisoned_flagger_call(name, other, ws)
+        out, log = poisoned_flagger_call(name, mine, ws, log=True)
+        return dict(flags=out.host(), ws_damage=scratch_poison.guards_intact(whole, size[pattern]), out_damage=out.damaged(), log=log)
+
+    def differs(pattern, got):
+        if got["ws_damage"] or got["out_damage"]:
+            return "guard bytes damaged"
+        return "" if np.array_equal(got["flags"], want.view(np.uint8)) else "flags differ"
+
+    return scratch_poison.first_difference(run, differs, list(size))[0]
+
+
 def child_main(path, names):
-    """Runs in the child process: the cases `names` under the environment it was started with."""
+    """Runs in the child process: the cases `names` under the environment it was started with, and after each case its
+    poisoned runs."""
     saved = {}
+    default_child = is_default_child()
     for name in names:
         out, dbg, log, stats = run_case(name)
         saved[name + "/out"] = out
@@ -145,6 +215,13 @@ def child_main(path, names):
         saved[name + "/log_counts"] = np.array(list(log.values()), np.int64)
         for k in TAP_F32 + TAP_U8:
             saved[name + "/" + k] = np.asarray(dbg[k])
+        poisoned = poison_case(name, out, default_child)
+        saved[name + "/poison_patterns"] = np.array(list(poisoned))
+        for i, got in enumerate(poisoned.values()):
+            saved[name + "/poison%d_flags" % i] = got["flags"]
+            saved[name + "/poison%d_damage" % i] = np.array([got["ws_damage"], got["out_damage"]], np.int64)
+            saved[name + "/poison%d_log_names" % i] = np.array(list(got["log"].keys()))
+            saved[name + "/poison%d_log_counts" % i] = np.array(list(got["log"].values()), np.int64)
     np.savez(path, **saved)
     print("CHILD DONE")
 
@@ -200,6 +277,10 @@ class Children:
             res[name] = dict(out=d[name + "/out"], stats=d[name + "/stats"],
                              log=dict(zip(d[name + "/log_names"].tolist(), d[name + "/log_counts"].tolist())),
                              **{k: d[name + "/" + k] for k in TAP_F32 + TAP_U8})
+            res[name]["poison"] = {
+                pattern: dict(flags=d[name + "/poison%d_flags" % i], damage=d[name + "/poison%d_damage" % i].tolist(),
+                              log=dict(zip(d[name + "/poison%d_log_names" % i].tolist(), d[name + "/poison%d_log_counts" % i].tolist())))
+                for i, pattern in enumerate(d[name + "/poison_patterns"].tolist())}
         self.done[key] = res
         return res
 
@@ -386,6 +467,61 @@ def test_unaligned_default_equals_the_switched_aligned_twin(children, case, env,
     diff = [f for f in frags if runs(mine, f) != runs(twin, f)]
     assert any(runs(mine, f) for f in frags) and not all(runs(mine, f) for f in frags), frags
     assert not diff, "%s\n%s by default:\n%s\nblocks with %s:\n%s" % (diff, case, show(mine), env_key(env), show(twin))
+
+
+# every environment some test of this module starts a child for
+ENVIRONMENTS = {}
+for _env in ([{}] + [e for _name, _i in MATRIX for e in (SWITCHES[_name]["legs"][_i]["env"], SWITCHES[_name]["legs"][_i]["base"])]
+             + [{"TRI_MEDREJ_FORCE_FALLBACK": "1"}] + [t[1] for t in TWINS]):
+    ENVIRONMENTS.setdefault(env_key(_env), _env)
+
+# Kernels that only the debug tap of run_case launches (iter_taps): the direct, poisoned call has no tap, so these and
+# no others may be missing from its log.
+TAP_ONLY = ("k_gather_col_f32", "k_gather_col_u8", "k_unpanel<float>", "k_unpanel<unsigned char>")
+
+# The default child's two-batch run hands the kernels one window at a time, and one pick looks at the number of windows
+# in a launch: the spectrum stage pipeline wants an even count (k_boxp_spec, else k_boxt_spec; see the module's
+# docstring).  These, by base name, and no others may leave or join the log of a batch of one.
+BATCH_OF_ONE = ("k_boxp_spec", "k_boxt_spec")
+
+
+@pytest.mark.parametrize("key", list(ENVIRONMENTS))
+def test_no_leg_depends_on_scratch_contents(gpu, children, key):
+    """Every case of the environment, poisoned: a workspace of exactly tri_workspace_bytes() between guard bands, holding
+    zeros, the leavings of a call on other inputs, and 0xFF; the output pre-filled.  The flags equal those of run_case
+    (held to the oracle by the tests above), no guard byte is touched, and the kernels are run_case's but for the tap's."""
+    got_all = children.get(ENVIRONMENTS[key])
+    default_child = not ENVIRONMENTS[key]
+    report = []
+    for case, got in got_all.items():
+        want = list(scratch_poison.PATTERNS) + ([TWO_BATCHES] if default_child and np.prod(CASES[case][0][:2]) == 2 else [])
+        ran, before = list(got["poison"]), len(report)
+        print("%s / %s: %s" % (key, case, "; ".join(
+            "%s: %d flags differ, %d + %d guard bytes damaged" % (p, int((r["flags"] != got["out"]).sum()), r["damage"][0], r["damage"][1])
+            for p, r in got["poison"].items())))
+        for pattern, res in got["poison"].items():
+            here = []
+            bad = int((res["flags"] != got["out"].view(np.uint8)).sum())
+            if bad:
+                here.append("%d of %d flags differ from the unpoisoned call's" % (bad, got["out"].size))
+            if not scratch_poison.only_0_and_1(res["flags"]):
+                here.append("flag bytes other than 0 and 1")
+            if res["damage"][0]:
+                here.append("%d guard bytes around the workspace were written" % res["damage"][0])
+            if res["damage"][1]:
+                here.append("%d guard bytes around the output were written" % res["damage"][1])
+            gone, new = sorted(set(got["log"]) - set(res["log"])), sorted(set(res["log"]) - set(got["log"]))
+            if pattern == TWO_BATCHES:
+                gone = [k for k in gone if base_name(k) not in BATCH_OF_ONE]
+                new = [k for k in new if base_name(k) not in BATCH_OF_ONE]
+            gone = [k for k in gone if k not in TAP_ONLY]
+            if gone or new:
+                here.append("kernels of the tapped call that are missing: %s; kernels it did not launch: %s" % (gone, new))
+            if here:
+                report.append("%s on case %s, pattern %s:\n  %s" % (key, case, pattern, "\n  ".join(here)))
+        if ran != want[:len(ran)] or (len(ran) < len(want) and len(report) == before):
+            report.append("%s on case %s: patterns run %s, expected %s" % (key, case, ran, want))
+    assert not report, "\n".join(report)
 
 
 def test_every_flagger_kernel_met_the_oracle(children, expected):
