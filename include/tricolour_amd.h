@@ -30,6 +30,7 @@ extern "C" {
 #endif
 
 #define TRI_MAX_WINDOWS 16
+#define TRI_MAX_HIST_BINS 2048   /* bins of an amplitude histogram (tri_amplitude_histogram) */
 
 enum tri_status {
     TRI_OK = 0,
@@ -734,6 +735,59 @@ int tri_window_quality(const void *vis, int vis_dtype, const uint8_t *flags,
                        int64_t *counts_time, double *sums_time,
                        int64_t *counts_chan, double *sums_chan, int accumulate,
                        void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Log-binned amplitude histograms of the kept and of the flagged samples: a
+ * measurement beside the strategy chain, not a strategy step (after the
+ * "log N - log S" histogram AOFlagger keeps beside its quality statistics; the
+ * definition is this library's own).
+ *
+ * vis (n_bl, n_corr, ntime, nchan) complex64, or float32 amplitudes; flags of
+ * the same shape, uint8, nonzero = flagged.  Every sample is counted exactly
+ * once, in one population (0 = kept: its flag is 0; 1 = flagged) and one slot.
+ *
+ * Bins are three integers: emin and emax, -126 <= emin < emax <= 128, and
+ * sub_bits, 0 <= sub_bits <= 5; nb = (emax - emin) << sub_bits bins, at most
+ * TRI_MAX_HIST_BINS.  There are nb + 3 slots (tri_histogram_slots; 0 for bins
+ * that are not allowed): 0 underflow (zero included), 1 .. nb the bins, nb + 1
+ * overflow, nb + 2 non-finite.  The slot of a sample:
+ *   1. either part NaN or +-Inf (a float32 input has one part): nb + 2;
+ *   2. otherwise a = (float)sqrt((double)re * re + (double)im * im) for
+ *      complex64, |x| for float32;
+ *   3. u = the bit pattern of a, and
+ *      k = (u >> (23 - sub_bits)) - ((emin + 127) << sub_bits);
+ *   4. k < 0: slot 0; k >= nb: slot nb + 1 (finite parts whose amplitude
+ *      rounds to +Inf land here); otherwise slot k + 1.
+ * No logarithm and no floating-point comparison.  With s = sub_bits, bin k
+ * covers [2^(emin + (k >> s)) * (1 + (k mod 2^s) / 2^s), next edge).
+ *
+ * Two groupings, filled in the same pass:
+ *   hist_bl     (n_bl, n_corr, 2, nb + 3) int64: one cell per window;
+ *   hist_chunk  (n_corr, n_chunk_ends - 1, 2, nb + 3) int64: over baselines and
+ *               times, per frequency chunk [chunk_ends[g], chunk_ends[g + 1]).
+ * chunk_ends is a host array that runs from 0 to nchan and never decreases; a
+ * repeated end is an empty chunk whose cells get nothing.  hist_bl is always
+ * written fresh (zeroed on `stream` first); hist_chunk is zeroed first when
+ * accumulate is 0 and continued from its contents otherwise.  Counts are
+ * integers added with integer atomics: the same bits for every order, every
+ * split into baseline ranges continued with accumulate, and every run.  No
+ * workspace; both outputs are the caller's; the inputs are never written.
+ *
+ * TRI_EINVAL for NULL pointers, negative sizes, a dtype other than complex64
+ * and float32, bins that are not allowed, chunk ends that do not run from 0 to
+ * nchan in non-decreasing order, and outputs that overlap an input or each
+ * other.  TRI_EUNSUPPORTED beyond the launch geometry: an extent above
+ * 2^31 - 1, more than 2^24 - 1 (window, band of 64 time rows) pairs in one
+ * call (pass fewer baselines per call), a chunk wider than 65535 * 1024
+ * channels, more than 2^30 chunk ends.  A shape with a zero extent zeroes what
+ * it would have zeroed and returns TRI_OK without a launch.
+ */
+int64_t tri_histogram_slots(int emin, int emax, int sub_bits);
+int tri_amplitude_histogram(const void *vis, int vis_dtype, const uint8_t *flags,
+                            int64_t n_bl, int64_t n_corr, int64_t ntime, int64_t nchan,
+                            const int64_t *chunk_ends, int64_t n_chunk_ends,
+                            int emin, int emax, int sub_bits,
+                            int64_t *hist_bl, int64_t *hist_chunk, int accumulate, void *stream);
 
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);

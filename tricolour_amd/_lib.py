@@ -20,7 +20,7 @@ DEPENDS = [os.path.join(_HERE, "csrc", f) for f in (
     "kernels_sumthreshold.hpp", "kernels_scan.hpp", "kernels_sir.hpp", "kernels_linerms.hpp",
     os.path.join("steps", "kernels_blint.hpp"), os.path.join("steps", "ldev", "kernels_ldev.hpp"),
     os.path.join("steps", "ins", "kernels_ins.hpp"), os.path.join("steps", "hyst", "kernels_hyst.hpp"),
-    os.path.join("steps", "quality", "kernels_quality.hpp"))]
+    os.path.join("steps", "quality", "kernels_quality.hpp"), os.path.join("steps", "hist", "kernels_hist.hpp"))]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tricolour_amd.h")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
@@ -36,6 +36,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
 TRI_OK, TRI_EINVAL, TRI_EUNSUPPORTED, TRI_EWORKSPACE, TRI_EHIP = range(5)
 TRI_VIS_C64, TRI_VIS_F32, TRI_VIS_C128, TRI_VIS_F64 = 0, 1, 2, 3
 TRI_MAX_WINDOWS = 16
+TRI_MAX_HIST_BINS = 2048
 
 
 class TriParams(C.Structure):
@@ -213,6 +214,10 @@ _SIGNATURES = {
     "tri_window_quality": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tri_histogram_slots": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "tri_amplitude_histogram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                          C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p]),
     "tri_last_error": (C.c_char_p, []),
     "tri_version": (C.c_int, []),
     "tri_bench_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -219,7 +219,10 @@ def flag_scan(data, flags, antenna1, antenna2, time, chan_freq, chan_width, stra
     ``quality``: None, or a :class:`tricolour_amd.quality.ScanQuality` that is
     filled in place with the quality statistics of the packed windows (in the
     Stokes modes the residual or Stokes windows the strategies see) under the
-    flags before and after the chain -- the same bits whole and streamed."""
+    flags before and after the chain -- the same bits whole and streamed.
+    ``ScanQuality(histograms=AmplitudeBins(...))`` takes the amplitude
+    histograms of the kept and the flagged samples of the same windows as well
+    (``original_histograms``, ``final_histograms``)."""
     import torch
     from tricolour_amd.strategies import apply_strategies
     from tricolour_amd.window_statistics import window_stats_block
@@ -311,15 +314,21 @@ def _quality_begin(quality, ubl, chan_freq, utime):
     """An emptied ``quality`` that knows its scan (None stays None)."""
     if quality is not None:
         quality.original = quality.final = None
+        quality.original_histograms = quality.final_histograms = None
         quality.ubl, quality.chan_freq, quality.times = ubl, chan_freq, utime
     return quality
 
 
 def _quality_add(quality, which, vis_w, flag_w):
-    """The statistics of these windows, the scan's next baselines, onto ``quality.original`` or ``quality.final``."""
+    """The statistics of these windows, the scan's next baselines, onto ``quality.original`` or ``quality.final`` --
+    and, if ``quality.histograms`` names bins, their amplitude histograms onto ``quality.<which>_histograms``."""
     if quality is not None:
-        from tricolour_amd.quality import window_quality
+        from tricolour_amd.quality import window_histograms, window_quality
         setattr(quality, which, window_quality(vis_w, flag_w, accumulate_into=getattr(quality, which)))
+        if quality.histograms is not None:
+            name = which + "_histograms"
+            setattr(quality, name, window_histograms(vis_w, flag_w, quality.histograms, quality.freq_chunks,
+                                                     accumulate_into=getattr(quality, name)))
 
 
 def last_stream_stats():
@@ -514,7 +523,7 @@ def _chunk_to_host(torch, flagging, link, main, out, rows, result, times):
 # ---------------------------------------------------------------------------
 def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fieldnames=None, ms_name="",
                flagging_strategy="standard", ignore_flags=False, antenna_positions=None, masked_channels=(),
-               antenna_names=None, baseline_chunks=None, quality=None):
+               antenna_names=None, baseline_chunks=None, quality=None, histograms=None):
     """The dataset loop of the application (app.py:327-486) over datasets
     already loaded, one dict per (field, ddid, scan) with the keys
     ``DATA``, ``FLAG``, ``ANTENNA1``, ``ANTENNA2``, ``TIME``, ``FIELD_ID``,
@@ -528,7 +537,9 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
     none was flagged).  ``baseline_chunks``: as for :func:`flag_scan`.
     ``quality``: None, or a list to which one
     :class:`tricolour_amd.quality.ScanQuality` per flagged dataset is
-    appended."""
+    appended; ``histograms``: None, or the
+    :class:`tricolour_amd.quality.AmplitudeBins` each of them is created with
+    (it needs the ``quality`` list)."""
     from tricolour_amd.window_statistics import summarise_stats
 
     baseline_chunks = _check_baseline_chunks(baseline_chunks)
@@ -538,6 +549,11 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
     _check_whole_scan_tasks(strategies, baseline_chunks)
     if quality is not None and not isinstance(quality, list):
         raise ValueError("quality must be None or a list, got %r" % (type(quality).__name__,))
+    if histograms is not None:
+        from tricolour_amd.quality import ScanQuality
+        if quality is None:
+            raise ValueError("histograms needs a quality list to append to")
+        ScanQuality(histograms=histograms)              # raises ValueError for anything but bins
     if fieldnames is None:
         nfield = max([int(ds["FIELD_ID"]) for ds in datasets], default=-1) + 1
         fieldnames = [str(i) for i in range(nfield)]
@@ -557,7 +573,7 @@ def flag_scans(datasets, strategies, scan_numbers=None, field_names=None, *, fie
         one = None
         if quality is not None:
             from tricolour_amd.quality import ScanQuality
-            one = ScanQuality()
+            one = ScanQuality(histograms=histograms)
         row_flags, original, final = flag_scan(
             ds["DATA"], ds.get("FLAG"), ds["ANTENNA1"], ds["ANTENNA2"], ds["TIME"], ds["CHAN_FREQ"],
             ds["CHAN_WIDTH"], strategies, model=ds.get("MODEL"), flagging_strategy=flagging_strategy,
