@@ -97,6 +97,47 @@ def test_no_silent_cpu_fallback():
         tricolour_amd.sum_threshold_flagger(vis, np.zeros(vis.shape, bool))
 
 
+def _reached(path, seen):
+    """Depth first: every file the quoted include lines below `path` name, each beside the file that names it."""
+    with open(path, encoding="utf-8") as fh:
+        lines = [ln.split('"') for ln in fh if ln.lstrip().startswith("#") and "include" in ln and '"' in ln]
+    for parts in lines:
+        dep = os.path.normpath(os.path.join(os.path.dirname(path), parts[1]))
+        if dep not in seen:
+            seen.add(dep)
+            _reached(dep, seen)
+    return seen
+
+
+def test_depends_is_the_include_closure_of_the_sources(tmp_path):
+    """_lib.DEPENDS (what a rebuild and source_hash() look at) is derived: every file the translation unit includes, the
+    C header apart, and no file under csrc/ that nothing includes."""
+    import shutil
+    from tricolour_amd import _lib
+    csrc = os.path.join(ROOT, "tricolour_amd", "csrc")
+    assert _lib.SOURCES == [os.path.join(csrc, "tricolour_amd.hip")] and _lib.HEADER not in _lib.DEPENDS
+    reached = set()
+    for src in _lib.SOURCES:
+        _reached(src, reached)
+    assert _lib.HEADER in reached
+    assert len(_lib.DEPENDS) == len(set(_lib.DEPENDS)) and set(_lib.DEPENDS) == reached - {_lib.HEADER}
+    assert os.path.join(csrc, "steps", "step_host.hpp") in _lib.DEPENDS and os.path.join(csrc, "tri_common.hpp") in _lib.DEPENDS
+    on_disk = {os.path.join(d, f) for d, _dirs, files in os.walk(csrc) for f in files}
+    assert on_disk == set(_lib.SOURCES + _lib.DEPENDS), sorted(on_disk ^ set(_lib.SOURCES + _lib.DEPENDS))
+    # a header more, named from a step host file of a copy of the tree, is one dependency more
+    copy = tmp_path / "tricolour_amd" / "csrc"
+    shutil.copytree(csrc, str(copy))
+    shutil.copytree(os.path.join(ROOT, "include"), str(tmp_path / "include"))
+    hip, header = str(copy / "tricolour_amd.hip"), str(tmp_path / "include" / "tricolour_amd.h")
+    before = _lib.include_closure([hip], header)
+    assert [os.path.relpath(p, str(copy)) for p in before] == [os.path.relpath(p, csrc) for p in _lib.DEPENDS]
+    (copy / "steps" / "ins" / "added.hpp").write_text("#pragma once\n", encoding="utf-8")
+    host = copy / "steps" / "ins" / "ins_host.hpp"
+    host.write_text('#include "added.hpp"\n' + host.read_text(encoding="utf-8"), encoding="utf-8")
+    after = _lib.include_closure([hip], header)
+    assert set(after) - set(before) == {str(copy / "steps" / "ins" / "added.hpp")} and set(before) <= set(after)
+
+
 def test_product_never_imports_the_oracle():
     """The oracle is test infrastructure: nothing under tricolour_amd/ or the
     HIP sources may reference it."""

@@ -563,7 +563,7 @@ def test_kernel_table_lists_what_the_sources_hold():
     from test_route_ledger import scan_instances, scan_kernels
     assert scan_hyst_kernels() == set(KERNELS)
     assert not set(KERNELS) & scan_kernels()                   # the ledger keeps the kernels directly under csrc/
-    sites = scan_instances()                                   # launch sites of tricolour_amd.hip, macros expanded
+    sites = scan_instances()                                   # launch sites of the host code, macros expanded
     for kernel, instances in KERNELS.items():
         assert sites.get(kernel) == instances, kernel
     with open(os.path.join(ROOT, "tricolour_amd", "csrc", "tricolour_amd.hip"), encoding="utf-8") as fh:

@@ -21,7 +21,8 @@ with '<' it is a prefix of the instantiation ("k_median2<true, false, 16>").
 Row of KERNELS
     "flagger" / "unlaunched" / "file.py::test"   as above and below
     dict(test="file.py::test", instances=[...])  the pack / unpack, scan and strategy-step kernels of the other entry
-             points: `instances` lists every instantiation a launch site of tricolour_amd.hip can produce, as fragments
+             points: `instances` lists every instantiation a launch site of the host code (tricolour_amd.hip and the
+             step host files it includes: host_text) can produce, as fragments
              with their template arguments ("k_pack_v<2>", "k_pack_scan_v<4, true, false, true>"; the bare name for a
              kernel that is no template).  An entry dict(name="k_x<3>", unreachable="why") is an instantiation no public
              call can reach.  The scans below hold the lists to the launch sites, and
@@ -51,6 +52,7 @@ import glob
 import itertools
 import os
 import re
+import shutil
 import subprocess
 
 import pytest
@@ -430,9 +432,24 @@ def _sources(directory=CSRC):
     return out
 
 
+def host_text(directory=CSRC):
+    """The host code: tricolour_amd.hip with the host files it includes (steps/step_host.hpp and one per step) spliced
+    in at their include lines.  The kernel headers (kernels_*.hpp) and tri_common.hpp stay include lines."""
+    def splice(m):
+        name = m.group(1)
+        if name == "tri_common.hpp" or os.path.basename(name).startswith("kernels_"):
+            return m.group(0)
+        with open(os.path.join(directory, name), encoding="utf-8") as fh:
+            return fh.read()
+    with open(os.path.join(directory, "tricolour_amd.hip"), encoding="utf-8") as fh:
+        return re.sub(r'^#include "([^"\n]+)"[^\n]*\n', splice, fh.read(), flags=re.M)
+
+
 def scan_getenv(directory=CSRC):
+    texts = _sources(directory)
+    texts[os.path.join(directory, "tricolour_amd.hip")] = host_text(directory)
     found = set()
-    for text in _sources(directory).values():
+    for text in texts.values():
         found.update(re.findall(r'getenv\(\s*"(TRI_[A-Z0-9_]+)"', text))
     return found
 
@@ -478,10 +495,9 @@ def _expand_launch_macros(hip):
 
 
 def scan_instances(directory=CSRC):
-    """{kernel: set of instantiations} of the launch sites of tricolour_amd.hip, launch macros expanded, template
+    """{kernel: set of instantiations} of the launch sites of the host code (host_text), launch macros expanded, template
     arguments in the demangler's spelling ("k_pack_scan_v<4, true, false, true>"; TRI_* codes as their numbers)."""
-    with open(os.path.join(directory, "tricolour_amd.hip"), encoding="utf-8") as fh:
-        hip = re.sub(r"//[^\n]*", "", fh.read())
+    hip = re.sub(r"//[^\n]*", "", host_text(directory))
     codes = _abi_codes()
     found = {}
     for m in re.finditer(r"hipLaunchKernelGGL\(\s*\(?\s*(k_\w+)\s*(?:<([^<>;()]*)>)?", _expand_launch_macros(hip)):
@@ -559,7 +575,15 @@ def test_every_kernel_has_a_row():
 
 def test_the_scans_notice_a_change(tmp_path):
     """A renamed getenv string, an added kernel or an added instantiation in a copy of the sources changes what the
-    scans find."""
+    scans find, in a step host file as in tricolour_amd.hip itself."""
+    shutil.copytree(CSRC, str(tmp_path), dirs_exist_ok=True)                  # the whole tree, steps/ included
+    step = tmp_path / "steps" / "linerms" / "linerms_host.hpp"
+    text = step.read_text(encoding="utf-8")
+    assert text.count("        hipLaunchKernelGGL(k_lrms_apply<true>,") == 1
+    text = text.replace("        hipLaunchKernelGGL(k_lrms_apply<true>,",
+                        "        hipLaunchKernelGGL(k_lrms_apply<7>, dim3(rows), dim3(256), 0, st);\n"
+                        "    else if (is1(getenv(\"TRI_ADDED_IN_A_STEP\")))\n        hipLaunchKernelGGL(k_lrms_apply<true>,")
+    step.write_text(text, encoding="utf-8")
     for path, text in _sources().items():
         text = text.replace('getenv("TRI_ST_NO_PIPE")', 'getenv("TRI_ST_NOPIPE")')
         if path.endswith("kernels_sir.hpp"):
@@ -573,11 +597,11 @@ def test_the_scans_notice_a_change(tmp_path):
                                 "        if (vec && ncorr == 8) TRI_PACK_SCAN_V(8, false);\n"
                                 "        else if (vec && ncorr == 4 && stokes) TRI_PACK_SCAN_V(4, true);", 1)
         (tmp_path / os.path.basename(path)).write_text(text, encoding="utf-8")
-    assert scan_getenv(str(tmp_path)) ^ set(SWITCHES) == {"TRI_ST_NO_PIPE", "TRI_ST_NOPIPE"}
+    assert scan_getenv(str(tmp_path)) ^ set(SWITCHES) == {"TRI_ST_NO_PIPE", "TRI_ST_NOPIPE", "TRI_ADDED_IN_A_STEP"}
     assert scan_kernels(str(tmp_path)) - set(KERNELS) == {"k_added_later"}
     before, after = scan_instances(), scan_instances(str(tmp_path))
     added = {f for k in after for f in after[k] - before.get(k, set())}
-    assert added == {"k_pack_v<8>"} | {"k_pack_scan_v<8, false, %s, %s>" % (m, f) for m in ("true", "false") for f in ("true", "false")}
+    assert added == {"k_pack_v<8>", "k_lrms_apply<7>"} | {"k_pack_scan_v<8, false, %s, %s>" % (m, f) for m in ("true", "false") for f in ("true", "false")}
     assert all(before[k] <= after[k] for k in before)
 
 
@@ -646,7 +670,7 @@ def test_instance_rows_cover_the_entry_point_kernels():
 
 
 def test_listed_instances_are_the_launch_sites():
-    """Every instantiation a launch site of tricolour_amd.hip produces is listed, and nothing else is."""
+    """Every instantiation a launch site of the host code produces is listed, and nothing else is."""
     found = scan_instances()
     for kernel in sorted(instance_rows()):
         listed = set(listed_instances(kernel))
@@ -657,8 +681,7 @@ def test_listed_instances_are_the_launch_sites():
 def test_the_literal_launch_sites_alone_miss_the_macro_families():
     """The macro families are found through the macro expansion only: without it the scan sees none of their
     instantiations (so the literal scan and the expansion are both at work), and with it the full product."""
-    with open(os.path.join(CSRC, "tricolour_amd.hip"), encoding="utf-8") as fh:
-        hip = re.sub(r"//[^\n]*", "", fh.read())
+    hip = re.sub(r"//[^\n]*", "", host_text())
     for kernel, macro in SCAN_FAMILIES.items():
         literal = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*%s\s*<([^<>;()]*)>" % kernel, hip)
         assert literal and all(re.search(r"\bNC\b", a) and re.search(r"\bS\b", a) for a in literal), kernel
@@ -784,8 +807,7 @@ def test_named_tests_exist():
 
 
 def test_unlaunched_kernels_have_no_launch_site():
-    with open(os.path.join(CSRC, "tricolour_amd.hip"), encoding="utf-8") as fh:
-        hip = fh.read()
+    hip = host_text()
     for kernel, where in KERNELS.items():
         used = re.search(r"\b%s\b" % kernel, re.sub(r"//[^\n]*", "", hip)) is not None
         defined_there = re.search(r"__global__[\s\S]{0,200}?\b%s\s*\(" % kernel, hip) is not None

@@ -7,6 +7,7 @@ fails loudly when the library is missing.
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -14,14 +15,27 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (kernel A/B experiments, scripts/build_variants.sh)
 LIB_PATH = os.environ.get("TRICOLOUR_AMD_LIB") or os.path.join(_HERE, "libtricolour_amd.so")
 SOURCES = [os.path.join(_HERE, "csrc", "tricolour_amd.hip")]   # one translation unit
-DEPENDS = [os.path.join(_HERE, "csrc", f) for f in (
-    "tri_common.hpp", "kernels_elementwise.hpp", "kernels_median.hpp", "kernels_reject.hpp", "kernels_reject_tile.hpp", "kernels_boxfilter.hpp", "kernels_boxline.hpp", "kernels_boxpipe.hpp",
-    "kernels_boxweight.hpp", "kernels_boxexact.hpp",
-    "kernels_sumthreshold.hpp", "kernels_scan.hpp", "kernels_sir.hpp", "kernels_linerms.hpp",
-    os.path.join("steps", "kernels_blint.hpp"), os.path.join("steps", "ldev", "kernels_ldev.hpp"),
-    os.path.join("steps", "ins", "kernels_ins.hpp"), os.path.join("steps", "hyst", "kernels_hyst.hpp"),
-    os.path.join("steps", "quality", "kernels_quality.hpp"), os.path.join("steps", "hist", "kernels_hist.hpp"))]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "tricolour_amd.h")
+
+
+def include_closure(sources, header=HEADER):
+    """Every file the quoted #include lines of `sources` reach, each resolved beside the file that names it, in the
+    order met; the sources themselves and the C header (kept apart as HEADER) are left out."""
+    found, todo = [], list(sources)
+    while todo:
+        path = todo.pop(0)
+        with open(path, encoding="utf-8") as fh:
+            names = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', fh.read(), re.M)
+        for name in names:
+            dep = os.path.normpath(os.path.join(os.path.dirname(path), name))
+            if dep not in found and dep not in sources and dep != header:
+                found.append(dep)
+                todo.append(dep)
+    return found
+
+
+# what a rebuild (needs_build) and source_hash() look at besides SOURCES and HEADER
+DEPENDS = include_closure(SOURCES)
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
                # IEEE evaluation order: no FMA contraction, no fast-math;

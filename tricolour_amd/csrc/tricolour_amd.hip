@@ -3244,1190 +3244,16 @@ extern "C" int tri_uvcontsub_flagger_debug(const void* vis_c64, const uint8_t* f
 }
 
 // ---------------------------------------------------------------------------
-// scale-invariant rank operator (kernels_sir.hpp): out = f | SIR_time(f) | SIR_freq(f) per (bl, corr) window
+// The stand-alone device steps: workspace, checks, launches and extern "C" entry points of each in a host file of its
+// own, beside its kernels where the step has a folder (still this one translation unit).  step_host.hpp holds the
+// checks they share.
 // ---------------------------------------------------------------------------
-// Routes, by line length alone:
-//   time  (n = ntime, 64 adjacent channels per block):  n <= 64: 256 threads x 1 sub-chunk;  n <= 256: 1024 x 1;
-//         n <= 1024: 1024 x 4;  longer: segments of 1024 samples (1024 x 4), three launches through the workspace
-//   freq  (n = nchan):  n <= 256: 16 lines per block, 256 threads x 1;  n <= 4096: one line per block, 256 x 1;
-//         n <= 16384: 1024 x 1;  n <= 65536: 512 x 8;  longer: segments of 65536 (512 x 8) through the workspace
-// The masked operator (tri_scale_invariant_rank_masked, k_sir<..., MISSING = true>) takes the same routes with the same
-// geometry; per (line, segment) its workspace holds one 64-bit (U, M) count where the unmasked one holds an int.
-#define SIR_TIME_SEG 1024
-#define SIR_FREQ_SEG 65536
-
-static size_t sir_ws_part(int64_t lines, int64_t n, int64_t seglen, size_t count_bytes) {
-    if (n <= seglen) return 0;
-    size_t e = (size_t)lines * (size_t)cdiv(n, seglen);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return al(e * count_bytes) + 2 * al(e * sizeof(double));
-}
-
-extern "C" size_t tri_sir_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan) {
-    if (n_win <= 0 || ntime <= 0 || nchan <= 0) return 0;
-    // the two axes run one after the other and share the workspace
-    return std::max(sir_ws_part(n_win * nchan, ntime, SIR_TIME_SEG, sizeof(int)),
-                    sir_ws_part(n_win * ntime, nchan, SIR_FREQ_SEG, sizeof(int)));
-}
-
-extern "C" size_t tri_sir_masked_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan) {
-    if (n_win <= 0 || ntime <= 0 || nchan <= 0) return 0;
-    return std::max(sir_ws_part(n_win * nchan, ntime, SIR_TIME_SEG, sizeof(unsigned long long)),
-                    sir_ws_part(n_win * ntime, nchan, SIR_FREQ_SEG, sizeof(unsigned long long)));
-}
-
-// miss == nullptr: the unmasked operator (penalty unused)
-struct SirMissing {
-    const uint8_t* miss;
-    double penalty;
-};
-
-template <int NT, int CB, int K, bool TIME, bool VEC, bool OR, bool MISSING>
-static int launch_sir(hipStream_t st, const uint8_t* in, uint8_t* out, int64_t nlines, int64_t ntime, int64_t nchan,
-                      double eta, void* ws, SirMissing mi) {
-    constexpr int SPAN = NT / CB * 16 * K;
-    const int64_t n = TIME ? ntime : nchan;
-    const int64_t gx = cdiv(nlines, CB);
-    if (gx >= (1ll << 31)) return set_err(TRI_EUNSUPPORTED, "too many lines for one launch");
-    if (n <= SPAN) {
-        hipLaunchKernelGGL((k_sir<NT, CB, K, SIR_FULL, TIME, VEC, OR, MISSING>), dim3((unsigned)gx), dim3(NT), 0, st, in,
-                           out, nlines, ntime, nchan, eta, 1, nullptr, nullptr, nullptr, mi.miss, mi.penalty);
-        LAUNCHCHK();
-        return TRI_OK;
-    }
-    const int64_t nseg = cdiv(n, SPAN);
-    if (nseg > 65535) return set_err(TRI_EUNSUPPORTED, "line too long");
-    const size_t e = (size_t)nlines * nseg;
-    Bump b(ws, SIZE_MAX, false);
-    int* cnt = MISSING ? (int*)b.get<unsigned long long>(e) : b.get<int>(e);
-    double* mn = b.get<double>(e);
-    double* mx = b.get<double>(e);
-    dim3 grid((unsigned)gx, (unsigned)nseg);
-    hipLaunchKernelGGL((k_sir<NT, CB, K, SIR_COUNT, TIME, VEC, OR, MISSING>), grid, dim3(NT), 0, st, in, out, nlines,
-                       ntime, nchan, eta, (int)nseg, cnt, mn, mx, mi.miss, mi.penalty);
-    hipLaunchKernelGGL((k_sir<NT, CB, K, SIR_MINMAX, TIME, VEC, OR, MISSING>), grid, dim3(NT), 0, st, in, out, nlines,
-                       ntime, nchan, eta, (int)nseg, cnt, mn, mx, mi.miss, mi.penalty);
-    hipLaunchKernelGGL((k_sir<NT, CB, K, SIR_FINAL, TIME, VEC, OR, MISSING>), grid, dim3(NT), 0, st, in, out, nlines,
-                       ntime, nchan, eta, (int)nseg, cnt, mn, mx, mi.miss, mi.penalty);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-template <bool VEC, bool OR, bool MISSING>
-static int launch_sir_freq(hipStream_t st, const uint8_t* in, uint8_t* out, int64_t n_win, int64_t ntime,
-                           int64_t nchan, double eta, void* ws, SirMissing mi) {
-    const int64_t lines = n_win * ntime;
-    if (nchan <= 256) return launch_sir<256, 16, 1, false, VEC, OR, MISSING>(st, in, out, lines, ntime, nchan, eta, ws, mi);
-    if (nchan <= 4096) return launch_sir<256, 1, 1, false, VEC, OR, MISSING>(st, in, out, lines, ntime, nchan, eta, ws, mi);
-    if (nchan <= 16384) return launch_sir<1024, 1, 1, false, VEC, OR, MISSING>(st, in, out, lines, ntime, nchan, eta, ws, mi);
-    // 512 x 8 rather than 1024 x 4: the latter needs more than the 128 VGPRs a 1024-thread block allows and spills
-    return launch_sir<512, 1, 8, false, VEC, OR, MISSING>(st, in, out, lines, ntime, nchan, eta, ws, mi);   // segments beyond 65536
-}
-
-template <bool MISSING>
-static int launch_sir_time(hipStream_t st, const uint8_t* in, uint8_t* out, int64_t n_win, int64_t ntime,
-                           int64_t nchan, double eta, void* ws, SirMissing mi) {
-    const int64_t lines = n_win * nchan;
-    if (ntime <= 64) return launch_sir<256, 64, 1, true, false, false, MISSING>(st, in, out, lines, ntime, nchan, eta, ws, mi);
-    if (ntime <= 256) return launch_sir<1024, 64, 1, true, false, false, MISSING>(st, in, out, lines, ntime, nchan, eta, ws, mi);
-    return launch_sir<1024, 64, 4, true, false, false, MISSING>(st, in, out, lines, ntime, nchan, eta, ws, mi);   // segments beyond 1024
-}
-static_assert(SIR_TIME_SEG == 1024 / 64 * 16 * 4 && SIR_FREQ_SEG == 512 * 16 * 8, "segment lengths follow the widest routes");
-
-// both entry points; MISSING: `mi.miss` has been checked by the caller
-template <bool MISSING>
-static int sir_run(const uint8_t* flags, uint8_t* out_flags, int64_t n_win, int64_t ntime, int64_t nchan,
-                   double eta_time, double eta_freq, SirMissing mi, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!flags || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (!(eta_time >= 0.0 && eta_time < 1.0) || !(eta_freq >= 0.0 && eta_freq < 1.0))
-        return set_err(TRI_EINVAL, "eta must lie in [0, 1)");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (ntime >= (1ll << 31) || nchan >= (1ll << 31) || n_win > (INT64_MAX / ntime) / nchan)
-        return set_err(TRI_EUNSUPPORTED, "window too large");
-    const size_t N = (size_t)n_win * ntime * nchan;
-    if ((uintptr_t)out_flags < (uintptr_t)flags + N && (uintptr_t)flags < (uintptr_t)out_flags + N)
-        return set_err(TRI_EINVAL, "out_flags must not overlap flags");
-    if (MISSING && (uintptr_t)out_flags < (uintptr_t)mi.miss + N && (uintptr_t)mi.miss < (uintptr_t)out_flags + N)
-        return set_err(TRI_EINVAL, "out_flags must not overlap missing");
-    const size_t need = MISSING ? tri_sir_masked_workspace_bytes(n_win, ntime, nchan) : tri_sir_workspace_bytes(n_win, ntime, nchan);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const bool t = eta_time > 0.0, f = eta_freq > 0.0;
-    if (!t && !f) {
-        hipLaunchKernelGGL(k_normalise_flags, dim3((unsigned)cdiv((int64_t)N, 256)), dim3(256), 0, st, flags, out_flags, N);
-        LAUNCHCHK();
-        return TRI_OK;
-    }
-    if (t) {
-        int rc = launch_sir_time<MISSING>(st, flags, out_flags, n_win, ntime, nchan, eta_time, workspace, mi);
-        if (rc) return rc;
-    }
-    if (f) {
-        // both axes read the INPUT mask; the frequency pass ORs into the time pass's result
-        const bool vec = nchan % 16 == 0 && (uintptr_t)flags % 16 == 0 && (uintptr_t)out_flags % 16 == 0 &&
-                         (!MISSING || (uintptr_t)mi.miss % 16 == 0);
-        int rc = vec ? (t ? launch_sir_freq<true, true, MISSING>(st, flags, out_flags, n_win, ntime, nchan, eta_freq, workspace, mi)
-                          : launch_sir_freq<true, false, MISSING>(st, flags, out_flags, n_win, ntime, nchan, eta_freq, workspace, mi))
-                     : (t ? launch_sir_freq<false, true, MISSING>(st, flags, out_flags, n_win, ntime, nchan, eta_freq, workspace, mi)
-                          : launch_sir_freq<false, false, MISSING>(st, flags, out_flags, n_win, ntime, nchan, eta_freq, workspace, mi));
-        if (rc) return rc;
-    }
-    return TRI_OK;
-}
-
-extern "C" int tri_scale_invariant_rank(const uint8_t* flags, uint8_t* out_flags, int64_t n_win, int64_t ntime,
-                                        int64_t nchan, double eta_time, double eta_freq, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-    return sir_run<false>(flags, out_flags, n_win, ntime, nchan, eta_time, eta_freq, SirMissing{nullptr, 0.0}, workspace,
-                          workspace_bytes, stream);
-}
-
-extern "C" int tri_scale_invariant_rank_masked(const uint8_t* flags, const uint8_t* missing, uint8_t* out_flags,
-                                               int64_t n_win, int64_t ntime, int64_t nchan, double eta_time,
-                                               double eta_freq, double penalty, void* workspace, size_t workspace_bytes,
-                                               void* stream) {
-    if (!missing) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (!(penalty >= 0.0) || !std::isfinite(penalty)) return set_err(TRI_EINVAL, "penalty must be finite and >= 0");
-    return sir_run<true>(flags, out_flags, n_win, ntime, nchan, eta_time, eta_freq, SirMissing{missing, penalty}, workspace,
-                         workspace_bytes, stream);
-}
-
-// ---------------------------------------------------------------------------
-// line-RMS statistics and thresholding of whole timesteps / channels (kernels_linerms.hpp)
-// ---------------------------------------------------------------------------
-// One shape of the power pass for every window (tiles of 64 rows x 1024 channels); two switches, by divisibility and
-// alignment alone (DESIGN.md §Line RMS): the power pass loads 16 bytes per lane when nchan % 4 == 0 and the bases
-// allow it, the apply pass 16 flags per lane when nchan % 16 == 0 and the bases allow it.  Neither changes a result.
-namespace {
-struct LrmsWs {
-    double *row_sum, *ch_sum, *rms_t, *rms_c;
-    int *row_cnt, *ch_cnt;
-    uint8_t *bad_t, *bad_c;
-    int64_t nstrip, ntiles;
-    size_t bytes;
-};
-
-LrmsWs lrms_carve(void* ws, int64_t n_win, int64_t ntime, int64_t nchan) {
-    LrmsWs w;
-    w.nstrip = cdiv(nchan, LRMS_CW);
-    w.ntiles = cdiv(ntime, LRMS_TR);
-    Bump b(ws, SIZE_MAX, ws == nullptr);
-    w.row_sum = b.get<double>((size_t)n_win * ntime * w.nstrip);
-    w.ch_sum = b.get<double>((size_t)n_win * w.ntiles * nchan);
-    w.rms_t = b.get<double>((size_t)n_win * ntime);
-    w.rms_c = b.get<double>((size_t)n_win * nchan);
-    w.row_cnt = b.get<int>((size_t)n_win * ntime * w.nstrip);
-    w.ch_cnt = b.get<int>((size_t)n_win * w.ntiles * nchan);
-    w.bad_t = b.get<uint8_t>((size_t)n_win * ntime);
-    w.bad_c = b.get<uint8_t>((size_t)n_win * nchan);
-    w.bytes = b.off;
-    return w;
-}
-
-// shape limits shared by the three entry points; 0 when the shape is fine
-int lrms_check_shape(int64_t n_win, int64_t ntime, int64_t nchan) {
-    if (ntime >= (1ll << 31) || nchan >= (1ll << 31) || n_win > (INT64_MAX / 16 / ntime) / nchan)
-        return set_err(TRI_EUNSUPPORTED, "window too large");
-    // a launch holds fewer than 2^32 threads: 256 per time row in the apply pass, 256 per tile in the power pass
-    if (n_win * ntime >= (1ll << 24) || n_win * cdiv(ntime, LRMS_TR) * cdiv(nchan, LRMS_CW) >= (1ll << 24) ||
-        n_win * (ntime + nchan) >= (1ll << 31) || cdiv(nchan, 256) > 65535)
-        return set_err(TRI_EUNSUPPORTED, "too many lines for one launch: pass fewer windows per call");
-    return 0;
-}
-
-// power pass and combine: rms (and counts, when asked for) of every line of n_win windows
-int lrms_statistics(hipStream_t st, const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_win, int64_t ntime,
-                    int64_t nchan, const LrmsWs& w, double* rms_t, double* rms_c, int* cnt_t, int* cnt_c) {
-    const bool c64 = vis_dtype == TRI_VIS_C64;
-    const bool vec = nchan % 4 == 0 && (uintptr_t)vis % 16 == 0 && (uintptr_t)flags % 4 == 0;
-    const dim3 grid((unsigned)(n_win * w.ntiles * w.nstrip));
-#define LRMS_POWER(V, VEC)                                                                                        \
-    hipLaunchKernelGGL((k_lrms_power<V, VEC>), grid, dim3(LRMS_NT), 0, st, vis, flags, ntime, nchan, (int)w.nstrip, \
-                       (int)w.ntiles, w.row_sum, w.row_cnt, w.ch_sum, w.ch_cnt)
-    if (c64) { if (vec) LRMS_POWER(TRI_VIS_C64, true); else LRMS_POWER(TRI_VIS_C64, false); }
-    else     { if (vec) LRMS_POWER(TRI_VIS_F32, true); else LRMS_POWER(TRI_VIS_F32, false); }
-#undef LRMS_POWER
-    LAUNCHCHK();
-    const int64_t lines = n_win * (ntime + nchan);
-    hipLaunchKernelGGL(k_lrms_combine, dim3((unsigned)cdiv(lines, 256)), dim3(256), 0, st, w.row_sum, w.row_cnt,
-                       w.ch_sum, w.ch_cnt, n_win, ntime, nchan, (int)w.nstrip, (int)w.ntiles, rms_t, rms_c, cnt_t, cnt_c);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-}  // namespace
-
-extern "C" size_t tri_line_rms_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan) {
-    if (n_win <= 0 || ntime <= 0 || nchan <= 0) return 0;
-    if (ntime >= (1ll << 31) || nchan >= (1ll << 31) || n_win > (INT64_MAX / 16 / ntime) / nchan) return 0;
-    return lrms_carve(nullptr, n_win, ntime, nchan).bytes;
-}
-
-extern "C" int tri_line_rms(const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_win, int64_t ntime,
-                            int64_t nchan, double* rms_time, double* rms_chan, int32_t* count_time,
-                            int32_t* count_chan, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!vis || !flags || !rms_time || !rms_chan) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = lrms_check_shape(n_win, ntime, nchan)) return rc;
-    const size_t need = tri_line_rms_workspace_bytes(n_win, ntime, nchan);
-    if (!workspace || workspace_bytes < need)
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    const LrmsWs w = lrms_carve(workspace, n_win, ntime, nchan);
-    return lrms_statistics((hipStream_t)stream, vis, vis_dtype, flags, n_win, ntime, nchan, w, rms_time, rms_chan,
-                           count_time, count_chan);
-}
-
-extern "C" int tri_line_rms_threshold(const void* vis, int vis_dtype, const uint8_t* flags, uint8_t* out_flags,
-                                      int64_t n_win, int64_t ntime, int64_t nchan, double nsigma_time,
-                                      double nsigma_freq, int flag_low, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
-    if (!vis || !flags || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (!(nsigma_time >= 0.0) || !(nsigma_freq >= 0.0)) return set_err(TRI_EINVAL, "nsigma must be >= 0");
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = lrms_check_shape(n_win, ntime, nchan)) return rc;
-    const size_t N = (size_t)n_win * ntime * nchan;
-    if ((uintptr_t)out_flags < (uintptr_t)flags + N && (uintptr_t)flags < (uintptr_t)out_flags + N)
-        return set_err(TRI_EINVAL, "out_flags must not overlap flags");
-    const size_t need = tri_line_rms_workspace_bytes(n_win, ntime, nchan);
-    if (!workspace || workspace_bytes < need)
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    if (nsigma_time == 0.0 && nsigma_freq == 0.0) {
-        hipLaunchKernelGGL(k_normalise_flags, dim3((unsigned)cdiv((int64_t)N, 256)), dim3(256), 0, st, flags, out_flags, N);
-        LAUNCHCHK();
-        return TRI_OK;
-    }
-    const LrmsWs w = lrms_carve(workspace, n_win, ntime, nchan);
-    if (int rc = lrms_statistics(st, vis, vis_dtype, flags, n_win, ntime, nchan, w, w.rms_t, w.rms_c, nullptr, nullptr))
-        return rc;
-    hipLaunchKernelGGL(k_lrms_decide, dim3((unsigned)n_win, 2), dim3(LRMS_DT), 0, st, w.rms_t, w.rms_c, ntime, nchan,
-                       nsigma_time, nsigma_freq, flag_low ? 1 : 0, w.bad_t, w.bad_c);
-    LAUNCHCHK();
-    const unsigned rows = (unsigned)(n_win * ntime);
-    if (nchan % 16 == 0 && (uintptr_t)flags % 16 == 0 && (uintptr_t)out_flags % 16 == 0)
-        hipLaunchKernelGGL(k_lrms_apply<true>, dim3(rows, (unsigned)cdiv(nchan, 4096)), dim3(256), 0, st, flags, w.bad_t,
-                           w.bad_c, out_flags, ntime, nchan);
-    else
-        hipLaunchKernelGGL(k_lrms_apply<false>, dim3(rows, (unsigned)cdiv(nchan, 256)), dim3(256), 0, st, flags, w.bad_t,
-                           w.bad_c, out_flags, ntime, nchan);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// ---------------------------------------------------------------------------
-// baseline integration: mean amplitude over baselines, flagged as one image (steps/kernels_blint.hpp)
-// ---------------------------------------------------------------------------
-// Two switches, by divisibility and alignment alone (DESIGN.md §Baseline integration): the accumulate owns 4 positions
-// per thread when n % 4 == 0 and the bases allow 16-byte loads, the apply pass 16 flags per thread when n % 16 == 0 and
-// the bases allow it.  Neither changes a result.
-extern "C" int tri_baseline_accumulate(const void* vis, int vis_dtype, const uint8_t* flags, const uint8_t* select,
-                                       int64_t nbl, int64_t n, double* sum, int32_t* count, void* stream) {
-    if (!vis || !flags || !sum || !count) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (nbl < 0 || n < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (nbl == 0 || n == 0) return TRI_OK;
-    if (n >= (1ll << 38) || nbl > (INT64_MAX / 16) / n) return set_err(TRI_EUNSUPPORTED, "image too large");
-    const bool vec = n % 4 == 0 && (uintptr_t)vis % 16 == 0 && (uintptr_t)flags % 4 == 0 && (uintptr_t)sum % 16 == 0 &&
-                     (uintptr_t)count % 16 == 0;
-    const int64_t npiece = vec ? n / 4 : n;
-    const dim3 grid((unsigned)cdiv(npiece, BLI_NT));
-    hipStream_t st = (hipStream_t)stream;
-#define BLI_ACCUMULATE(V, VEC)                                                                                   \
-    hipLaunchKernelGGL((k_bli_accumulate<V, VEC>), grid, dim3(BLI_NT), 0, st, vis, flags, select, nbl, n, npiece, sum, \
-                       count)
-    if (vis_dtype == TRI_VIS_C64) { if (vec) BLI_ACCUMULATE(TRI_VIS_C64, 4); else BLI_ACCUMULATE(TRI_VIS_C64, 1); }
-    else                          { if (vec) BLI_ACCUMULATE(TRI_VIS_F32, 4); else BLI_ACCUMULATE(TRI_VIS_F32, 1); }
-#undef BLI_ACCUMULATE
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-extern "C" int tri_baseline_mean(const double* sum, const int32_t* count, int64_t n, int64_t min_count, float* amp,
-                                 uint8_t* flag, void* stream) {
-    if (!sum || !count || !amp || !flag) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (min_count < 1) return set_err(TRI_EINVAL, "min_count must be >= 1");
-    if (n == 0) return TRI_OK;
-    if (n >= (1ll << 38)) return set_err(TRI_EUNSUPPORTED, "image too large");
-    hipLaunchKernelGGL(k_bli_finish, dim3((unsigned)cdiv(n, BLI_NT)), dim3(BLI_NT), 0, (hipStream_t)stream, sum, count, n,
-                       min_count, amp, flag);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-extern "C" int tri_broadcast_or(const uint8_t* flags, const uint8_t* line, uint8_t* out, int64_t nbl, int64_t n,
-                                void* stream) {
-    if (!flags || !line || !out) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (nbl < 0 || n < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (nbl == 0 || n == 0) return TRI_OK;
-    if (n >= (1ll << 38) || nbl > (INT64_MAX / 16) / n) return set_err(TRI_EUNSUPPORTED, "image too large");
-    const size_t N = (size_t)nbl * n;
-    if ((uintptr_t)out < (uintptr_t)line + (size_t)n && (uintptr_t)line < (uintptr_t)out + N)
-        return set_err(TRI_EINVAL, "out must not overlap line");
-    // in place (out == flags) is fine: every byte is read and written by one thread; a shifted overlap is not
-    if (out != flags && (uintptr_t)out < (uintptr_t)flags + N && (uintptr_t)flags < (uintptr_t)out + N)
-        return set_err(TRI_EINVAL, "out must be flags itself or not overlap it");
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned gy = (unsigned)std::min<int64_t>(nbl, 65535);
-    if (n % 16 == 0 && (uintptr_t)flags % 16 == 0 && (uintptr_t)line % 16 == 0 && (uintptr_t)out % 16 == 0)
-        hipLaunchKernelGGL(k_bli_apply<true>, dim3((unsigned)cdiv(n / 16, BLI_NT), gy), dim3(BLI_NT), 0, st, flags, line,
-                           out, nbl, n);
-    else
-        hipLaunchKernelGGL(k_bli_apply<false>, dim3((unsigned)cdiv(n, BLI_NT), gy), dim3(BLI_NT), 0, st, flags, line, out,
-                           nbl, n);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// ---------------------------------------------------------------------------
-// sliding-window complex deviation and its thresholding (steps/ldev/kernels_ldev.hpp)
-// ---------------------------------------------------------------------------
-// Routes, by width, divisibility and alignment alone (DESIGN.md §Local deviation): windows 3 and 5 run the compiled
-// register-ring kernels, every other width the run-time one; the deviation passes load 16 bytes per lane when
-// nchan % 4 == 0 and the bases allow it, the apply pass 16 flags per lane when the sample count % 16 == 0 and the bases
-// allow it.  None changes a result.
-namespace {
-struct LdevWs {
-    float *d_t, *d_f;
-    uint8_t *hit_t, *hit_f;
-    int64_t* ends;
-    size_t bytes;
-};
-
-LdevWs ldev_carve(void* ws, int64_t n_win, int64_t ntime, int64_t nchan, int64_t n_chunk_ends) {
-    LdevWs w;
-    const size_t N = (size_t)n_win * ntime * nchan;
-    Bump b(ws, SIZE_MAX, ws == nullptr);
-    w.d_t = b.get<float>(N);
-    w.d_f = b.get<float>(N);
-    w.hit_t = b.get<uint8_t>(N);
-    w.hit_f = b.get<uint8_t>(N);
-    w.ends = b.get<int64_t>((size_t)n_chunk_ends);
-    w.bytes = b.off;
-    return w;
-}
-
-bool ldev_shape_fits(int64_t n_win, int64_t ntime, int64_t nchan) {
-    return ntime < (1ll << 31) && nchan < (1ll << 31) && n_win <= (INT64_MAX / 16 / ntime) / nchan;
-}
-
-// shape limits of the entry points; 0 when the shape is fine
-int ldev_check_shape(int64_t n_win, int64_t ntime, int64_t nchan, int64_t nchunk) {
-    if (!ldev_shape_fits(n_win, ntime, nchan)) return set_err(TRI_EUNSUPPORTED, "window too large");
-    // every launch is one-dimensional and holds fewer than 2^31 blocks
-    const int64_t lim = (1ll << 31) - 1;
-    const int64_t strips = cdiv(nchan, LDEV_CW);
-    if (n_win > lim / (ntime * strips) || n_win > lim / cdiv(nchan, LDEV_LC) ||
-        cdiv((int64_t)n_win * ntime * nchan, LDEV_NT) > lim || (nchunk > 0 && n_win * ntime > lim / nchunk))
-        return set_err(TRI_EUNSUPPORTED, "too many lines for one launch: pass fewer windows per call");
-    return 0;
-}
-
-int ldev_check_window(const char* name, int64_t w) {
-    if (w < 3 || w > LDEV_MAXW || w % 2 == 0)
-        return set_err(TRI_EINVAL, "%s must be an odd integer in [3, %d], got %lld", name, LDEV_MAXW, (long long)w);
-    return 0;
-}
-
-// d along one axis (time: axis 0) of n_win windows into `out`
-int ldev_deviation(hipStream_t st, int axis, const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_win,
-                   int64_t ntime, int64_t nchan, int window, float* out) {
-    const bool c64 = vis_dtype == TRI_VIS_C64;
-    const bool vec = nchan % 4 == 0 && (uintptr_t)vis % 16 == 0 && (uintptr_t)flags % 4 == 0 && (uintptr_t)out % 16 == 0;
-    const int nstrip = (int)cdiv(nchan, LDEV_CW);
-    const int ntiles = (int)cdiv(ntime, axis == 0 ? LDEV_TR : LDEV_FR);
-    const dim3 grid((unsigned)(n_win * ntiles * nstrip));
-#define LDEV_PASS(K, V, VEC)                                                                                          \
-    do {                                                                                                              \
-        if (window == 3)                                                                                              \
-            hipLaunchKernelGGL((K<V, 3, VEC>), grid, dim3(LDEV_NT), 0, st, vis, flags, ntime, nchan, nstrip, ntiles,  \
-                               window, out);                                                                          \
-        else if (window == 5)                                                                                         \
-            hipLaunchKernelGGL((K<V, 5, VEC>), grid, dim3(LDEV_NT), 0, st, vis, flags, ntime, nchan, nstrip, ntiles,  \
-                               window, out);                                                                          \
-        else                                                                                                          \
-            hipLaunchKernelGGL((K<V, 0, VEC>), grid, dim3(LDEV_NT), 0, st, vis, flags, ntime, nchan, nstrip, ntiles,  \
-                               window, out);                                                                          \
-    } while (0)
-    if (axis == 0) {
-        if (c64) { if (vec) LDEV_PASS(k_ldev_time, TRI_VIS_C64, true); else LDEV_PASS(k_ldev_time, TRI_VIS_C64, false); }
-        else     { if (vec) LDEV_PASS(k_ldev_time, TRI_VIS_F32, true); else LDEV_PASS(k_ldev_time, TRI_VIS_F32, false); }
-    } else {
-        if (c64) { if (vec) LDEV_PASS(k_ldev_freq, TRI_VIS_C64, true); else LDEV_PASS(k_ldev_freq, TRI_VIS_C64, false); }
-        else     { if (vec) LDEV_PASS(k_ldev_freq, TRI_VIS_F32, true); else LDEV_PASS(k_ldev_freq, TRI_VIS_F32, false); }
-    }
-#undef LDEV_PASS
-    LAUNCHCHK();
-    return TRI_OK;
-}
-}  // namespace
-
-extern "C" size_t tri_local_deviation_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan,
-                                                      int64_t n_chunk_ends) {
-    if (n_win <= 0 || ntime <= 0 || nchan <= 0 || n_chunk_ends < 2) return 0;
-    if (!ldev_shape_fits(n_win, ntime, nchan)) return 0;
-    return ldev_carve(nullptr, n_win, ntime, nchan, n_chunk_ends).bytes;
-}
-
-extern "C" int tri_local_deviation(const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_win, int64_t ntime,
-                                   int64_t nchan, int64_t window_time, int64_t window_freq, float* d_time,
-                                   float* d_freq, void* stream) {
-    if (!vis || !flags) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (int rc = ldev_check_window("window_time", window_time)) return rc;
-    if (int rc = ldev_check_window("window_freq", window_freq)) return rc;
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = ldev_check_shape(n_win, ntime, nchan, 0)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (d_time)
-        if (int rc = ldev_deviation(st, 0, vis, vis_dtype, flags, n_win, ntime, nchan, (int)window_time, d_time)) return rc;
-    if (d_freq)
-        if (int rc = ldev_deviation(st, 1, vis, vis_dtype, flags, n_win, ntime, nchan, (int)window_freq, d_freq)) return rc;
-    return TRI_OK;
-}
-
-extern "C" int tri_local_deviation_threshold(const void* vis, int vis_dtype, const uint8_t* flags, uint8_t* out_flags,
-                                             int64_t n_win, int64_t ntime, int64_t nchan, int64_t window_time,
-                                             int64_t window_freq, double scale_time, double scale_freq,
-                                             const int64_t* chunk_ends, int64_t n_chunk_ends, void* workspace,
-                                             size_t workspace_bytes, void* stream) {
-    if (!vis || !flags || !out_flags || !chunk_ends) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (int rc = ldev_check_window("window_time", window_time)) return rc;
-    if (int rc = ldev_check_window("window_freq", window_freq)) return rc;
-    if (!(scale_time >= 0.0) || !(scale_freq >= 0.0)) return set_err(TRI_EINVAL, "scale must be >= 0");
-    if (n_chunk_ends < 2 || n_chunk_ends > (1ll << 30)) return set_err(TRI_EINVAL, "freq_chunks must be >= 1");
-    if (chunk_ends[0] != 0 || chunk_ends[n_chunk_ends - 1] != nchan)
-        return set_err(TRI_EINVAL, "freq chunk ends must start at 0 and end at the channel count");
-    for (int64_t g = 1; g < n_chunk_ends; g++)
-        if (chunk_ends[g] < chunk_ends[g - 1]) return set_err(TRI_EINVAL, "freq chunk ends must not decrease");
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    const int64_t nchunk = n_chunk_ends - 1;
-    if (int rc = ldev_check_shape(n_win, ntime, nchan, nchunk)) return rc;
-    const size_t N = (size_t)n_win * ntime * nchan;
-    if ((uintptr_t)out_flags < (uintptr_t)flags + N && (uintptr_t)flags < (uintptr_t)out_flags + N)
-        return set_err(TRI_EINVAL, "out_flags must not overlap flags");
-    const size_t need = tri_local_deviation_workspace_bytes(n_win, ntime, nchan, n_chunk_ends);
-    if (!workspace || workspace_bytes < need)
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const bool on_t = scale_time > 0.0, on_f = scale_freq > 0.0;
-    if (!on_t && !on_f) {
-        hipLaunchKernelGGL(k_normalise_flags, dim3((unsigned)cdiv((int64_t)N, 256)), dim3(256), 0, st, flags, out_flags, N);
-        LAUNCHCHK();
-        return TRI_OK;
-    }
-    const LdevWs w = ldev_carve(workspace, n_win, ntime, nchan, n_chunk_ends);
-    if (on_t) {
-        if (int rc = ldev_deviation(st, 0, vis, vis_dtype, flags, n_win, ntime, nchan, (int)window_time, w.d_t)) return rc;
-        hipLaunchKernelGGL(k_ldev_level<0>, dim3((unsigned)(n_win * cdiv(nchan, LDEV_LC))), dim3(LDEV_NT), 0, st, w.d_t,
-                           n_win, ntime, nchan, (const int64_t*)nullptr, 0, scale_time, w.hit_t);
-        LAUNCHCHK();
-    }
-    if (on_f) {
-        // (pageable host memory: the copy is staged before the call returns, so the caller's array may go)
-        HIPCHK(hipMemcpyAsync(w.ends, chunk_ends, (size_t)n_chunk_ends * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        if (int rc = ldev_deviation(st, 1, vis, vis_dtype, flags, n_win, ntime, nchan, (int)window_freq, w.d_f)) return rc;
-        hipLaunchKernelGGL(k_ldev_level<1>, dim3((unsigned)cdiv(n_win * ntime * nchunk, LDEV_LW)), dim3(LDEV_NT), 0, st,
-                           w.d_f, n_win, ntime, nchan, (const int64_t*)w.ends, (int)nchunk, scale_freq, w.hit_f);
-        LAUNCHCHK();
-    }
-    const uint8_t* ht = on_t ? w.hit_t : nullptr;
-    const uint8_t* hf = on_f ? w.hit_f : nullptr;
-    if (N % 16 == 0 && (uintptr_t)flags % 16 == 0 && (uintptr_t)out_flags % 16 == 0)
-        hipLaunchKernelGGL(k_ldev_apply<true>, dim3((unsigned)cdiv((int64_t)N / 16, LDEV_NT)), dim3(LDEV_NT), 0, st, flags,
-                           ht, hf, out_flags, (int64_t)N);
-    else
-        hipLaunchKernelGGL(k_ldev_apply<false>, dim3((unsigned)cdiv((int64_t)N, LDEV_NT)), dim3(LDEV_NT), 0, st, flags, ht,
-                           hf, out_flags, (int64_t)N);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// ---------------------------------------------------------------------------
-// sky-subtracted incoherent noise spectrum (steps/ins/kernels_ins.hpp)
-// ---------------------------------------------------------------------------
-// Three switches, by size, divisibility and alignment alone (DESIGN.md §Incoherent noise spectrum): the accumulate
-// owns strips of 8 difference rows when the image then still fills the device and single rows otherwise, and 4 channels
-// per thread when nchan % 4 == 0 and the bases allow 16-byte loads; the apply pass owns 16 flags per thread when
-// nchan % 16 == 0 and the bases allow it.  None changes a result.
-namespace {
-struct InsWs {
-    float *x, *level;
-    uint8_t *live, *valid;
-    int32_t* q;
-    size_t bytes;
-};
-
-// nimg = ncorr * (ntime - 1) * nchan positions, nline = ncorr * nchan lines
-InsWs ins_carve(void* ws, size_t nimg, size_t nline) {
-    InsWs w;
-    Bump b(ws, SIZE_MAX, ws == nullptr);
-    w.x = b.get<float>(nimg);
-    w.live = b.get<uint8_t>(nline);
-    w.level = b.get<float>(nline);
-    w.q = b.get<int32_t>(nimg);
-    w.valid = b.get<uint8_t>(nimg);
-    w.bytes = b.off;
-    return w;
-}
-
-bool ins_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-
-// shape limits of the entry points (every launch is one-dimensional in x and holds fewer than 2^31 blocks); 0 when
-// the shape is fine.  Called with all three sizes > 0.
-int ins_check_shape(int64_t nbl, int64_t ncorr, int64_t ntime, int64_t nchan) {
-    if (ntime >= (1ll << 31) || nchan >= (1ll << 31) || ncorr > ((1ll << 38) / ntime) / nchan)
-        return set_err(TRI_EUNSUPPORTED, "image too large");
-    if (nbl > (INT64_MAX / 16) / (ncorr * ntime * nchan)) return set_err(TRI_EUNSUPPORTED, "image too large");
-    if (ncorr * ntime >= (1ll << 31)) return set_err(TRI_EUNSUPPORTED, "too many rows for one launch");
-    return 0;
-}
-
-// level, q and valid of one round from x / count / mask
-int ins_round(hipStream_t st, const float* x, const int32_t* count, const uint8_t* mask, int64_t ncorr, int64_t nd,
-              int64_t nchan, int64_t min_count, float* level, uint8_t* live, int32_t* q, uint8_t* valid) {
-    const int64_t nimg = ncorr * nd * nchan;
-    hipLaunchKernelGGL(k_ins_level, dim3((unsigned)(ncorr * cdiv(nchan, INS_LC))), dim3(INS_NT), 0, st, x, mask, nd, nchan,
-                       level, live);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(k_ins_zq, dim3((unsigned)cdiv(nimg, INS_NT)), dim3(INS_NT), 0, st, x, count, mask,
-                       (const float*)level, (const uint8_t*)live, nd, nchan, nimg, min_count, q, valid);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-}  // namespace
-
-extern "C" int tri_ins_accumulate(const void* vis, int vis_dtype, const uint8_t* flags, const uint8_t* select,
-                                  int64_t nbl, int64_t ncorr, int64_t ntime, int64_t nchan, double* sum,
-                                  int32_t* count, void* stream) {
-    if (!vis || !flags || !sum || !count) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (nbl < 0 || ncorr < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (nbl == 0 || ncorr == 0 || ntime < 2 || nchan == 0) return TRI_OK;
-    if (int rc = ins_check_shape(nbl, ncorr, ntime, nchan)) return rc;
-    const size_t nimg = (size_t)ncorr * (ntime - 1) * nchan;
-    if (ins_overlap(sum, nimg * sizeof(double), count, nimg * sizeof(int32_t)))
-        return set_err(TRI_EINVAL, "sum and count must not overlap");
-    const bool vec = nchan % 4 == 0 && (uintptr_t)vis % 16 == 0 && (uintptr_t)flags % 4 == 0 && (uintptr_t)sum % 16 == 0 &&
-                     (uintptr_t)count % 16 == 0;
-    // strips of INS_STRIP rows when those fill the device, else one row per thread
-    static_assert(INS_STRIP == 8 && INS_UNROLL == 4, "the launch sites below spell the two forms out");
-    const int64_t npc = vec ? nchan / 4 : nchan;
-    const bool strips = ncorr * cdiv(ntime - 1, INS_STRIP) * npc >= INS_FILL;
-    const int64_t ntile = strips ? cdiv(ntime - 1, INS_STRIP) : ntime - 1;
-    const dim3 grid((unsigned)cdiv(ncorr * ntile * npc, INS_NT));
-    hipStream_t st = (hipStream_t)stream;
-#define INS_ACCUMULATE(V, VEC)                                                                                        \
-    do {                                                                                                              \
-        if (strips)                                                                                                   \
-            hipLaunchKernelGGL((k_ins_accumulate<V, VEC, 8, 1>), grid, dim3(INS_NT), 0, st, vis, flags, select, nbl,  \
-                               ncorr, ntime, nchan, npc, ntile, sum, count);                                          \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_ins_accumulate<V, VEC, 1, 4>), grid, dim3(INS_NT), 0, st, vis, flags, select, nbl,  \
-                               ncorr, ntime, nchan, npc, ntile, sum, count);                                          \
-    } while (0)
-    if (vis_dtype == TRI_VIS_C64) { if (vec) INS_ACCUMULATE(TRI_VIS_C64, 4); else INS_ACCUMULATE(TRI_VIS_C64, 1); }
-    else                          { if (vec) INS_ACCUMULATE(TRI_VIS_F32, 4); else INS_ACCUMULATE(TRI_VIS_F32, 1); }
-#undef INS_ACCUMULATE
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-extern "C" size_t tri_ins_workspace_bytes(int64_t ncorr, int64_t ntime, int64_t nchan) {
-    if (ncorr <= 0 || ntime < 2 || nchan <= 0) return 0;
-    if (ntime >= (1ll << 31) || nchan >= (1ll << 31) || ncorr > ((1ll << 38) / ntime) / nchan) return 0;
-    return ins_carve(nullptr, (size_t)ncorr * (ntime - 1) * nchan, (size_t)ncorr * nchan).bytes;
-}
-
-extern "C" int tri_ins_zscore(const double* sum, const int32_t* count, const uint8_t* mask, int64_t ncorr,
-                              int64_t ntime, int64_t nchan, int64_t min_count, float* level, int32_t* q,
-                              uint8_t* valid, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!sum || !count || !mask || !level || !q || !valid) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (ncorr < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (min_count < 1) return set_err(TRI_EINVAL, "min_count must be >= 1");
-    if (ncorr == 0 || ntime < 2 || nchan == 0) return TRI_OK;
-    if (int rc = ins_check_shape(1, ncorr, ntime, nchan)) return rc;
-    const int64_t nd = ntime - 1;
-    const size_t nimg = (size_t)ncorr * nd * nchan, nline = (size_t)ncorr * nchan;
-    const void* ptr[6] = {level, q, valid, sum, count, mask};
-    const size_t len[6] = {nline * 4, nimg * 4, nimg, nimg * 8, nimg * 4, nimg};
-    for (int a = 0; a < 3; a++)                              // every output against everything after it
-        for (int b = a + 1; b < 6; b++)
-            if (ins_overlap(ptr[a], len[a], ptr[b], len[b]))
-                return set_err(TRI_EINVAL, "level, q and valid must not overlap each other or the inputs");
-    const size_t need = tri_ins_workspace_bytes(ncorr, ntime, nchan);
-    if (!workspace || workspace_bytes < need)
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    const InsWs w = ins_carve(workspace, nimg, nline);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ins_mean, dim3((unsigned)cdiv((int64_t)nimg, INS_NT)), dim3(INS_NT), 0, st, sum, count,
-                       (int64_t)nimg, min_count, w.x);
-    LAUNCHCHK();
-    return ins_round(st, w.x, count, mask, ncorr, nd, nchan, min_count, level, w.live, q, valid);
-}
-
-extern "C" int tri_ins_match(const double* sum, const int32_t* count, int64_t ncorr, int64_t ntime, int64_t nchan,
-                             int64_t min_count, const int64_t* shape_lo, const int64_t* shape_hi,
-                             const double* shape_nsigma, int64_t n_shapes, double nsigma_narrow, int64_t rounds,
-                             uint8_t* mask, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!sum || !count || !mask) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (ncorr < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (min_count < 1) return set_err(TRI_EINVAL, "min_count must be >= 1");
-    if (n_shapes < 0 || n_shapes > INS_MAX_SHAPES)
-        return set_err(TRI_EINVAL, "at most %d shapes, got %lld", INS_MAX_SHAPES, (long long)n_shapes);
-    if (n_shapes > 0 && (!shape_lo || !shape_hi || !shape_nsigma)) return set_err(TRI_EINVAL, "NULL pointer argument");
-    InsShapes sh;
-    memset(&sh, 0, sizeof(sh));
-    for (int64_t i = 0; i < n_shapes; i++) {
-        if (!(0 <= shape_lo[i] && shape_lo[i] < shape_hi[i] && shape_hi[i] <= nchan))
-            return set_err(TRI_EINVAL, "shape %lld: channels [%lld, %lld) do not lie in [0, %lld)", (long long)i,
-                           (long long)shape_lo[i], (long long)shape_hi[i], (long long)nchan);
-        if (!(shape_nsigma[i] > 0.0)) return set_err(TRI_EINVAL, "shape %lld: nsigma must be > 0", (long long)i);
-    }
-    if (!(nsigma_narrow >= 0.0)) return set_err(TRI_EINVAL, "nsigma_narrow must be >= 0 (0 switches it off)");
-    if (rounds < 1 || rounds > 16) return set_err(TRI_EINVAL, "rounds must lie in [1, 16], got %lld", (long long)rounds);
-    if (ncorr == 0 || ntime < 2 || nchan == 0) return TRI_OK;
-    if (int rc = ins_check_shape(1, ncorr, ntime, nchan)) return rc;
-    const int64_t nd = ntime - 1;
-    const size_t nimg = (size_t)ncorr * nd * nchan, nline = (size_t)ncorr * nchan;
-    if (ins_overlap(mask, nimg, sum, nimg * 8) || ins_overlap(mask, nimg, count, nimg * 4))
-        return set_err(TRI_EINVAL, "mask must not overlap sum or count");
-    const size_t need = tri_ins_workspace_bytes(ncorr, ntime, nchan);
-    if (!workspace || workspace_bytes < need)
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    sh.n = (int)n_shapes;
-    for (int64_t i = 0; i < n_shapes; i++) {
-        sh.lo[i] = (int)shape_lo[i];
-        sh.hi[i] = (int)shape_hi[i];
-        sh.nsigma[i] = shape_nsigma[i];
-    }
-    sh.nsigma_narrow = nsigma_narrow;
-    const InsWs w = ins_carve(workspace, nimg, nline);
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(mask, 0, nimg, st));
-    hipLaunchKernelGGL(k_ins_mean, dim3((unsigned)cdiv((int64_t)nimg, INS_NT)), dim3(INS_NT), 0, st, sum, count,
-                       (int64_t)nimg, min_count, w.x);
-    LAUNCHCHK();
-    // a fixed number of rounds, nothing read back: a round that finds nothing changes nothing
-    for (int64_t r = 0; r < rounds; r++) {
-        if (int rc = ins_round(st, w.x, count, mask, ncorr, nd, nchan, min_count, w.level, w.live, w.q, w.valid)) return rc;
-        hipLaunchKernelGGL(k_ins_match, dim3((unsigned)(ncorr * nd)), dim3(INS_NT), 0, st, (const int32_t*)w.q,
-                           (const uint8_t*)w.valid, nchan, sh, mask);
-        LAUNCHCHK();
-    }
-    return TRI_OK;
-}
-
-extern "C" int tri_ins_apply(const uint8_t* flags, const uint8_t* mask, uint8_t* out, int64_t nbl, int64_t ncorr,
-                             int64_t ntime, int64_t nchan, void* stream) {
-    if (!flags || !mask || !out) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (nbl < 0 || ncorr < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (nbl == 0 || ncorr == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = ins_check_shape(nbl, ncorr, ntime, nchan)) return rc;
-    const int64_t n = ncorr * ntime * nchan;
-    const size_t N = (size_t)nbl * n, nimg = (size_t)ncorr * (ntime - 1) * nchan;
-    if (nimg && ins_overlap(out, N, mask, nimg)) return set_err(TRI_EINVAL, "out must not overlap mask");
-    // in place (out == flags) is fine: every byte is read and written by one thread; a shifted overlap is not
-    if (out != flags && ins_overlap(out, N, flags, N))
-        return set_err(TRI_EINVAL, "out must be flags itself or not overlap it");
-    const unsigned gy = (unsigned)std::min<int64_t>(nbl, 65535);
-    hipStream_t st = (hipStream_t)stream;
-    if (nchan % 16 == 0 && (uintptr_t)flags % 16 == 0 && (uintptr_t)mask % 16 == 0 && (uintptr_t)out % 16 == 0)
-        hipLaunchKernelGGL(k_ins_apply<true>, dim3((unsigned)cdiv(n / 16, INS_NT), gy), dim3(INS_NT), 0, st, flags, mask,
-                           out, nbl, ntime, nchan, n);
-    else
-        hipLaunchKernelGGL(k_ins_apply<false>, dim3((unsigned)cdiv(n, INS_NT), gy), dim3(INS_NT), 0, st, flags, mask, out,
-                           nbl, ntime, nchan, n);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// ---------------------------------------------------------------------------
-// value-driven hysteresis growth of flags (steps/hyst/kernels_hyst.hpp)
-// ---------------------------------------------------------------------------
-// Routes, by shape, divisibility and alignment alone (DESIGN.md §Hysteresis growth): a level line of at most HYST_LN
-// samples keeps its keys in LDS, a longer one is re-read for every pass (decided inside the kernel, per line); the
-// growth kernel writes 16 flags per lane when nchan % 16 == 0 and the bases allow it.  None changes a result.
-namespace {
-struct HystWs {
-    float *med_t, *mad_t, *med_f, *mad_f;
-    unsigned *seed, *et, *ef;
-    int64_t* ends;
-    size_t bytes;
-};
-
-HystWs hyst_carve(void* ws, int64_t n_win, int64_t ntime, int64_t nchan, int64_t n_chunk_ends) {
-    HystWs w;
-    const size_t lines_t = (size_t)n_win * nchan, lines_f = (size_t)n_win * ntime * (size_t)(n_chunk_ends - 1);
-    const size_t words = (size_t)n_win * ntime * (size_t)cdiv(nchan, 32);
-    Bump b(ws, SIZE_MAX, ws == nullptr);
-    w.med_t = b.get<float>(lines_t);
-    w.mad_t = b.get<float>(lines_t);
-    w.med_f = b.get<float>(lines_f);
-    w.mad_f = b.get<float>(lines_f);
-    w.seed = b.get<unsigned>(words);
-    w.et = b.get<unsigned>(words);
-    w.ef = b.get<unsigned>(words);
-    w.ends = b.get<int64_t>((size_t)n_chunk_ends);
-    w.bytes = b.off;
-    return w;
-}
-
-bool hyst_shape_fits(int64_t n_win, int64_t ntime, int64_t nchan, int64_t n_chunk_ends) {
-    return ntime < (1ll << 31) && nchan < (1ll << 31) && n_chunk_ends <= (1ll << 30) &&
-           n_win <= (INT64_MAX / 64 / ntime) / std::max(nchan, n_chunk_ends);
-}
-
-// shape limits of the entry points; 0 when the shape is fine
-int hyst_check_shape(int64_t n_win, int64_t ntime, int64_t nchan, int64_t n_chunk_ends) {
-    if (!hyst_shape_fits(n_win, ntime, nchan, n_chunk_ends)) return set_err(TRI_EUNSUPPORTED, "window too large");
-    // every launch is one-dimensional and holds fewer than 2^31 blocks
-    const int64_t lim = (1ll << 31) - 1;
-    const int64_t nchunk = n_chunk_ends - 1;
-    if (n_win > lim / cdiv(nchan, HYST_LC) || cdiv(n_win * ntime * nchunk, HYST_LW) > lim ||
-        n_win > lim / (cdiv(ntime, HYST_ER) * cdiv(nchan, HYST_NT)) ||
-        n_win > lim / (cdiv(ntime, HYST_GR) * cdiv(cdiv(nchan, 32), HYST_GW)))
-        return set_err(TRI_EUNSUPPORTED, "too many lines for one launch: pass fewer windows per call");
-    return 0;
-}
-
-// the host's chunk ends; 0 when they are fine
-int hyst_check_chunks(int64_t nchan, const int64_t* chunk_ends, int64_t n_chunk_ends) {
-    if (!chunk_ends) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_chunk_ends < 2 || n_chunk_ends > (1ll << 30)) return set_err(TRI_EINVAL, "freq_chunks must be >= 1");
-    if (chunk_ends[0] != 0 || chunk_ends[n_chunk_ends - 1] != nchan)
-        return set_err(TRI_EINVAL, "freq chunk ends must start at 0 and end at the channel count");
-    for (int64_t g = 1; g < n_chunk_ends; g++)
-        if (chunk_ends[g] < chunk_ends[g - 1]) return set_err(TRI_EINVAL, "freq chunk ends must not decrease");
-    return 0;
-}
-
-int hyst_check_nsigma(double nsigma_time, double nsigma_freq) {
-    if (!(nsigma_time >= 0.0) || !(nsigma_freq >= 0.0)) return set_err(TRI_EINVAL, "nsigma must be >= 0");
-    return 0;
-}
-
-int hyst_check_workspace(void* workspace, size_t workspace_bytes, int64_t n_win, int64_t ntime, int64_t nchan,
-                         int64_t n_chunk_ends) {
-    const size_t need = hyst_carve(nullptr, n_win, ntime, nchan, n_chunk_ends).bytes;
-    if (!workspace || workspace_bytes < need)
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    return 0;
-}
-
-bool hyst_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-
-// med and mad of the lines of one axis (time: axis 0); `ends` on the device
-int hyst_levels(hipStream_t st, int axis, const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_win,
-                int64_t ntime, int64_t nchan, const int64_t* ends, int64_t nchunk, float* med, float* mad) {
-    const bool c64 = vis_dtype == TRI_VIS_C64;
-    if (axis == 0) {
-        const dim3 grid((unsigned)(n_win * cdiv(nchan, HYST_LC)));
-        if (c64)
-            hipLaunchKernelGGL((k_hyst_level<TRI_VIS_C64, 0>), grid, dim3(HYST_NT), 0, st, vis, flags, n_win, ntime, nchan,
-                               ends, (int)nchunk, med, mad);
-        else
-            hipLaunchKernelGGL((k_hyst_level<TRI_VIS_F32, 0>), grid, dim3(HYST_NT), 0, st, vis, flags, n_win, ntime, nchan,
-                               ends, (int)nchunk, med, mad);
-    } else {
-        const dim3 grid((unsigned)cdiv(n_win * ntime * nchunk, HYST_LW));
-        if (c64)
-            hipLaunchKernelGGL((k_hyst_level<TRI_VIS_C64, 1>), grid, dim3(HYST_NT), 0, st, vis, flags, n_win, ntime, nchan,
-                               ends, (int)nchunk, med, mad);
-        else
-            hipLaunchKernelGGL((k_hyst_level<TRI_VIS_F32, 1>), grid, dim3(HYST_NT), 0, st, vis, flags, n_win, ntime, nchan,
-                               ends, (int)nchunk, med, mad);
-    }
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// levels of the axes that are on, then the planes and / or the byte images
-int hyst_eligible(hipStream_t st, const void* vis, int vis_dtype, const uint8_t* flags, const uint8_t* missing,
-                  int64_t n_win, int64_t ntime, int64_t nchan, double nsigma_time, double nsigma_freq,
-                  const int64_t* chunk_ends, int64_t n_chunk_ends, const HystWs& w, bool planes, uint8_t* b_et,
-                  uint8_t* b_ef) {
-    const int64_t nchunk = n_chunk_ends - 1;
-    // (pageable host memory: the copy is staged before the call returns, so the caller's array may go)
-    HIPCHK(hipMemcpyAsync(w.ends, chunk_ends, (size_t)n_chunk_ends * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (nsigma_time > 0.0)
-        if (int rc = hyst_levels(st, 0, vis, vis_dtype, flags, n_win, ntime, nchan, w.ends, nchunk, w.med_t, w.mad_t)) return rc;
-    if (nsigma_freq > 0.0)
-        if (int rc = hyst_levels(st, 1, vis, vis_dtype, flags, n_win, ntime, nchan, w.ends, nchunk, w.med_f, w.mad_f)) return rc;
-    const int nstrip = (int)cdiv(nchan, HYST_NT), ntiles = (int)cdiv(ntime, HYST_ER), nw = (int)cdiv(nchan, 32);
-    const dim3 grid((unsigned)(n_win * ntiles * nstrip));
-    const double scale_t = nsigma_time * TRI_MAD_NORMAL, scale_f = nsigma_freq * TRI_MAD_NORMAL;
-    unsigned *ps = planes ? w.seed : nullptr, *pt = planes ? w.et : nullptr, *pf = planes ? w.ef : nullptr;
-    if (vis_dtype == TRI_VIS_C64)
-        hipLaunchKernelGGL((k_hyst_eligible<TRI_VIS_C64>), grid, dim3(HYST_NT), 0, st, vis, flags, missing, ntime, nchan,
-                           nstrip, ntiles, (const int64_t*)w.ends, (int)nchunk, scale_t, scale_f, (const float*)w.med_t,
-                           (const float*)w.mad_t, (const float*)w.med_f, (const float*)w.mad_f, nw, ps, pt, pf, b_et, b_ef);
-    else
-        hipLaunchKernelGGL((k_hyst_eligible<TRI_VIS_F32>), grid, dim3(HYST_NT), 0, st, vis, flags, missing, ntime, nchan,
-                           nstrip, ntiles, (const int64_t*)w.ends, (int)nchunk, scale_t, scale_f, (const float*)w.med_t,
-                           (const float*)w.mad_t, (const float*)w.med_f, (const float*)w.mad_f, nw, ps, pt, pf, b_et, b_ef);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// out = (base != 0) | G_reach from the planes of the workspace
-int hyst_grow(hipStream_t st, const HystWs& w, const uint8_t* base, uint8_t* out, int64_t n_win, int64_t ntime,
-              int64_t nchan, int reach) {
-    const int nw = (int)cdiv(nchan, 32), ntr = (int)cdiv(ntime, HYST_GR), ntw = (int)cdiv(nw, HYST_GW);
-    const dim3 grid((unsigned)(n_win * ntr * ntw));
-    if (nchan % 16 == 0 && (uintptr_t)base % 16 == 0 && (uintptr_t)out % 16 == 0)
-        hipLaunchKernelGGL(k_hyst_grow<true>, grid, dim3(HYST_NT), 0, st, (const unsigned*)w.seed, (const unsigned*)w.et,
-                           (const unsigned*)w.ef, base, out, ntime, nchan, nw, ntr, ntw, reach);
-    else
-        hipLaunchKernelGGL(k_hyst_grow<false>, grid, dim3(HYST_NT), 0, st, (const unsigned*)w.seed, (const unsigned*)w.et,
-                           (const unsigned*)w.ef, base, out, ntime, nchan, nw, ntr, ntw, reach);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-}  // namespace
-
-extern "C" size_t tri_hyst_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan, int64_t n_chunk_ends) {
-    if (n_win <= 0 || ntime <= 0 || nchan <= 0 || n_chunk_ends < 2) return 0;
-    if (!hyst_shape_fits(n_win, ntime, nchan, n_chunk_ends)) return 0;
-    return hyst_carve(nullptr, n_win, ntime, nchan, n_chunk_ends).bytes;
-}
-
-extern "C" int tri_hyst_levels(const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_win, int64_t ntime,
-                               int64_t nchan, const int64_t* chunk_ends, int64_t n_chunk_ends, float* med_time,
-                               float* mad_time, float* med_freq, float* mad_freq, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-    if (!vis || !flags || !med_time || !mad_time || !med_freq || !mad_freq)
-        return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (int rc = hyst_check_chunks(nchan, chunk_ends, n_chunk_ends)) return rc;
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = hyst_check_shape(n_win, ntime, nchan, n_chunk_ends)) return rc;
-    if (int rc = hyst_check_workspace(workspace, workspace_bytes, n_win, ntime, nchan, n_chunk_ends)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const HystWs w = hyst_carve(workspace, n_win, ntime, nchan, n_chunk_ends);
-    HIPCHK(hipMemcpyAsync(w.ends, chunk_ends, (size_t)n_chunk_ends * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (int rc = hyst_levels(st, 0, vis, vis_dtype, flags, n_win, ntime, nchan, w.ends, n_chunk_ends - 1, med_time, mad_time)) return rc;
-    return hyst_levels(st, 1, vis, vis_dtype, flags, n_win, ntime, nchan, w.ends, n_chunk_ends - 1, med_freq, mad_freq);
-}
-
-extern "C" int tri_hyst_eligible(const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_win, int64_t ntime,
-                                 int64_t nchan, double nsigma_time, double nsigma_freq, const int64_t* chunk_ends,
-                                 int64_t n_chunk_ends, uint8_t* e_time, uint8_t* e_freq, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    if (!vis || !flags || !e_time || !e_freq) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (int rc = hyst_check_nsigma(nsigma_time, nsigma_freq)) return rc;
-    if (int rc = hyst_check_chunks(nchan, chunk_ends, n_chunk_ends)) return rc;
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = hyst_check_shape(n_win, ntime, nchan, n_chunk_ends)) return rc;
-    const size_t N = (size_t)n_win * ntime * nchan;
-    if (hyst_overlap(e_time, N, flags, N) || hyst_overlap(e_freq, N, flags, N) || hyst_overlap(e_time, N, e_freq, N))
-        return set_err(TRI_EINVAL, "e_time and e_freq must not overlap flags or each other");
-    if (int rc = hyst_check_workspace(workspace, workspace_bytes, n_win, ntime, nchan, n_chunk_ends)) return rc;
-    const HystWs w = hyst_carve(workspace, n_win, ntime, nchan, n_chunk_ends);
-    return hyst_eligible((hipStream_t)stream, vis, vis_dtype, flags, nullptr, n_win, ntime, nchan, nsigma_time,
-                         nsigma_freq, chunk_ends, n_chunk_ends, w, false, e_time, e_freq);
-}
-
-extern "C" int tri_hyst_grow(const uint8_t* seeds, const uint8_t* e_time, const uint8_t* e_freq, uint8_t* out,
-                             int64_t n_win, int64_t ntime, int64_t nchan, int64_t reach, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    if (!seeds || !e_time || !e_freq || !out) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (reach < 1 || reach > HYST_MAXREACH)
-        return set_err(TRI_EINVAL, "reach must be an integer in [1, %d], got %lld", HYST_MAXREACH, (long long)reach);
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = hyst_check_shape(n_win, ntime, nchan, 2)) return rc;
-    const size_t N = (size_t)n_win * ntime * nchan;
-    if (hyst_overlap(out, N, seeds, N) || hyst_overlap(out, N, e_time, N) || hyst_overlap(out, N, e_freq, N))
-        return set_err(TRI_EINVAL, "out must not overlap an input");
-    if (int rc = hyst_check_workspace(workspace, workspace_bytes, n_win, ntime, nchan, 2)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const HystWs w = hyst_carve(workspace, n_win, ntime, nchan, 2);
-    const int nstrip = (int)cdiv(nchan, HYST_NT), ntiles = (int)cdiv(ntime, HYST_ER), nw = (int)cdiv(nchan, 32);
-    hipLaunchKernelGGL(k_hyst_pack, dim3((unsigned)(n_win * ntiles * nstrip)), dim3(HYST_NT), 0, st, seeds, e_time, e_freq,
-                       ntime, nchan, nstrip, ntiles, nw, w.seed, w.et, w.ef);
-    LAUNCHCHK();
-    return hyst_grow(st, w, seeds, out, n_win, ntime, nchan, (int)reach);
-}
-
-extern "C" int tri_hysteresis_growth(const void* vis, int vis_dtype, const uint8_t* flags, const uint8_t* missing,
-                                     uint8_t* out_flags, int64_t n_win, int64_t ntime, int64_t nchan,
-                                     double nsigma_time, double nsigma_freq, int64_t reach, const int64_t* chunk_ends,
-                                     int64_t n_chunk_ends, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!vis || !flags || !out_flags) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_win < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (int rc = hyst_check_nsigma(nsigma_time, nsigma_freq)) return rc;
-    if (reach < 1 || reach > HYST_MAXREACH)
-        return set_err(TRI_EINVAL, "reach must be an integer in [1, %d], got %lld", HYST_MAXREACH, (long long)reach);
-    if (int rc = hyst_check_chunks(nchan, chunk_ends, n_chunk_ends)) return rc;
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EUNSUPPORTED, "vis dtype must be complex64 or float32");
-    if (n_win == 0 || ntime == 0 || nchan == 0) return TRI_OK;
-    if (int rc = hyst_check_shape(n_win, ntime, nchan, n_chunk_ends)) return rc;
-    const size_t N = (size_t)n_win * ntime * nchan;
-    if (hyst_overlap(out_flags, N, flags, N) || (missing && hyst_overlap(out_flags, N, missing, N)))
-        return set_err(TRI_EINVAL, "out_flags must not overlap flags or missing");
-    if (int rc = hyst_check_workspace(workspace, workspace_bytes, n_win, ntime, nchan, n_chunk_ends)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const HystWs w = hyst_carve(workspace, n_win, ntime, nchan, n_chunk_ends);
-    if (int rc = hyst_eligible(st, vis, vis_dtype, flags, missing, n_win, ntime, nchan, nsigma_time, nsigma_freq,
-                               chunk_ends, n_chunk_ends, w, true, nullptr, nullptr)) return rc;
-    return hyst_grow(st, w, flags, out_flags, n_win, ntime, nchan, (int)reach);
-}
-
-// ---------------------------------------------------------------------------
-// quality statistics of the unflagged samples (steps/quality/kernels_quality.hpp)
-// ---------------------------------------------------------------------------
-// One route per dtype, by divisibility and alignment alone: the walk loads 16 bytes per lane when nchan % QUAL_V == 0 and
-// the bases allow it.  It changes no result.
-namespace {
-struct QualWs {
-    QualRow* rows;              // (n_win, nstrips, ntime)
-    long long *ccnt, *tcnt;     // (n_win, 2, nchan), (n_win, 2, ntime)
-    double *csum, *tsum;        // (n_win, 4, nchan), (n_win, 4, ntime)
-    size_t bytes;
-};
-
-QualWs qual_carve(void* ws, int64_t n_win, int64_t ntime, int64_t nchan) {
-    QualWs w;
-    const size_t nstrips = (size_t)cdiv(nchan, QUAL_SW);
-    Bump b(ws, SIZE_MAX, ws == nullptr);
-    w.rows = b.get<QualRow>((size_t)n_win * nstrips * (size_t)ntime);
-    w.ccnt = b.get<long long>((size_t)n_win * 2 * (size_t)nchan);
-    w.tcnt = b.get<long long>((size_t)n_win * 2 * (size_t)ntime);
-    w.csum = b.get<double>((size_t)n_win * 4 * (size_t)nchan);
-    w.tsum = b.get<double>((size_t)n_win * 4 * (size_t)ntime);
-    w.bytes = b.off;
-    return w;
-}
-
-// every launch is one-dimensional and holds fewer than 2^31 blocks; every index fits 63 bits
-bool qual_shape_fits(int64_t n_bl, int64_t n_corr, int64_t ntime, int64_t nchan) {
-    const int64_t lim = (1ll << 31) - 1;
-    if (ntime > lim || nchan > lim - QUAL_SW || n_corr > lim || n_bl > lim) return false;
-    const int64_t n_win = n_bl * n_corr;
-    if (n_win > lim) return false;
-    const int64_t ngroups = cdiv(cdiv(nchan, QUAL_SW), QUAL_WPB);
-    if (n_win > lim / ngroups) return false;
-    if (n_corr > lim * QUAL_NT / 6 / std::max(ntime, nchan)) return false;
-    return n_win <= (INT64_MAX / 64 / ntime) / nchan;
-}
-
-bool qual_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    return na > 0 && nb > 0 && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-}  // namespace
-
-extern "C" size_t tri_quality_workspace_bytes(int64_t n_bl, int64_t n_corr, int64_t ntime, int64_t nchan) {
-    if (n_bl <= 0 || n_corr <= 0 || ntime <= 0 || nchan <= 0) return 0;
-    if (!qual_shape_fits(n_bl, n_corr, ntime, nchan)) return 0;
-    return qual_carve(nullptr, n_bl * n_corr, ntime, nchan).bytes;
-}
-
-extern "C" int tri_window_quality(const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_bl, int64_t n_corr,
-                                  int64_t ntime, int64_t nchan, int64_t* counts_bl, double* sums_bl,
-                                  int64_t* counts_time, double* sums_time, int64_t* counts_chan, double* sums_chan,
-                                  int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!vis || !flags || !counts_bl || !sums_bl || !counts_time || !sums_time || !counts_chan || !sums_chan)
-        return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_bl < 0 || n_corr < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EINVAL, "vis dtype must be complex64 or float32");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t lim = (1ll << 31) - 1;
-    if (n_bl == 0 || n_corr == 0 || ntime == 0 || nchan == 0) {
-        // no sample: the bl cells are zeros, the others are zeros or stay
-        if (n_bl > lim || n_corr > lim || ntime > lim || nchan > lim) return set_err(TRI_EUNSUPPORTED, "window too large");
-        const size_t nb = (size_t)(n_bl * n_corr), nt = (size_t)(n_corr * ntime), nc = (size_t)(n_corr * nchan);
-        if (nb) {
-            HIPCHK(hipMemsetAsync(counts_bl, 0, 2 * nb * sizeof(int64_t), st));
-            HIPCHK(hipMemsetAsync(sums_bl, 0, 4 * nb * sizeof(double), st));
-        }
-        if (!accumulate && nt) {
-            HIPCHK(hipMemsetAsync(counts_time, 0, 2 * nt * sizeof(int64_t), st));
-            HIPCHK(hipMemsetAsync(sums_time, 0, 4 * nt * sizeof(double), st));
-        }
-        if (!accumulate && nc) {
-            HIPCHK(hipMemsetAsync(counts_chan, 0, 2 * nc * sizeof(int64_t), st));
-            HIPCHK(hipMemsetAsync(sums_chan, 0, 4 * nc * sizeof(double), st));
-        }
-        return TRI_OK;
-    }
-    if (!qual_shape_fits(n_bl, n_corr, ntime, nchan))
-        return set_err(TRI_EUNSUPPORTED, "window too large for one launch: pass fewer baselines per call");
-    const int64_t n_win = n_bl * n_corr;
-    {
-        const size_t N = (size_t)n_win * ntime * nchan;
-        const void* p[8] = {vis, flags, counts_bl, sums_bl, counts_time, sums_time, counts_chan, sums_chan};
-        const size_t nb[8] = {N * (vis_dtype == TRI_VIS_C64 ? 8 : 4), N, (size_t)n_win * 16, (size_t)n_win * 32,
-                              (size_t)(n_corr * ntime) * 16, (size_t)(n_corr * ntime) * 32,
-                              (size_t)(n_corr * nchan) * 16, (size_t)(n_corr * nchan) * 32};
-        for (int a = 2; a < 8; a++)
-            for (int b = 0; b < a; b++)
-                if (qual_overlap(p[a], nb[a], p[b], nb[b]))
-                    return set_err(TRI_EINVAL, "outputs must not overlap the inputs or each other");
-    }
-    const QualWs w = qual_carve(workspace, n_win, ntime, nchan);
-    if (!workspace || workspace_bytes < w.bytes)
-        return set_err(TRI_EWORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, w.bytes);
-
-    const int nstrips = (int)cdiv(nchan, QUAL_SW), ngroups = (int)cdiv(nstrips, QUAL_WPB);
-    const dim3 grid((unsigned)(n_win * ngroups));
-    const bool c64 = vis_dtype == TRI_VIS_C64;
-    const bool vec = nchan % QUAL_V == 0 && (uintptr_t)vis % 16 == 0 && (uintptr_t)flags % 4 == 0;
-    if (c64 && vec)
-        hipLaunchKernelGGL((k_quality_walk<TRI_VIS_C64, true>), grid, dim3(QUAL_NT), 0, st, vis, flags, ntime, nchan, nstrips,
-                           ngroups, w.rows, w.ccnt, w.csum);
-    else if (c64)
-        hipLaunchKernelGGL((k_quality_walk<TRI_VIS_C64, false>), grid, dim3(QUAL_NT), 0, st, vis, flags, ntime, nchan, nstrips,
-                           ngroups, w.rows, w.ccnt, w.csum);
-    else if (vec)
-        hipLaunchKernelGGL((k_quality_walk<TRI_VIS_F32, true>), grid, dim3(QUAL_NT), 0, st, vis, flags, ntime, nchan, nstrips,
-                           ngroups, w.rows, w.ccnt, w.csum);
-    else
-        hipLaunchKernelGGL((k_quality_walk<TRI_VIS_F32, false>), grid, dim3(QUAL_NT), 0, st, vis, flags, ntime, nchan, nstrips,
-                           ngroups, w.rows, w.ccnt, w.csum);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(k_quality_window, dim3((unsigned)n_win), dim3(QUAL_NT), 0, st, (const QualRow*)w.rows, n_win, ntime,
-                       nstrips, w.tcnt, w.tsum, (long long*)counts_bl, sums_bl);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(k_quality_fold, dim3((unsigned)cdiv(6 * n_corr * ntime, QUAL_NT)), dim3(QUAL_NT), 0, st,
-                       (const long long*)w.tcnt, (const double*)w.tsum, n_bl, n_corr, ntime, (long long*)counts_time,
-                       sums_time, accumulate);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(k_quality_fold, dim3((unsigned)cdiv(6 * n_corr * nchan, QUAL_NT)), dim3(QUAL_NT), 0, st,
-                       (const long long*)w.ccnt, (const double*)w.csum, n_bl, n_corr, nchan, (long long*)counts_chan,
-                       sums_chan, accumulate);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// ---------------------------------------------------------------------------
-// log-binned amplitude histograms of the kept and the flagged samples (steps/hist/kernels_hist.hpp)
-// ---------------------------------------------------------------------------
-// One route per dtype, by divisibility and alignment alone (16-byte loads when nchan % HIST_V == 0 and the bases allow
-// it).  It changes no result.  No workspace: the chunk ends travel as kernel arguments, HIST_CPL chunks per launch.
-namespace {
-template <int VIS, bool VEC>
-void hist_launch(hipStream_t st, dim3 grid, size_t lds, const void* vis, const uint8_t* flags, int64_t ntime, int64_t nchan,
-                 int n_corr, int nbands, int64_t nchunks, const HistChunks& ch, int ebase, int shift, int nb,
-                 int64_t* hist_bl, int64_t* hist_chunk) {
-    hipLaunchKernelGGL((k_hist_fill<VIS, VEC>), grid, dim3(HIST_NT), lds, st, vis, flags, ntime, nchan, n_corr, nbands, nchunks,
-                       ch, ebase, shift, nb, (unsigned long long*)hist_bl, (unsigned long long*)hist_chunk);
-}
-}  // namespace
-
-extern "C" int64_t tri_histogram_slots(int emin, int emax, int sub_bits) {
-    if (emin < -126 || emax > 128 || emin >= emax || sub_bits < 0 || sub_bits > 5) return 0;
-    const int64_t nb = (int64_t)(emax - emin) << sub_bits;
-    return nb <= TRI_MAX_HIST_BINS ? nb + 3 : 0;
-}
-
-extern "C" int tri_amplitude_histogram(const void* vis, int vis_dtype, const uint8_t* flags, int64_t n_bl, int64_t n_corr,
-                                       int64_t ntime, int64_t nchan, const int64_t* chunk_ends, int64_t n_chunk_ends,
-                                       int emin, int emax, int sub_bits, int64_t* hist_bl, int64_t* hist_chunk,
-                                       int accumulate, void* stream) {
-    if (!vis || !flags || !chunk_ends || !hist_bl || !hist_chunk) return set_err(TRI_EINVAL, "NULL pointer argument");
-    if (n_bl < 0 || n_corr < 0 || ntime < 0 || nchan < 0) return set_err(TRI_EINVAL, "bad shape");
-    if (vis_dtype != TRI_VIS_C64 && vis_dtype != TRI_VIS_F32)
-        return set_err(TRI_EINVAL, "vis dtype must be complex64 or float32");
-    const int64_t slots = tri_histogram_slots(emin, emax, sub_bits);
-    if (slots == 0)
-        return set_err(TRI_EINVAL, "bins must have -126 <= emin < emax <= 128, 0 <= sub_bits <= 5 and at most %d bins",
-                       TRI_MAX_HIST_BINS);
-    if (n_chunk_ends < 2) return set_err(TRI_EINVAL, "freq_chunks must be >= 1");
-    if (n_chunk_ends > (1ll << 30)) return set_err(TRI_EUNSUPPORTED, "at most 2^30 chunk ends");
-    if (chunk_ends[0] != 0 || chunk_ends[n_chunk_ends - 1] != nchan)
-        return set_err(TRI_EINVAL, "freq chunk ends must start at 0 and end at the channel count");
-    int64_t widest = 0;
-    for (int64_t g = 1; g < n_chunk_ends; g++) {
-        if (chunk_ends[g] < chunk_ends[g - 1]) return set_err(TRI_EINVAL, "freq chunk ends must not decrease");
-        widest = std::max(widest, chunk_ends[g] - chunk_ends[g - 1]);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t lim = (1ll << 31) - 1, nchunks = n_chunk_ends - 1, cells = 2 * slots;
-    if (n_bl > lim || n_corr > lim || ntime > lim || nchan > lim || n_bl * n_corr > lim ||
-        n_corr > (INT64_MAX / 64 / cells) / nchunks)
-        return set_err(TRI_EUNSUPPORTED, "window too large");
-    const int64_t n_win = n_bl * n_corr;
-    const size_t bytes_bl = (size_t)(n_win * cells) * sizeof(int64_t);
-    const size_t bytes_chunk = (size_t)(n_corr * nchunks * cells) * sizeof(int64_t);
-    if (n_win == 0 || ntime == 0 || nchan == 0) {
-        // no sample: the bl cells are zeros, the chunk cells are zeros or stay
-        if (bytes_bl) HIPCHK(hipMemsetAsync(hist_bl, 0, bytes_bl, st));
-        if (!accumulate && bytes_chunk) HIPCHK(hipMemsetAsync(hist_chunk, 0, bytes_chunk, st));
-        return TRI_OK;
-    }
-    const int64_t nbands = cdiv(ntime, HIST_ROWS);
-    if (n_win > HIST_MAX_GRID_X / nbands)
-        return set_err(TRI_EUNSUPPORTED, "window too large for one launch: pass fewer baselines per call");
-    if (cdiv(widest, HIST_SPAN) > 65535) return set_err(TRI_EUNSUPPORTED, "a frequency chunk is too wide");
-    if (n_win > (INT64_MAX / 64 / ntime) / nchan) return set_err(TRI_EUNSUPPORTED, "window too large");
-    {
-        const size_t N = (size_t)n_win * ntime * nchan;
-        const void* p[4] = {vis, flags, hist_bl, hist_chunk};
-        const size_t nby[4] = {N * (vis_dtype == TRI_VIS_C64 ? 8 : 4), N, bytes_bl, bytes_chunk};
-        for (int a = 2; a < 4; a++)
-            for (int b = 0; b < a; b++)
-                if (qual_overlap(p[a], nby[a], p[b], nby[b]))
-                    return set_err(TRI_EINVAL, "outputs must not overlap the inputs or each other");
-    }
-    HIPCHK(hipMemsetAsync(hist_bl, 0, bytes_bl, st));
-    if (!accumulate) HIPCHK(hipMemsetAsync(hist_chunk, 0, bytes_chunk, st));
-
-    const int nb = (int)slots - 3, ebase = (emin + 127) << sub_bits, shift = 23 - sub_bits;
-    const size_t lds = (size_t)cells * sizeof(unsigned);
-    const bool c64 = vis_dtype == TRI_VIS_C64;
-    const bool vec = nchan % HIST_V == 0 && (uintptr_t)vis % 16 == 0 && (uintptr_t)flags % 4 == 0;
-    for (int64_t g0 = 0; g0 < nchunks; g0 += HIST_CPL) {
-        HistChunks ch;
-        const int n = (int)std::min<int64_t>(HIST_CPL, nchunks - g0);
-        int64_t wide = 0;
-        for (int j = 0; j < HIST_CPL; j++) {
-            const int64_t g = g0 + (j < n ? j : 0);             // the unused rows repeat the first: never indexed
-            ch.lo[j] = (int)chunk_ends[g];
-            ch.hi[j] = (int)chunk_ends[g + 1];
-            ch.idx[j] = (int)g;
-            if (j < n) wide = std::max(wide, chunk_ends[g + 1] - chunk_ends[g]);
-        }
-        if (wide == 0) continue;                                // nothing but empty chunks
-        const dim3 grid((unsigned)(n_win * nbands), (unsigned)n, (unsigned)cdiv(wide, HIST_SPAN));
-        if (c64 && vec)
-            hist_launch<TRI_VIS_C64, true>(st, grid, lds, vis, flags, ntime, nchan, (int)n_corr, (int)nbands, nchunks, ch,
-                                           ebase, shift, nb, hist_bl, hist_chunk);
-        else if (c64)
-            hist_launch<TRI_VIS_C64, false>(st, grid, lds, vis, flags, ntime, nchan, (int)n_corr, (int)nbands, nchunks, ch,
-                                            ebase, shift, nb, hist_bl, hist_chunk);
-        else if (vec)
-            hist_launch<TRI_VIS_F32, true>(st, grid, lds, vis, flags, ntime, nchan, (int)n_corr, (int)nbands, nchunks, ch,
-                                           ebase, shift, nb, hist_bl, hist_chunk);
-        else
-            hist_launch<TRI_VIS_F32, false>(st, grid, lds, vis, flags, ntime, nchan, (int)n_corr, (int)nbands, nchunks, ch,
-                                            ebase, shift, nb, hist_bl, hist_chunk);
-        LAUNCHCHK();
-    }
-    return TRI_OK;
-}
+#include "steps/step_host.hpp"
+#include "steps/sir/sir_host.hpp"
+#include "steps/linerms/linerms_host.hpp"
+#include "steps/blint_host.hpp"
+#include "steps/ldev/ldev_host.hpp"
+#include "steps/ins/ins_host.hpp"
+#include "steps/hyst/hyst_host.hpp"
+#include "steps/quality/quality_host.hpp"
+#include "steps/hist/hist_host.hpp"
