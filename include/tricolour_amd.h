@@ -789,6 +789,69 @@ int tri_amplitude_histogram(const void *vis, int vis_dtype, const uint8_t *flags
                             int emin, int emax, int sub_bits,
                             int64_t *hist_bl, int64_t *hist_chunk, int accumulate, void *stream);
 
+/*
+ * Sliding 2-D median background of (n_win, ntime, nchan) windows and the
+ * thresholding of single samples on the robust z-score against it (beyond the
+ * reference; the model is detrend_medfilt of HERA's xrfi, the definition is
+ * this library's own and identity with xrfi is not claimed: the neighbourhood
+ * is cut at the edges, not reflected, and flagged samples are left out of both
+ * medians).  Every window is treated on its own.  Per window, visibilities v
+ * (complex64, or float32 amplitudes), uint8 flags f (nonzero = flagged), radii
+ * Kt = radius_time, Kf = radius_freq and min_samples:
+ *   a      = the flagger's amplitude: hypotf for complex64, fabsf for float32.
+ *   valid  = f == 0 and a is finite (its bit pattern lies below 0x7F800000).
+ *   W(t,f) = every (t', f') of the window's image with |t' - t| <= Kt and
+ *            |f' - f| <= Kf: cut at the edges, never reflected, never another
+ *            window's sample.
+ *   median of n values x_0 <= ... <= x_{n-1}: x_{(n-1)/2} for odd n,
+ *            (float)(((double)x_{n/2-1} + (double)x_{n/2}) / 2.0) for even n,
+ *            NaN for n < min_samples.
+ *   b(t,f) = the median of the valid a over W(t,f): defined at every sample,
+ *            whether or not the centre is valid.
+ *   r      = a - b, one float32 subtraction without contraction, where the
+ *            centre is valid and b is not NaN; NaN otherwise.
+ *   m(t,f) = the median, by the same rule and min_samples, of fabsf(r) over the
+ *            non-NaN r of W(t,f).
+ *   z      = (float)((double)r / ((double)m * 1.4826)) where r and m are not
+ *            NaN, NaN otherwise; IEEE from there: m == 0 gives NaN for r == 0
+ *            and +-inf otherwise.
+ *   hit    = (double)fabsf(z) > nsigma: a NaN never hits, an infinite z does.
+ *   rounds: g_0 = (f != 0); for k = 1 ... rounds the hits of (v, g_{k-1}) give
+ *            g_k = g_{k-1} | hit_k;  out_flags = g_rounds  (0/1).
+ * Every NaN written is 0x7FC00000.  The medians are exact selections: the same
+ * bits on every run, for every alignment and for every split of the windows
+ * over calls.  Input buffers are never written.
+ * Limits: Kt and Kf in [0, 32], not both 0; area = (2 Kt + 1)(2 Kf + 1) <= 625;
+ * min_samples in [1, area]; nsigma > 0 and not NaN; rounds in [1, 4].
+ * tri_medfilt_background writes b (background) and, unless NULL, r (residual).
+ * tri_medfilt_zscore takes any float32 residual image (every non-NaN value
+ * counts, an infinite one too) and writes z (zscore) and, unless NULL, m
+ * (scale); its outputs must not overlap residual.
+ * tri_median_zscore_threshold runs the rounds.  There is no workspace: residual
+ * and zscore are required (n_win, ntime, nchan) float32 images of the caller's
+ * and are OUTPUTS: on return they hold the last round's r and z, every element
+ * written, whatever they held before.  out_flags doubles as the running flags
+ * g_k.  No output may overlap an input or another output.
+ * TRI_EINVAL for NULL pointers (other than those marked), negative shapes, bad
+ * radii, min_samples, nsigma, rounds and overlaps; TRI_EUNSUPPORTED for vis
+ * dtypes other than complex64 and float32 and for more tiles than one launch
+ * holds (pass fewer windows per call).  Empty shapes return TRI_OK without a
+ * launch.
+ */
+int tri_medfilt_background(const void *vis, int vis_dtype, const uint8_t *flags,
+                           int64_t n_win, int64_t ntime, int64_t nchan,
+                           int64_t radius_time, int64_t radius_freq, int64_t min_samples,
+                           float *background, float *residual /* may be NULL */,
+                           void *stream);
+int tri_medfilt_zscore(const float *residual, int64_t n_win, int64_t ntime, int64_t nchan,
+                       int64_t radius_time, int64_t radius_freq, int64_t min_samples,
+                       float *scale /* may be NULL */, float *zscore, void *stream);
+int tri_median_zscore_threshold(const void *vis, int vis_dtype, const uint8_t *flags,
+                                uint8_t *out_flags, int64_t n_win, int64_t ntime,
+                                int64_t nchan, int64_t radius_time, int64_t radius_freq,
+                                int64_t min_samples, double nsigma, int64_t rounds,
+                                float *residual, float *zscore, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

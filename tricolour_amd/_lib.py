@@ -232,6 +232,13 @@ _SIGNATURES = {
     "tri_amplitude_histogram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p]),
+    "tri_medfilt_background": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                         C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tri_medfilt_zscore": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tri_median_zscore_threshold": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                              C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "tri_last_error": (C.c_char_p, []),
     "tri_version": (C.c_int, []),
     "tri_bench_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

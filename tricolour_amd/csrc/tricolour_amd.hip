@@ -34,6 +34,7 @@
 #include "steps/hyst/kernels_hyst.hpp"
 #include "steps/quality/kernels_quality.hpp"
 #include "steps/hist/kernels_hist.hpp"
+#include "steps/medz/kernels_medz.hpp"
 
 // ===========================================================================
 // host side
@@ -3257,3 +3258,4 @@ extern "C" int tri_uvcontsub_flagger_debug(const void* vis_c64, const uint8_t* f
 #include "steps/hyst/hyst_host.hpp"
 #include "steps/quality/quality_host.hpp"
 #include "steps/hist/hist_host.hpp"
+#include "steps/medz/medz_host.hpp"

@@ -1146,6 +1146,172 @@ def hysteresis_growth(vis, flags, missing=None, nsigma_time=2.5, nsigma_freq=2.5
     return _like_flags(torch, out, flags, from_numpy)
 
 
+MEDZ_MAX_RADIUS = 32        # largest radius of the sliding median
+MEDZ_MAX_AREA = 625         # largest neighbourhood, (2 radius_time + 1) (2 radius_freq + 1)
+MEDZ_MAX_ROUNDS = 4
+
+
+def _medz_int(name, v):
+    """An integer as an int, or None (bools and non-integral floats are not integers)."""
+    try:
+        ok = not isinstance(v, bool) and isinstance(v, (int, np.integer, float)) and float(v) == int(v)
+    except (ValueError, OverflowError):       # NaN, infinity
+        ok = False
+    return int(v) if ok else None
+
+
+def _medz_radii(radius_time, radius_freq, min_samples):
+    kt, kf = _medz_int("radius_time", radius_time), _medz_int("radius_freq", radius_freq)
+    for name, k, given in (("radius_time", kt, radius_time), ("radius_freq", kf, radius_freq)):
+        if k is None or not 0 <= k <= MEDZ_MAX_RADIUS:
+            raise ValueError("%s must be an integer in [0, %d], got %r" % (name, MEDZ_MAX_RADIUS, given))
+    if kt == 0 and kf == 0:
+        raise ValueError("radius_time and radius_freq must not both be 0")
+    area = (2 * kt + 1) * (2 * kf + 1)
+    if area > MEDZ_MAX_AREA:
+        raise ValueError("(2 radius_time + 1) (2 radius_freq + 1) must be at most %d, got %d" % (MEDZ_MAX_AREA, area))
+    if min_samples is None:
+        ms = max(1, (area + 7) // 8)
+    else:
+        ms = _medz_int("min_samples", min_samples)
+        if ms is None or not 1 <= ms <= area:
+            raise ValueError("min_samples must be an integer in [1, %d], got %r" % (area, min_samples))
+    return kt, kf, ms
+
+
+def check_median_zscore_kwargs(nsigma=6.0, radius_time=8, radius_freq=8, min_samples=None, rounds=1):
+    """The argument checks of :func:`threshold_median_zscore` (no device work): a radius that is no integer in
+    [0, 32], both radii 0, a neighbourhood of more than 625 samples, ``min_samples`` outside [1, neighbourhood],
+    ``nsigma`` that is not > 0 and ``rounds`` outside [1, 4] raise ``ValueError``.  Returns the values, ``min_samples``
+    resolved (``None``: an eighth of the neighbourhood, rounded up, at least 1)."""
+    try:
+        ok = float(nsigma) > 0.0              # also rejects NaN
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("nsigma must be > 0, got %r" % (nsigma,))
+    kt, kf, ms = _medz_radii(radius_time, radius_freq, min_samples)
+    r = _medz_int("rounds", rounds)
+    if r is None or not 1 <= r <= MEDZ_MAX_ROUNDS:
+        raise ValueError("rounds must be an integer in [1, %d], got %r" % (MEDZ_MAX_ROUNDS, rounds))
+    return float(nsigma), kt, kf, ms, r
+
+
+def _medz_inputs(name, vis, flags):
+    """Shape and dtype checks (ValueError, before any device work) and device inputs of the median z-score calls."""
+    shape = tuple(vis.shape)
+    if len(shape) != 4:
+        raise ValueError("vis must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    if tuple(flags.shape) != shape:
+        raise ValueError("vis and flags must have the same shape, got %s and %s" % (shape, tuple(flags.shape)))
+    if str(vis.dtype).replace("torch.", "") not in ("complex64", "float32"):
+        raise ValueError("tricolour_amd.%s: visibilities must be complex64 or float32, got %s" % (name, vis.dtype))
+    return _line_rms_inputs(name, vis, flags)
+
+
+def _medz_cap(ntime, nchan):
+    """Windows one launch of the median z-score family holds (every launch is one-dimensional and holds fewer than
+    2^31 blocks: one per tile of 16 rows x 64 channels)."""
+    return ((1 << 31) - 1) // (-(-ntime // 16) * -(-nchan // 64))
+
+
+def _medz_launches(torch, device, n_win, ntime, nchan, max_windows):
+    """The batches of a median z-score call, sized so that two float32 images of a batch (8 bytes per sample: the
+    residual and the z-score) fit the workspace budget, as a list of ``(at, b)``, and the stream."""
+    launches, (_, _, stream) = _window_launches(torch, device, n_win, lambda b: 8 * b * ntime * nchan,
+                                                _medz_cap(ntime, nchan), max_windows, workspace=False)
+    return list(launches), stream
+
+
+def median_filter_background(vis, flags, radius_time=8, radius_freq=8, min_samples=None, _max_windows=None):
+    """Sliding 2-D median background of (bl, corr, time, chan) windows (after
+    ``detrend_medfilt`` of HERA's ``xrfi``; the definition is this library's
+    own): ``background`` is, at EVERY sample, the median amplitude of the
+    unflagged, finite samples within ``radius_time`` rows and ``radius_freq``
+    channels of it, the neighbourhood cut at the window's edges; NaN where
+    fewer than ``min_samples`` count (``None``: an eighth of the neighbourhood).
+    ``residual = amplitude - background`` where the sample itself counts and
+    the background is defined, NaN elsewhere.  A robust bandpass / waterfall:
+    defined under flags too, and one pass, since the median ignores what is not
+    yet flagged.  Definition: ``include/tricolour_amd.h``.  Returns
+    ``(background, residual)``, float32 of the shape of ``vis`` -- numpy arrays
+    for numpy input, tensors on the device otherwise.  Inputs are not
+    modified."""
+    kt, kf, ms = _medz_radii(radius_time, radius_freq, min_samples)
+    torch, v, f8, code, from_numpy, device = _medz_inputs("median_filter_background", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    bg = torch.empty(v.shape, dtype=torch.float32, device=device)
+    res = torch.empty(v.shape, dtype=torch.float32, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            launches, stream = _medz_launches(torch, device, n_win, ntime, nchan, _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_medfilt_background(at(v), code, at(f8), b, ntime, nchan, kt, kf, ms, at(bg), at(res),
+                                                      stream))
+    return _like_input(from_numpy, bg, res)
+
+
+def median_zscore(vis, flags, radius_time=8, radius_freq=8, min_samples=None, _max_windows=None):
+    """Robust (modified) z-score of (bl, corr, time, chan) windows against
+    their sliding median background: with ``residual`` of
+    :func:`median_filter_background`, ``scale`` is the sliding median, over the
+    same neighbourhood and by the same rule, of ``|residual|`` and ``z =
+    residual / (1.4826 * scale)`` in float64, stored as float32; NaN where the
+    residual or the scale is.  Definition: ``include/tricolour_amd.h``.  Returns
+    ``z`` of the shape of ``vis`` -- a numpy array for numpy input, a tensor on
+    the device otherwise.  ``z`` is a float32 image like any other: the steps
+    that take float32 amplitudes accept it.  Inputs are not modified."""
+    kt, kf, ms = _medz_radii(radius_time, radius_freq, min_samples)
+    torch, v, f8, code, from_numpy, device = _medz_inputs("median_zscore", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    z = torch.empty(v.shape, dtype=torch.float32, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            launches, stream = _medz_launches(torch, device, n_win, ntime, nchan, _max_windows)
+            # the residual of one batch at a time; its background passes through the batch's part of z
+            res = torch.empty((launches[0][1], ntime, nchan), dtype=torch.float32, device=device)
+            for at, b in launches:
+                _lib.check(lib.tri_medfilt_background(at(v), code, at(f8), b, ntime, nchan, kt, kf, ms, at(z),
+                                                      res.data_ptr(), stream))
+                _lib.check(lib.tri_medfilt_zscore(res.data_ptr(), b, ntime, nchan, kt, kf, ms, None, at(z), stream))
+    return _like_input(from_numpy, z)[0]
+
+
+def threshold_median_zscore(vis, flags, nsigma=6.0, radius_time=8, radius_freq=8, min_samples=None, rounds=1,
+                            _max_windows=None):
+    """Flags single samples of (bl, corr, time, chan) windows on their robust
+    z-score against a sliding 2-D median background (after ``detrend_medfilt``
+    of HERA's ``xrfi``; the definition is this library's own): a sample is hit
+    when ``|z| > nsigma`` with ``z`` of :func:`median_zscore`.  Background and
+    scale are local -- ``radius_time`` rows and ``radius_freq`` channels around
+    the sample -- and medians, so interference that is not yet flagged does not
+    pull them up and one round does what the linear background needs
+    iterations for.  ``rounds`` > 1 repeats the step on the grown flags:
+    ``g_k = g_{k-1} | hits(vis, g_{k-1})``.  ``out = flags | hits``.
+    Definition: ``include/tricolour_amd.h``.  Returns a new array in the
+    container / dtype of ``flags``; the inputs are not modified."""
+    nsigma, kt, kf, ms, rounds = check_median_zscore_kwargs(nsigma, radius_time, radius_freq, min_samples, rounds)
+    torch, v, f8, code, from_numpy, device = _medz_inputs("threshold_median_zscore", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            launches, stream = _medz_launches(torch, device, n_win, ntime, nchan, _max_windows)
+            # the library's two output images of one batch at a time
+            res = torch.empty((launches[0][1], ntime, nchan), dtype=torch.float32, device=device)
+            z = torch.empty_like(res)
+            for at, b in launches:
+                _lib.check(lib.tri_median_zscore_threshold(at(v), code, at(f8), at(out), b, ntime, nchan, kt, kf, ms,
+                                                           nsigma, rounds, res.data_ptr(), z.data_ptr(), stream))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
 def _bli_inputs(name, vis, flags, select):
     """Checks of the baseline-integration calls (all before any device work), then the device inputs:
     (torch, vis, flags uint8, dtype code, from_numpy, device, select uint8 on the device or None)."""
