@@ -11,7 +11,11 @@
  * Plain pointers and sizes only; no torch / Python types.  All data pointers
  * are DEVICE pointers (HBM resident); `stream` is a hipStream_t (NULL = the
  * null stream).  Functions enqueue work on `stream` and return without
- * synchronising; inputs are never written; outputs and the workspace are
+ * synchronising (tri_sum_threshold_flagger and tri_bench_boxfilter also use
+ * one internal stream per calling thread for launches that are independent of
+ * their neighbours; it is ordered behind `stream` and `stream` behind it by
+ * events, so the caller sees the order of a single stream; TRI_SUBSTREAMS=0
+ * keeps everything on `stream`); inputs are never written; outputs and the workspace are
  * caller-allocated.  Every function returns 0 on success or a TRI_E* code, in
  * which case tri_last_error() (thread-local) describes the failure.  The
  * library is re-entrant: it keeps no mutable global state, so concurrent calls

@@ -398,6 +398,15 @@ struct Debug {
     uint8_t* u8;    // [spec_flags Fa][time_flags TF][freq_flags TF]
 };
 
+// The side lane of a calling thread: two launches that share nothing but read-only inputs go to two streams of equal
+// priority and run side by side.  That pays where two thin stream kernels meet (the write-bound k_boxw beside the read-heavier
+// k_boxt); beside a stage pipeline the pair takes what it took in series.
+struct SideLane {
+    hipStream_t st = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    int device = -1;
+};
+
 struct Run {
     hipStream_t st;
     Plan pl;
@@ -414,7 +423,38 @@ struct Run {
     // flagging.py:858-870), else NULL.  Set once per process_windows() call, beside ampl_cached.
     const uint8_t* data_mask = nullptr;
     size_t data_mask_ws = 0;
+    // one extra stream for a launch that is independent of the next one on st (get_side_lane()), or NULL: single-stream order
+    const SideLane* side = nullptr;
 };
+
+// Which sites fork (compile-time: the runtime switch is TRI_SUBSTREAMS=0, which takes the side lane away altogether)
+#ifndef OVERLAP_TIME_STAGE
+#define OVERLAP_TIME_STAGE 2             // weight image beside data image: 0 = never, 1 = beside k_boxq / k_boxq_deep, 2 = beside k_boxt too
+#endif                                   // (1008-window step, profiles/overlap_ab.txt: 2 saves 15 - 19 ms, 1 nothing -- the gain is at the k_boxt radii)
+#ifndef OVERLAP_RESID_MEDIANS
+#define OVERLAP_RESID_MEDIANS 1          // time medians of the residual beside its transpose (9 - 11 ms; both sites together 23 - 26 ms)
+#endif
+
+// Everything queued on r.st so far happens before what is launched through the returned Run, whose st is the side stream.
+// Without a side lane (or when an event call fails) the returned Run is r itself: the launches stay in order on r.st.
+static Run fork(const Run& r) {
+    Run f = r;
+    f.side = nullptr;
+    if (!r.side) return f;
+    if (hipEventRecord(r.side->fork, r.st) != hipSuccess || hipStreamWaitEvent(r.side->st, r.side->fork, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return f;
+    }
+    f.st = r.side->st;
+    return f;
+}
+// Everything queued on the side stream so far happens before what is launched on r.st from here on.  Called on every way
+// out of a forked region: r.st never runs ahead of queued side work.
+static void join(const Run& r) {
+    if (!r.side) return;
+    (void)hipEventRecord(r.side->join, r.side->st);
+    (void)hipStreamWaitEvent(r.st, r.side->join, 0);
+}
 
 // The register cascade covers windows exactly (1,2,4,8) in that order; the
 // environment variable TRI_ST_GENERIC=1 forces the generic kernel (tests).
@@ -638,6 +678,17 @@ int launch_boxw(const Run& r, const uint8_t* srcFlags, float* dstW, int n, int C
 #undef BOXW_CASE
     return set_err(TRI_EINVAL, "no integer weight filter for radius %d", rad);
 }
+// The weight image through K4w beside the kernel of the data image, which `data` launches on r.st: they read the same flag
+// words and write disjoint images.  overlap: K4w goes to the side lane of r, if it has one; both are done when r.st goes on.
+template <class LaunchData>
+static int launch_boxw_beside(const Run& r, bool overlap, const uint8_t* srcFlags, float* dstW, int n, int C, int rad, float denom,
+                              size_t sws, size_t dws, int64_t W, LaunchData&& data) {
+    const Run side = overlap ? fork(r) : r;
+    const int rc = launch_boxw(side, srcFlags, dstW, n, C, rad, denom, sws, dws, W);
+    if (!rc) data();
+    if (overlap) join(r);
+    return rc;
+}
 
 template <int KS>
 int launch_boxt_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
@@ -648,14 +699,17 @@ int launch_boxt_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, 
     HIPCHK(lds_optin_all(160 * 1024, &k_boxt<KS, true, 0>, &k_boxt<KS, true, 1>));
     // one launch per image: a compute unit then runs (mostly) one of the two long loop bodies at a time
     // (the weight image through the integer kernel K4w where it applies)
-    const bool wk = boxw_usable(rad, n, C);
-    if (wk) { const int rc = launch_boxw(r, srcFlags, dstW, n, C, rad, denom, sws, dws, W); if (rc) return rc; }
-    if (d > 0) {
-        if (!wk) hipLaunchKernelGGL((k_boxt<KS, true, 0>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstW, n, C, rad, denom, sws, dws);
-        hipLaunchKernelGGL((k_boxt<KS, true, 1>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstO, n, C, rad, denom, sws, dws);
+    const auto data_image = [&] {
+        if (d > 0) hipLaunchKernelGGL((k_boxt<KS, true, 1>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstO, n, C, rad, denom, sws, dws);
+        else hipLaunchKernelGGL((k_boxt<KS, false, 1>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstO, n, C, rad, denom, sws, dws);
+    };
+    if (boxw_usable(rad, n, C)) {
+        const int rc = launch_boxw_beside(r, OVERLAP_TIME_STAGE >= 2, srcFlags, dstW, n, C, rad, denom, sws, dws, W, data_image);
+        if (rc) return rc;
     } else {
-        if (!wk) hipLaunchKernelGGL((k_boxt<KS, false, 0>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstW, n, C, rad, denom, sws, dws);
-        hipLaunchKernelGGL((k_boxt<KS, false, 1>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstO, n, C, rad, denom, sws, dws);
+        if (d > 0) hipLaunchKernelGGL((k_boxt<KS, true, 0>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstW, n, C, rad, denom, sws, dws);
+        else hipLaunchKernelGGL((k_boxt<KS, false, 0>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstW, n, C, rad, denom, sws, dws);
+        data_image();
     }
     LAUNCHCHK();
     return TRI_OK;
@@ -728,9 +782,16 @@ int launch_boxq_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, 
     HIPCHK(lds_optin_all(160 * 1024, &k_boxq<KS, 0, B>, &k_boxq<KS, 1, B>));
     dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
     const BoxDenom dn = box_reciprocal(denom);
-    if (boxw_usable(rad, n, C)) { const int rc = launch_boxw(r, srcFlags, dstW, n, C, rad, denom, sws, dws, W); if (rc) return rc; }
-    else hipLaunchKernelGGL((k_boxq<KS, 0, B>), grid, dim3(256), boxq_lds_bytes(B), r.st, srcData, srcFlags, dstW, n, C, rad, dn, sws, dws);
-    hipLaunchKernelGGL((k_boxq<KS, 1, B>), grid, dim3(256), boxq_lds_bytes(B), r.st, srcData, srcFlags, dstO, n, C, rad, dn, sws, dws);
+    const auto data_image = [&] {
+        hipLaunchKernelGGL((k_boxq<KS, 1, B>), grid, dim3(256), boxq_lds_bytes(B), r.st, srcData, srcFlags, dstO, n, C, rad, dn, sws, dws);
+    };
+    if (boxw_usable(rad, n, C)) {
+        const int rc = launch_boxw_beside(r, OVERLAP_TIME_STAGE >= 1, srcFlags, dstW, n, C, rad, denom, sws, dws, W, data_image);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL((k_boxq<KS, 0, B>), grid, dim3(256), boxq_lds_bytes(B), r.st, srcData, srcFlags, dstW, n, C, rad, dn, sws, dws);
+        data_image();
+    }
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -756,9 +817,16 @@ int launch_boxq_deep(const Run& r, const float* srcData, const uint8_t* srcFlags
     HIPCHK(lds_optin_all(160 * 1024, &k_boxq_deep<KS, 0>, &k_boxq_deep<KS, 1>));
     dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
     const BoxDenom dn = box_reciprocal(denom);
-    if (boxw_usable(rad, n, C)) { const int rc = launch_boxw(r, srcFlags, dstW, n, C, rad, denom, sws, dws, W); if (rc) return rc; }
-    else hipLaunchKernelGGL((k_boxq_deep<KS, 0>), grid, dim3(256), boxq_lds_bytes(8, 4), r.st, srcData, srcFlags, dstW, n, C, rad, dn, sws, dws);
-    hipLaunchKernelGGL((k_boxq_deep<KS, 1>), grid, dim3(256), boxq_lds_bytes(8, 4), r.st, srcData, srcFlags, dstO, n, C, rad, dn, sws, dws);
+    const auto data_image = [&] {
+        hipLaunchKernelGGL((k_boxq_deep<KS, 1>), grid, dim3(256), boxq_lds_bytes(8, 4), r.st, srcData, srcFlags, dstO, n, C, rad, dn, sws, dws);
+    };
+    if (boxw_usable(rad, n, C)) {
+        const int rc = launch_boxw_beside(r, OVERLAP_TIME_STAGE >= 1, srcFlags, dstW, n, C, rad, denom, sws, dws, W, data_image);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL((k_boxq_deep<KS, 0>), grid, dim3(256), boxq_lds_bytes(8, 4), r.st, srcData, srcFlags, dstW, n, C, rad, dn, sws, dws);
+        data_image();
+    }
     LAUNCHCHK();
     return TRI_OK;
 }
@@ -1986,16 +2054,32 @@ static int iter_spectrum(const Run& r, const IterStep& s) {
 
 // flagging.py:957-962  2-D background (FT layout, ws.Bo); the residual data - background was written by its final masked
 // division (and redone by the interpolation pass on repaired lines) into ws.Bw, window stride PF * T.  *residTF: the same
-// in the TF layout, window stride N: ws.residP where the final frequency stage wrote the panels itself, else a transpose
-// into ws.Aw (the time-axis scratch is free again).
-static int iter_residual(const Run& r, const IterStep& s, const float** residTF) {
+// in the TF layout, window stride N: ws.residP where the final frequency stage wrote the panels itself, else ws.Aw (the
+// time-axis scratch is free again), which iter_time_inputs() still has to fill (*transpose_pending).
+static int iter_residual(const Run& r, const IterStep& s, const float** residTF, bool* transpose_pending) {
     const Ws& ws = r.ws;
-    const int T = (int)r.pl.T, Fa = (int)r.pl.Fa;
     bool wrote_panel = false;
     const int rc = background2d(r, s.ft_current(), s.fused_resid ? ws.residP : nullptr, &wrote_panel);
     *residTF = wrote_panel ? ws.residP : ws.Aw;
-    if (rc || wrote_panel) return rc;
-    return launch_transpose<float>(r, ws.Bw, ws.Aw, Fa, T, (size_t)r.pl.PF * T, (size_t)T * Fa, r.Wb, 0.0f, s.panel);
+    *transpose_pending = !wrote_panel;
+    return rc;
+}
+
+// What SumThreshold along time reads besides the flags: the residual in the TF layout, and its MAD per channel over time =
+// contiguous rows of the FT layout (flags = input | spectral flags, so the FT flag image is brought up to date first).
+// Transpose and medians only read ws.Bw: where both run, the medians (and the flag transpose ahead of them) take the side lane.
+// Nothing on r.st touches ws.med or ws.flagsFT before the join.
+static int iter_time_inputs(const Run& r, const IterStep& s, bool transpose_pending) {
+    const Ws& ws = r.ws;
+    const int T = (int)r.pl.T, Fa = (int)r.pl.Fa;
+    const size_t N = (size_t)T * Fa, wsB = (size_t)r.pl.PF * T;
+    const bool overlap = OVERLAP_RESID_MEDIANS && transpose_pending;
+    const Run side = overlap ? fork(r) : r;
+    int rc = transpose_pending ? launch_transpose<float>(r, ws.Bw, ws.Aw, Fa, T, wsB, N, r.Wb, 0.0f, s.panel) : TRI_OK;
+    if (!rc && !s.ft_current()) rc = launch_transpose<uint8_t>(side, ws.flagsTF, ws.flagsFT, T, Fa, N, N, r.Wb);
+    if (!rc) rc = time_medians(side, ws.Bw, wsB);
+    if (overlap) join(r);
+    return rc;
 }
 
 // flagging.py:964-969  SumThreshold along time, flags |= time_flags, SumThreshold along frequency
@@ -2005,10 +2089,7 @@ static int iter_sumthreshold(const Run& r, const IterStep& s, const float* resid
     const int T = (int)pl.T, Fa = (int)pl.Fa, G = (int)pl.G;
     const size_t N = (size_t)T * Fa, wsB = (size_t)pl.PF * T;
     const int64_t W = r.Wb;
-    // MAD per channel over time = contiguous rows of the FT layout; flags = input | spectral flags
-    int rc = s.ft_current() ? TRI_OK : launch_transpose<uint8_t>(r, ws.flagsTF, ws.flagsFT, T, Fa, N, N, W);
-    if (!rc) rc = time_medians(r, ws.Bw, wsB);
-    if (!rc) rc = launch_colst(r, pl.swT, residTF, ws.med, ws.tflTF, ws.d_tends, T, Fa, 1, N, N, W, s.panel);
+    int rc = launch_colst(r, pl.swT, residTF, ws.med, ws.tflTF, ws.d_tends, T, Fa, 1, N, N, W, s.panel);
     if (rc) return rc;
     // MAD per (time, chunk) = contiguous row segments of the TF layout; flags = input | spectral | time flags
     MedianJob cj;
@@ -2094,9 +2175,11 @@ static int iter_finish(const Run& r, const IterStep& s, const void* vis, int vis
 // One major iteration (_get_flags_impl, flagging.py:745-781) for a batch: the stages in the order of flagging.py:921-976.
 int run_iteration(const Run& r, const IterStep& s, const void* vis, int vis_dtype, uint8_t* out_flags, bool update_iter, bool tap) {
     const float* residTF = nullptr;
+    bool transpose_pending = false;
     int rc = iter_begin(r, s, vis, vis_dtype);
     if (!rc) rc = iter_spectrum(r, s);
-    if (!rc) rc = iter_residual(r, s, &residTF);
+    if (!rc) rc = iter_residual(r, s, &residTF, &transpose_pending);
+    if (!rc) rc = iter_time_inputs(r, s, transpose_pending);
     if (!rc) rc = iter_sumthreshold(r, s, residTF);
     if (!rc && tap && r.dbg) rc = iter_taps(r, s, residTF);
     if (!rc) rc = iter_finish(r, s, vis, vis_dtype, out_flags, update_iter);
@@ -2206,6 +2289,35 @@ int get_substreams(SubStreams** out) {
     return TRI_OK;
 }
 
+// TRI_SUBSTREAMS=0 / 1 forces the single-stream / two-stream schedule; -1 when unset.  Read per call: tests toggle it
+static int substreams_forced() {
+    const char* fe = getenv("TRI_SUBSTREAMS");
+    return fe ? atoi(fe) : -1;
+}
+
+// The side lane of the calling thread on the current device (created once, owned like the SubStreams), or NULL: under
+// TRI_SUBSTREAMS=0, and when a stream or an event cannot be made -- the caller then keeps the single-stream order.
+thread_local SideLane g_side;
+const SideLane* get_side_lane() {
+    if (substreams_forced() == 0) return nullptr;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (g_side.device == dev) return &g_side;
+    if (g_side.device >= 0) return nullptr;              // (a calling thread stays on one device)
+    HipStream st;
+    HipEvent fork, join;
+    // (a plain stream: the priority a caller's stream has unless it asked for another -- neither kernel of a pair is preferred)
+    const bool ok = hipStreamCreateWithFlags(st.out(), hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(fork.out(), hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(join.out(), hipEventDisableTiming) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); return nullptr; }
+    g_side.st = st.release();
+    g_side.fork = fork.release();
+    g_side.join = join.release();
+    g_side.device = dev;
+    return &g_side;
+}
+
 int flagger_impl(const void* vis, int vis_dtype, const uint8_t* flags, uint8_t* out_flags,
                  int64_t n_cp, int64_t T, int64_t F, const tri_params* p, void* workspace,
                  size_t workspace_bytes, void* stream, Debug* dbg) {
@@ -2229,9 +2341,7 @@ int flagger_impl(const void* vis, int vis_dtype, const uint8_t* flags, uint8_t* 
     if (p->num_major_iterations == 0)
         HIPCHK(hipMemsetAsync(out_flags, 0, (size_t)n_cp * (size_t)T * F, r.st));
 
-    // TRI_SUBSTREAMS=0 / 1 forces the single-stream / two-stream schedule
-    const char* fe = getenv("TRI_SUBSTREAMS");      // read per call: tests toggle it
-    const int force = fe ? atoi(fe) : -1;
+    const int force = substreams_forced();
     Ws probe;
     carve(r.pl, 1, nullptr, 0, true, &probe);
     const size_t half = (workspace_bytes / 2) & ~(size_t)255;
@@ -2240,8 +2350,12 @@ int flagger_impl(const void* vis, int vis_dtype, const uint8_t* flags, uint8_t* 
     //  512 lines per window on the frequency axis -- than the overlap of the spectrum kernels returns:
     //  1.5 against 2.5 Gvis/s, profiles/r02_bench_ska.log)
     const bool want_split = force == 1;
-    if (!(can_split && want_split))
+    if (!(can_split && want_split)) {
+        // one stream for the windows, the side lane for the independent launch pairs inside a major iteration (the halves
+        // of the split below are on internal streams already and get none)
+        r.side = get_side_lane();
         return process_windows(r, vis, vis_dtype, flags, out_flags, 0, n_cp, T, F, workspace, workspace_bytes, true);
+    }
 
     SubStreams* ss = nullptr;
     rc = get_substreams(&ss);
@@ -2747,6 +2861,7 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     r.st = (hipStream_t)stream;
     r.p = nullptr;
     r.dbg = nullptr;
+    r.side = get_side_lane();       // as in the flagger: the time-axis legs time the weight image beside the data image
     HipEvent e0, e1;
     HIPCHK(hipEventCreate(e0.out()));
     HIPCHK(hipEventCreate(e1.out()));
