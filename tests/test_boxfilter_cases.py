@@ -7,12 +7,12 @@ import re
 import pytest
 
 import test_boxfilter_instances_gpu as m
-from test_route_ledger import CSRC
+from test_route_ledger import CSRC, host_text
 
 
 def _hip():
-    with open(os.path.join(CSRC, "tricolour_amd.hip"), encoding="utf-8") as fh:
-        return fh.read()
+    """tricolour_amd.hip with its host files (boxfilter_host.hpp among them) spliced in."""
+    return host_text()
 
 
 def _define(text, name):
@@ -31,7 +31,7 @@ def test_the_copied_limits_are_the_sources():
         assert m.BOXX_AMAX == _define(fh.read(), "BOXX_AMAX")
     # boxr_pick_ks: the radius limit and the largest ring; the spectrum pipeline's limit and its LDS budget
     assert "rad < 4 || rad > %d) return 0;" % m.BOXR_R_MAX in hip and "2 * rad >= 80 ? 80 :" in hip
-    assert "boxp_pick_block(rad, C) > 0 && rad <= %d &&" % m.BOXR_R_MAX in hip
+    assert "boxp_pick_block(b, rad, C) > 0 && rad <= %d &&" % m.BOXR_R_MAX in hip
     assert "boxp_lds_bytes(rad, 16) <= 160 * 1024" in hip and "boxp_lds_bytes(rad, 8) <= 160 * 1024" in hip
     with open(os.path.join(CSRC, "kernels_boxpipe.hpp"), encoding="utf-8") as fh:
         pipe = fh.read()
@@ -40,12 +40,14 @@ def test_the_copied_limits_are_the_sources():
     # byte flags of a medium radius: the LDS kernel up to r = 40, the multi-pass kernel beyond
     assert "bt = rad <= 20 ? 128 : (rad <= 40 ? 64 : 0);" in hip
     # the candidates of the exact row filter, in the order boxx_pick_l tries them, and its rule for the 128-thread ones
-    cands = re.search(r"static const Cand cands\[\] = \{(.*?)\};", hip).group(1)
-    assert [tuple(map(int, c)) for c in re.findall(r"\{(\d+), (\d+)\}", cands)] == m.BOXX_CANDS
-    assert "if (c.nti == 128 && (P <= 128 * 17 || rad < 64)) continue;" in hip
+    cands = re.search(r"using BoxxCodes = Ints<(.*?)>;", hip).group(1)
+    assert [tuple(map(int, c)) for c in re.findall(r"(\d+) << 8 \| (\d+)", cands)] == m.BOXX_CANDS
+    assert len(cands.split(",")) == len(m.BOXX_CANDS)
+    assert "return first_of(BoxxCodes{}, [&](int c) {" in hip and "const int nti = c >> 8, l = c & 255;" in hip
+    assert "if (nti == 128 && (P <= 128 * 17 || rad < 64)) return false;" in hip
     assert "return rad <= 128 || rad == 166 || rad == 221 || rad == 277 || rad == 397 || rad == 795;" in hip
     # the hook refuses the multi-pass family
-    assert "ScopedSet<bool> unpadded(g_colfilter_unpadded, true);" in hip
+    assert "b.unpadded = true;" in hip and "b.unpadded ? ColFamily::MultiPassUnpadded : ColFamily::MultiPass" in hip
     assert (m.ring_r_max(), m.pipe_r_max(16), m.pipe_r_max(8)) == (70, 48, 64)
     assert m.REFUSED == {"time[r=161]"} | {"spectrum[r=%d]" % r for r in (71, 107, 108, 160, 161)}
     assert {107, 108, 160, 161} <= set(m.RADII_TIME) and set(m.RADII_TIME) <= set(m.RADII_SPEC) and m.RADII_FREQ == m.RADII_TIME

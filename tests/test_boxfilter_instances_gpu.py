@@ -1,7 +1,7 @@
 """Every instantiation of the box-filter kernels against the oracle's sequential filter.
 
-The radius alone picks the instantiation (the `switch` statements of launch_boxw, launch_boxt, launch_boxt_spec,
-launch_boxq, launch_boxf, launch_boxx and launch_colfilter), so the sweeps below walk the radii:
+The radius alone picks the instantiation (pick_col_filter, pick_freq_stage and boxx_pick_l of boxfilter_host.hpp, whose
+launchers dispatch over its lists of instantiations), so the sweeps below walk the radii:
 
 hook sweep      tri_bench_boxfilter, stages 0 (time axis, packed flags), 1 (frequency axis fused with the masked division,
                 a non-final iteration: MODE 1) and 2 (spectrum, byte flags), every radius 1 .. 56 and the radii at either

@@ -30,8 +30,8 @@ Row of KERNELS
     dict(test=..., instances=[...], flagger=True)   the symbol-held rows (SYMBOL_KERNELS): the box-filter kernels
              (BOX_KERNELS) and the SumThreshold kernels (ST_KERNELS).  Launched by the flagger -- they count as `flagger`
              kernels for test_route_matrix_gpu.py (is_flagger) -- and listed by instantiation as well.  The box filters
-             are launched from template functions behind the dispatchers' `switch` statements, which the launch-site scan
-             cannot follow, so these rows are held to the symbol table of the built library instead (one weak
+             are launched from template functions behind with_constant() over the lists of boxfilter_host.hpp, which the
+             launch-site scan cannot follow, so these rows are held to the symbol table of the built library instead (one weak
              __device_stub__ symbol per instantiation: test_box_rows_are_the_library_symbols);
              tests/test_boxfilter_instances_gpu.py launches every reachable box-filter instantiation in a call it compares
              with the oracle, tests/test_sumthreshold_kernels_gpu.py every SumThreshold one in calls over chunked lines

@@ -407,7 +407,52 @@ struct SideLane {
     int device = -1;
 };
 
+// The route switches of the box-filter family (boxfilter_host.hpp) as one value.  The flagger runs with from_env();
+// tri_bench_boxfilter builds its own for the variant it was asked for.  The picks are functions of it: nothing else steers them.
+#ifndef BOXQF_B8_DEFAULT
+#define BOXQF_B8_DEFAULT 1               // K4qf: blocks of 8 positions unless TRI_FILTER_PIPE_F_B8=0
+#endif
+enum class Want { Off, Auto, Forced };        // Auto: where the measured crossovers say so; Forced: wherever the shape allows
+enum class SpecPipe { Off, B8, B16, Auto };     // B8 / B16: blocks of that length only
+struct BoxRoutes {
+    bool reg_rings = true, reg_rings_f = true;        // K4r: register delay lines (else the LDS-ring kernels); _f: in the fused frequency stage
+    bool boxw = true;                                 // K4w: the time stage's weight image in integer arithmetic
+    SpecPipe spec_pipe = SpecPipe::Auto;              // K4p: stage pipeline of the spectra
+    Want pipe_t = Want::Auto, pipe_f = Want::Auto;    // K4q / K4qf: stage pipeline of the time stage / of the fused frequency stage ...
+    bool pipe_t_b8 = true, pipe_f_b8 = BOXQF_B8_DEFAULT;         // ... with blocks of 8 positions where they exist
+    Want exact = Want::Auto;                          // K4x: exact rows ...
+    int exact_nti = 0;                                // ... only the instantiations with this many threads per image (128 / 256), 0 = any
+    bool lane4 = true, multipass = false;             // K4c: lane per stage; the in-place multi-pass kernel (K4) for every radius
+    bool t_in = true, fused_div = true;               // frequency stages that read the TF images directly; ... fused with the masked division
+    bool unpadded = false;                            // the images are the caller's, n rows each, without the n + 4r rows K4 works in: it is refused
+
+    // What the environment asks for, read once per process (A/B runs, tests)
+    static const BoxRoutes& from_env() {
+        static const BoxRoutes env = [] {
+            BoxRoutes b;
+            b.reg_rings = !is1(getenv("TRI_FILTER_NO_REGRING"));
+            b.reg_rings_f = !is1(getenv("TRI_FILTER_NO_REGRING_F"));
+            b.boxw = !is1(getenv("TRI_FILTER_NO_BOXW"));
+            b.spec_pipe = is1(getenv("TRI_SPEC_NO_PIPE")) ? SpecPipe::Off : SpecPipe::Auto;
+            b.pipe_t = is1(getenv("TRI_FILTER_NO_PIPE_T")) ? Want::Off : Want::Auto;
+            // (both stages take their register slots from the time stage's pick: without it the frequency stage has no pipeline either)
+            b.pipe_f = (is1(getenv("TRI_FILTER_NO_PIPE_F")) || b.pipe_t == Want::Off) ? Want::Off : Want::Auto;
+            if (const char* e = getenv("TRI_FILTER_PIPE_T_B8")) b.pipe_t_b8 = atoi(e) != 0;
+            if (const char* e = getenv("TRI_FILTER_PIPE_F_B8")) b.pipe_f_b8 = atoi(e) != 0;
+            b.exact = is1(getenv("TRI_FILTER_NO_EXACT")) ? Want::Off : Want::Auto;
+            if (const char* e = getenv("TRI_BOXX_NTI")) b.exact_nti = atoi(e);
+            b.lane4 = !is1(getenv("TRI_FILTER_NO_LANE4"));
+            b.multipass = is1(getenv("TRI_FILTER_MULTIPASS"));
+            b.t_in = !is1(getenv("TRI_FILTER_NO_TIN"));
+            b.fused_div = !is1(getenv("TRI_FILTER_NO_FUSED_DIV"));
+            return b;
+        }();
+        return env;
+    }
+};
+
 struct Run {
+    BoxRoutes box = BoxRoutes::from_env();
     hipStream_t st;
     Plan pl;
     Ws ws;
@@ -585,397 +630,7 @@ int launch_median(const Run& r, MedianJob j) {
     return TRI_OK;
 }
 
-// LDS budget of the single-sweep filter: 4 stages x 2r slots x BT threads x 4 B.
-// Returns the block size to use, or 0 when the radius is too large and the
-// in-place multi-pass kernel must be used instead.
-// Radius limits of the single-sweep kernels.  r <= LDS_R_MAX: K4b with 256
-// threads (4 rings per thread); r <= LANE4_R_MAX: K4c (one ring per thread);
-// beyond: the in-place multi-pass kernel.
-// Measured crossovers (scripts/build_variants.sh -DLDS_R_MAX=.. -DLANE4_R_MAX=..): four rings per thread win
-// up to r = 15 (256 threads to r = 10, 128 beyond; K4c needs 2r >= 32 anyway), one ring per thread up to
-// r = 160 (two waves per CU), the multi-pass kernel beyond.
-#ifndef LDS_R_MAX
-#define LDS_R_MAX 15
-#endif
-#ifndef LANE4_R_MAX
-#define LANE4_R_MAX 160
-#endif
-static bool filter_no_lane4() { static const bool v = is1(getenv("TRI_FILTER_NO_LANE4")); return v; }
-int colfilter_lds_block(int rad, int C) {
-    static const bool disabled = is1(getenv("TRI_FILTER_MULTIPASS"));
-    if (disabled || rad <= 0) return 0;
-    if (filter_no_lane4()) {
-        int bt = rad <= 10 ? 256 : (rad <= 20 ? 128 : (rad <= 40 ? 64 : 0));   // K4b alone (TRI_FILTER_NO_LANE4)
-        while (bt > 64 && bt / 2 >= C) bt /= 2;
-        return bt;
-    }
-    if (rad <= LDS_R_MAX) {
-        int bt = rad <= 10 ? 256 : 128;
-        while (bt > 64 && bt / 2 >= C) bt /= 2;
-        return bt;
-    }
-    return rad <= LANE4_R_MAX ? 64 : 0;
-}
-inline bool colfilter_use_lane4(int rad) { return !filter_no_lane4() && rad > LDS_R_MAX && rad <= LANE4_R_MAX; }
-
-// Register-ring single sweep (K4r, kernels_boxline.hpp): KS register slots per stage, the
-// rest of the 2r-deep delay line in LDS.  Returns 0 when the radius is outside its range.
-// TRI_FILTER_NO_REGRING=1 keeps the LDS-ring kernels (A/B runs, tests).
-#ifndef BOXR_MAX_LDS_SLOTS
-#define BOXR_MAX_LDS_SLOTS 60
-#endif
-thread_local int g_boxr_override = -1;     // measurement hook: 0 = LDS-ring kernels, 1 = register-ring kernels
-int boxr_pick_ks(int rad) {
-    static const bool env_off = is1(getenv("TRI_FILTER_NO_REGRING"));
-    const bool off = g_boxr_override >= 0 ? g_boxr_override == 0 : env_off;
-    if (off || rad < 4 || rad > 107) return 0;
-    const int ks = 2 * rad >= 80 ? 80 : (2 * rad >= 64 ? 64 : (2 * rad >= 32 ? 32 : (2 * rad >= 16 ? 16 : 8)));
-    return 2 * rad - ks <= BOXR_MAX_LDS_SLOTS ? ks : 0;
-}
-
-// the time-axis stage keeps K4b below 16 slots (already at the HBM floor there); the fused
-// frequency stage takes the register form from r = 4 on
-#ifndef BOXT_MIN_2R
-#define BOXT_MIN_2R 32
-#endif
-#ifndef BOXT_EXACT20
-#define BOXT_EXACT20 1                   // r = 10: all 20 slots of a delay line in registers (k_boxt<20, false, *>): no LDS traffic at all,
-                                         // 11.7 ms per 1008-window launch pair against 13.9 for the LDS delay lines (K4b)
-#endif
-int boxr_pick_ks_t(int rad) {
-    if (BOXT_EXACT20 && 2 * rad == 20) return boxr_pick_ks(rad) > 0 ? 20 : 0;
-    return 2 * rad >= BOXT_MIN_2R ? boxr_pick_ks(rad) : 0;
-}
-int boxr_pick_ks_f(int rad) {
-    static const bool off = is1(getenv("TRI_FILTER_NO_REGRING_F"));
-    return off ? 0 : boxr_pick_ks(rad);
-}
-
-// K4w (kernels_boxweight.hpp): the weight image of the time-axis stage in integer arithmetic, one thread per line, for
-// 20 <= 2r <= 110 -- every radius the register-delay-line kernels (K4r, K4q) serve on that axis.  Returns false when it does
-// not apply; the caller's kernels then filter both images as before.  TRI_FILTER_NO_BOXW=1 switches it off (A/B runs, tests).
-thread_local int g_boxw_override = -1;     // tests / benches: 0 = off
-static bool boxw_usable(int rad, int n, int C) {
-    static const bool off = is1(getenv("TRI_FILTER_NO_BOXW"));
-    if (g_boxw_override == 0 || (off && g_boxw_override < 0)) return false;
-    return 2 * rad >= 20 && 2 * rad <= 110 && n % 4 == 0 && (uint64_t)n * (uint64_t)C * 4u < (1ull << 31);
-}
-template <int R2>
-int launch_boxw_r2(const Run& r, const uint8_t* srcFlags, float* dstW, int n, int C, float denom, size_t sws, size_t dws, int64_t W) {
-    dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
-    hipLaunchKernelGGL((k_boxw<R2>), grid, dim3(64), 0, r.st, srcFlags, dstW, n, C, box_reciprocal(denom), sws, dws);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-int launch_boxw(const Run& r, const uint8_t* srcFlags, float* dstW, int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-#define BOXW_CASE(R2) case R2: return launch_boxw_r2<R2>(r, srcFlags, dstW, n, C, denom, sws, dws, W);
-#define BOXW_CASE5(A) BOXW_CASE(A) BOXW_CASE(A + 2) BOXW_CASE(A + 4) BOXW_CASE(A + 6) BOXW_CASE(A + 8)
-    switch (2 * rad) {
-        BOXW_CASE5(20) BOXW_CASE5(30) BOXW_CASE5(40) BOXW_CASE5(50) BOXW_CASE5(60) BOXW_CASE5(70) BOXW_CASE5(80) BOXW_CASE5(90) BOXW_CASE5(100)
-        BOXW_CASE(110)
-    }
-#undef BOXW_CASE5
-#undef BOXW_CASE
-    return set_err(TRI_EINVAL, "no integer weight filter for radius %d", rad);
-}
-// The weight image through K4w beside the kernel of the data image, which `data` launches on r.st: they read the same flag
-// words and write disjoint images.  overlap: K4w goes to the side lane of r, if it has one; both are done when r.st goes on.
-template <class LaunchData>
-static int launch_boxw_beside(const Run& r, bool overlap, const uint8_t* srcFlags, float* dstW, int n, int C, int rad, float denom,
-                              size_t sws, size_t dws, int64_t W, LaunchData&& data) {
-    const Run side = overlap ? fork(r) : r;
-    const int rc = launch_boxw(side, srcFlags, dstW, n, C, rad, denom, sws, dws, W);
-    if (!rc) data();
-    if (overlap) join(r);
-    return rc;
-}
-
-template <int KS>
-int launch_boxt_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                   int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-    const int d = 2 * rad - KS;
-    const size_t lds = (size_t)4 * d * 64 * sizeof(float);
-    dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
-    HIPCHK(lds_optin_all(160 * 1024, &k_boxt<KS, true, 0>, &k_boxt<KS, true, 1>));
-    // one launch per image: a compute unit then runs (mostly) one of the two long loop bodies at a time
-    // (the weight image through the integer kernel K4w where it applies)
-    const auto data_image = [&] {
-        if (d > 0) hipLaunchKernelGGL((k_boxt<KS, true, 1>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstO, n, C, rad, denom, sws, dws);
-        else hipLaunchKernelGGL((k_boxt<KS, false, 1>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstO, n, C, rad, denom, sws, dws);
-    };
-    if (boxw_usable(rad, n, C)) {
-        const int rc = launch_boxw_beside(r, OVERLAP_TIME_STAGE >= 2, srcFlags, dstW, n, C, rad, denom, sws, dws, W, data_image);
-        if (rc) return rc;
-    } else {
-        if (d > 0) hipLaunchKernelGGL((k_boxt<KS, true, 0>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstW, n, C, rad, denom, sws, dws);
-        else hipLaunchKernelGGL((k_boxt<KS, false, 0>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstW, n, C, rad, denom, sws, dws);
-        data_image();
-    }
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// Spectrum path (byte flags [n][C], a single "window", both images in one launch)
-template <int KS>
-int launch_boxt_spec_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                        int n, int C, int rad, float denom) {
-    const int d = 2 * rad - KS;
-    const size_t lds = (size_t)4 * d * 64 * sizeof(float);
-    dim3 grid((unsigned)cdiv(C, 64), 2);
-    HIPCHK(lds_optin_all(160 * 1024, &k_boxt_spec<KS, true>));
-    if (d > 0) hipLaunchKernelGGL((k_boxt_spec<KS, true>), grid, dim3(64), lds, r.st, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-    else hipLaunchKernelGGL((k_boxt_spec<KS, false>), grid, dim3(64), 0, r.st, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-int launch_boxt_spec(const Run& r, int ks, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                     int n, int C, int rad, float denom) {
-    switch (ks) {
-        case 8: return launch_boxt_spec_ks<8>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-        case 16: return launch_boxt_spec_ks<16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-        case 32: return launch_boxt_spec_ks<32>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-        case 64: return launch_boxt_spec_ks<64>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-        case 80: return launch_boxt_spec_ks<80>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-    }
-    return set_err(TRI_EINVAL, "no register-ring kernel for %d slots", ks);
-}
-
-// Stage-pipelined form (kernels_boxpipe.hpp): block length B for radius rad, 0 when it does not apply
-// (2r >= B, four stage buffers within the CU's 160 KB of LDS).  TRI_SPEC_NO_PIPE=1 keeps the register rings.
-static thread_local int g_boxp_override = -1;   // tests / benches: 0 = off, 8 / 16 = only that block length
-static int boxp_pick_block(int rad, int C) {
-    static const bool off = is1(getenv("TRI_SPEC_NO_PIPE"));
-    if (g_boxp_override == 0 || (off && g_boxp_override < 0)) return 0;
-    if (g_boxp_override != 8 && 2 * rad >= 16 && C % 4 == 0 && boxp_lds_bytes(rad, 16) <= 160 * 1024) return 16;
-    if (g_boxp_override == 16) return 0;
-    if (2 * rad >= 8 && C % 2 == 0 && boxp_lds_bytes(rad, 8) <= 160 * 1024) return 8;
-    return 0;
-}
-
-template <int B, int P>
-int launch_boxp_spec_b(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                       int n, int C, int rad, float denom) {
-    HIPCHK(lds_optin_all(160 * 1024, &k_boxp_spec<B, P>));
-    dim3 grid((unsigned)cdiv(C, 64), 2);
-    hipLaunchKernelGGL((k_boxp_spec<B, P>), grid, dim3(256), boxp_lds_bytes(rad, B), r.st, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// K4q (kernels_boxpipe.hpp): register part of the delay lines for radius rad, 0 when it does not apply.
-// TRI_FILTER_NO_PIPE_T=1 keeps the K4r / LDS kernels.
-#ifndef BOXQ_MIN_2R
-#define BOXQ_MIN_2R 56
-#endif
-thread_local int g_boxq_override = -1;   // tests / benches: 0 = off, 1 = on wherever it applies
-static int boxq_pick_ks(int rad) {
-    static const bool off = is1(getenv("TRI_FILTER_NO_PIPE_T"));
-    if (g_boxq_override == 0 || (off && g_boxq_override < 0)) return 0;
-    const int ks = 2 * rad / 16 * 16;
-    return (ks >= 16 && ks <= 96) ? ks : 0;
-}
-
-template <int KS, int B = 16>
-int launch_boxq_ks(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                   int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-    HIPCHK(lds_optin_all(160 * 1024, &k_boxq<KS, 0, B>, &k_boxq<KS, 1, B>));
-    dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
-    const BoxDenom dn = box_reciprocal(denom);
-    const auto data_image = [&] {
-        hipLaunchKernelGGL((k_boxq<KS, 1, B>), grid, dim3(256), boxq_lds_bytes(B), r.st, srcData, srcFlags, dstO, n, C, rad, dn, sws, dws);
-    };
-    if (boxw_usable(rad, n, C)) {
-        const int rc = launch_boxw_beside(r, OVERLAP_TIME_STAGE >= 1, srcFlags, dstW, n, C, rad, denom, sws, dws, W, data_image);
-        if (rc) return rc;
-    } else {
-        hipLaunchKernelGGL((k_boxq<KS, 0, B>), grid, dim3(256), boxq_lds_bytes(B), r.st, srcData, srcFlags, dstW, n, C, rad, dn, sws, dws);
-        data_image();
-    }
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// blocks of 8 positions (four workgroups = four waves per SIMD) while the delay line fits 128 registers: KS = 8 * floor(2r / 8)
-#ifndef BOXQ_B8_MIN_2R
-#define BOXQ_B8_MIN_2R 32
-#endif
-#ifndef BOXQ_B8_MAX2R
-#define BOXQ_B8_MAX2R 88
-#endif
-thread_local int g_boxq_b8_override = -1;   // tests: 0 = blocks of 16 only (time- and frequency-axis stage pipelines)
-static int boxq_pick_ks8(int rad) {
-    static const int b8 = [] { const char* e = getenv("TRI_FILTER_PIPE_T_B8"); return e ? atoi(e) : 1; }();
-    if (!b8 || g_boxq_b8_override == 0 || 2 * rad < BOXQ_B8_MIN_2R || 2 * rad >= BOXQ_B8_MAX2R) return 0;
-    return 2 * rad / 8 * 8;
-}
-
-// blocks of 8 with FIFOs one block deeper (k_boxq_deep): KS = 80 for 2r = 88 .. 95, KS = 96 for 2r = 104 .. 111
-template <int KS>
-int launch_boxq_deep(const Run& r, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                     int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-    HIPCHK(lds_optin_all(160 * 1024, &k_boxq_deep<KS, 0>, &k_boxq_deep<KS, 1>));
-    dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
-    const BoxDenom dn = box_reciprocal(denom);
-    const auto data_image = [&] {
-        hipLaunchKernelGGL((k_boxq_deep<KS, 1>), grid, dim3(256), boxq_lds_bytes(8, 4), r.st, srcData, srcFlags, dstO, n, C, rad, dn, sws, dws);
-    };
-    if (boxw_usable(rad, n, C)) {
-        const int rc = launch_boxw_beside(r, OVERLAP_TIME_STAGE >= 1, srcFlags, dstW, n, C, rad, denom, sws, dws, W, data_image);
-        if (rc) return rc;
-    } else {
-        hipLaunchKernelGGL((k_boxq_deep<KS, 0>), grid, dim3(256), boxq_lds_bytes(8, 4), r.st, srcData, srcFlags, dstW, n, C, rad, dn, sws, dws);
-        data_image();
-    }
-    LAUNCHCHK();
-    return TRI_OK;
-}
-#ifndef BOXQ_DEEP
-#define BOXQ_DEEP 1
-#endif
-
-int launch_boxq(const Run& r, int ks, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-    if (BOXQ_DEEP && boxq_pick_ks8(40) > 0) {              // (blocks of 8 not switched off)
-        if (2 * rad >= 88 && 2 * rad < 96) return launch_boxq_deep<80>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        if (2 * rad >= 104 && 2 * rad < 112) return launch_boxq_deep<96>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-    }
-    switch (boxq_pick_ks8(rad)) {
-        case 32: return launch_boxq_ks<32, 8>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 40: return launch_boxq_ks<40, 8>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 48: return launch_boxq_ks<48, 8>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 56: return launch_boxq_ks<56, 8>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 64: return launch_boxq_ks<64, 8>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        // (72: the data image's kernel would spill 7 registers at 128 -- blocks of 16 with KS = 64 take 2r = 72 .. 78)
-        case 80: return launch_boxq_ks<80, 8>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-    }
-    switch (ks) {
-        case 16: return launch_boxq_ks<16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 32: return launch_boxq_ks<32>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 48: return launch_boxq_ks<48>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 64: return launch_boxq_ks<64>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 80: return launch_boxq_ks<80>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 96: return launch_boxq_ks<96>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-    }
-    return set_err(TRI_EINVAL, "no stage-pipeline kernel for %d slots", ks);
-}
-
-int launch_boxt(const Run& r, int ks, const float* srcData, const uint8_t* srcFlags, float* dstW, float* dstO,
-                int n, int C, int rad, float denom, size_t sws, size_t dws, int64_t W) {
-    switch (ks) {
-        case 16: return launch_boxt_ks<16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 20: return launch_boxt_ks<20>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 32: return launch_boxt_ks<32>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 64: return launch_boxt_ks<64>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case 80: return launch_boxt_ks<80>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-    }
-    return set_err(TRI_EINVAL, "no register-ring kernel for %d slots", ks);
-}
-
-// Where launch_colfilter() takes the two images from
-enum class ColSrc {
-    ByteFlags,     // built on the fly from (srcData, srcFlags) [n][C], one flag byte per sample
-    Images,        // float arrays: for the multi-pass kernel in rows [4r, 4r+n) of bufW / bufO, for the LDS kernels in rows [0,n)
-    PackedFlags    // built on the fly from (srcData, srcFlags), four line positions of a column per flag word (n % 4 == 0)
-};
-enum ColFlag : unsigned {
-    COL_TRANSPOSED_OUT = 1,   // write [C][n] (LDS-ring kernel, float images only)
-    COL_WEIGHTS_01 = 2        // the weights are 0 / 1: integer arithmetic where it is exact
-};
-enum class ColFamily { SpecPipe, SpecRing, StagePipe, RegRing, Lane4, LdsRing, MultiPass };   // K4p, K4r (spectrum), K4q, K4r, K4c, K4b, K4
-// tri_bench_boxfilter sets this: its images are the caller's, n rows each, without the n + 4r rows the in-place
-// multi-pass kernel works in -- launch_colfilter then refuses that family instead of launching it
-thread_local bool g_colfilter_unpadded = false;
-
-// One axis of masked_gaussian_filter's two box filters (weight image and data image) on a column-layout image pair.
-// Output: rows [0,n) of dstW / dstO.  deferred_denom (optional): where the kernel can, the division by float32(d)**4 is left
-// to the consumer (transpose / masked_div) and *deferred_denom receives the denominator; otherwise it is set to 0.
-int launch_colfilter(const Run& r, ColSrc src, float* bufW, float* bufO, const float* srcData,
-                     const uint8_t* srcFlags, float* dstW, float* dstO, int n, int C, int rad,
-                     size_t bws, size_t sws, size_t dws, int64_t W, unsigned flags = 0, float* deferred_denom = nullptr) {
-    const bool transposed_out = flags & COL_TRANSPOSED_OUT, weights_are_01 = flags & COL_WEIGHTS_01;
-    const float denom = box_denominator(rad);
-    // integer arithmetic for the weight image is exact while (2r+1)^4 <= 2^24
-    const int intw = (weights_are_01 && rad <= 31) ? 1 : 0;
-    int bt = colfilter_lds_block(rad, C);
-    if (deferred_denom) *deferred_denom = 0.0f;
-    // --- which kernel family ---
-    // the register-ring and stage-pipeline kernels build 0 / 1 weights themselves, divide themselves, write [n][C] and address
-    // a window through signed 32-bit buffer offsets
-    const bool regs_ok = !deferred_denom && !transposed_out && weights_are_01 && (uint64_t)n * (uint64_t)C * 4u < (1ull << 31);
-    const bool spectrum = regs_ok && src == ColSrc::ByteFlags && W == 1;    // one "window" of byte flags + data, both images per launch
-    const bool packed = regs_ok && src == ColSrc::PackedFlags && n % 4 == 0;
-    ColFamily fam;
-    if (spectrum && boxp_pick_block(rad, C) > 0 && rad <= 107 && ((uintptr_t)srcData % 16 == 0) && ((uintptr_t)srcFlags % 4 == 0) &&
-        ((uintptr_t)dstW % 16 == 0) && ((uintptr_t)dstO % 16 == 0))
-        fam = ColFamily::SpecPipe;
-    else if (spectrum && boxr_pick_ks(rad) > 0) fam = ColFamily::SpecRing;     // from r = 4 on
-    // measured (1008 windows, both images): K4r 13.4 / 13.5 / 14.6 / 15.9 / 19.2 / 21.9 / 19.9 / 23.0 / 23.7 ms at
-    // r = 17 / 21 / 27 / 28 / 32 / 35 / 40 / 43 / 54; K4q with blocks of 8 (four waves per SIMD, r <= 43)
-    // 15.3 / 15.8 / 16.0 / 15.9 / 16.1 / 16.3 / 17.2 / 17.3, with blocks of 16 19.3 ... 20.8
-    else if (packed && boxq_pick_ks(rad) > 0 && rad <= 107 && (g_boxq_override == 1 || 2 * rad >= BOXQ_MIN_2R)) fam = ColFamily::StagePipe;
-    else if (packed && boxr_pick_ks_t(rad) > 0) fam = ColFamily::RegRing;
-    else if (bt > 0 && colfilter_use_lane4(rad) && !transposed_out && src != ColSrc::ByteFlags) fam = ColFamily::Lane4;
-    else {
-        if (bt > 0 && colfilter_use_lane4(rad) && src == ColSrc::ByteFlags) {
-            // byte flags with a medium radius (no lane-per-stage kernel for them): 4-ring kernel with a small block if it fits
-            bt = rad <= 20 ? 128 : (rad <= 40 ? 64 : 0);
-            while (bt > 64 && bt / 2 >= C) bt /= 2;
-        }
-        fam = bt > 0 ? ColFamily::LdsRing : ColFamily::MultiPass;
-    }
-    if (fam == ColFamily::MultiPass && g_colfilter_unpadded)
-        return set_err(TRI_EUNSUPPORTED, "radius %d takes the in-place multi-pass filter, which needs images padded to n + 4r rows", rad);
-    // --- launch ---
-    // (kernels that build their images ignore bufW / bufO)
-    const bool built = src != ColSrc::Images, divide = !deferred_denom;
-    const float *const inW = built ? nullptr : bufW, *const inO = built ? nullptr : bufO;
-    const size_t in_ws = built ? 0 : bws;
-    switch (fam) {
-        case ColFamily::SpecPipe:
-            if (boxp_pick_block(rad, C) == 16) return launch_boxp_spec_b<16, 16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-            return launch_boxp_spec_b<8, 16>(r, srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-        case ColFamily::SpecRing:
-            return launch_boxt_spec(r, boxr_pick_ks(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom);
-        case ColFamily::StagePipe:
-            return launch_boxq(r, boxq_pick_ks(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case ColFamily::RegRing:
-            return launch_boxt(r, boxr_pick_ks_t(rad), srcData, srcFlags, dstW, dstO, n, C, rad, denom, sws, dws, W);
-        case ColFamily::Lane4: {
-            HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lane4<0, true>, &k_colfilter_lane4<1, true>, &k_colfilter_lane4<1, false>,
-                                 &k_colfilter_lane4<2, false>, &k_colfilter_lane4<2, true>));
-            const auto k = src == ColSrc::PackedFlags ? (divide ? &k_colfilter_lane4<2, true> : &k_colfilter_lane4<2, false>)
-                                                      : (divide ? &k_colfilter_lane4<1, true> : &k_colfilter_lane4<1, false>);
-            if (!divide) *deferred_denom = denom;
-            hipLaunchKernelGGL(k, dim3((unsigned)cdiv(C, 16), (unsigned)W, 2), dim3(64), (size_t)lane4_ring_capacity(rad) * 64 * sizeof(float), r.st,
-                               inW, inO, srcData, srcFlags, dstW, dstO, n, C, rad, denom, in_ws, sws, dws);
-            break;
-        }
-        case ColFamily::LdsRing: {
-            HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lds<0, true, false>, &k_colfilter_lds<1, true, false>, &k_colfilter_lds<1, false, false>,
-                                 &k_colfilter_lds<1, true, true>, &k_colfilter_lds<2, false, false>, &k_colfilter_lds<2, true, false>));
-            // (the division is deferred for float images and packed flags only, the transposed output exists for float images only)
-            auto k = &k_colfilter_lds<0, true, false>;
-            bool div = true;
-            if (src == ColSrc::PackedFlags) { div = divide; k = div ? &k_colfilter_lds<2, true, false> : &k_colfilter_lds<2, false, false>; }
-            else if (transposed_out) k = &k_colfilter_lds<1, true, true>;
-            else if (src == ColSrc::Images) { div = divide; k = div ? &k_colfilter_lds<1, true, false> : &k_colfilter_lds<1, false, false>; }
-            if (!div) *deferred_denom = denom;
-            hipLaunchKernelGGL(k, dim3((unsigned)cdiv(C, bt), (unsigned)W, 2), dim3(bt), (size_t)4 * 2 * rad * bt * sizeof(float), r.st,
-                               inW, inO, srcData, srcFlags, dstW, dstO, n, C, rad, denom, in_ws, sws, dws, intw);
-            break;
-        }
-        case ColFamily::MultiPass: {
-            const int blk = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-            const auto k = src == ColSrc::ByteFlags ? &k_colfilter<0> : &k_colfilter<1>;
-            hipLaunchKernelGGL(k, dim3((unsigned)cdiv(C, blk), (unsigned)W, 2), dim3(blk), 0, r.st, bufW, bufO, srcData, srcFlags,
-                               dstW, dstO, n, C, rad, denom, bws, sws, dws);
-            break;
-        }
-    }
-    LAUNCHCHK();
-    return TRI_OK;
-}
+#include "boxfilter_host.hpp"
 
 // K7p applies: up to eight windows whose flag-byte ring fits the CU's LDS (there are no prefix rings any more)
 // (TRI_ST_NO_PIPE=1 keeps the global-scratch kernel)
@@ -1109,246 +764,6 @@ int launch_sub(const Run& r, const float* a, const float* b, float* out, size_t 
     return TRI_OK;
 }
 
-// Frequency-axis stage reading the time-axis stage's TF images directly
-// (k_colfilter_lds_t).  Usable for radii whose four rings fit LDS at 128 threads.
-static bool filter_no_tin() { static const bool v = is1(getenv("TRI_FILTER_NO_TIN")); return v; }
-bool colfilter_t_usable(int rad) { return !filter_no_tin() && rad > 0 && rad <= 16; }
-
-int launch_colfilter_t(const Run& r, const float* srcW, const float* srcO, float* dstW, float* dstO,
-                       int n, int C, int ld, int rad, size_t sws_img, size_t dws, int64_t W, float* deferred_denom) {
-    float denom = box_denominator(rad);
-    size_t lds = ((size_t)4 * 2 * rad * CFT_BT + (size_t)CFT_PF * (CFT_BT + 1)) * sizeof(float);
-    HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lds_t<false>, &k_colfilter_lds_t<true>));
-    dim3 grid((unsigned)cdiv(C, CFT_BT), (unsigned)W, 2);
-    if (deferred_denom) *deferred_denom = denom;
-    const auto k = deferred_denom ? &k_colfilter_lds_t<false> : &k_colfilter_lds_t<true>;
-    hipLaunchKernelGGL(k, grid, dim3(CFT_BT), lds, r.st, srcW, srcO, dstW, dstO, n, C, ld, rad, denom, sws_img, dws);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// The same stage fused with the masked division that follows it (k_colfilter_lds_tf):
-// MODE 1 leaves |data - background| in dstO, MODE 2 the background in dstO, the signed
-// residual in dstW and the per-line NaN markers.  TRI_FILTER_NO_FUSED_DIV=1 keeps the
-// separate kernels (A/B runs).
-bool colfilter_tf_usable(int rad) {
-    static const bool off = is1(getenv("TRI_FILTER_NO_FUSED_DIV"));
-    return !off && colfilter_t_usable(rad);
-}
-
-template <int MODE>
-int launch_colfilter_tf(const Run& r, const float* srcW, const float* srcO, float* dstW, float* dstO, const float* data,
-                        int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag) {
-    float denom = box_denominator(rad);
-    size_t lds = (size_t)2 * ((size_t)4 * 2 * rad * CFF_BT + (size_t)CFT_PF * (CFF_BT + 1)) * sizeof(float);
-    HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lds_tf<MODE>));
-    dim3 grid((unsigned)cdiv(C, CFF_BT), (unsigned)W);
-    hipLaunchKernelGGL(k_colfilter_lds_tf<MODE>, grid, dim3(2 * CFF_BT), lds, r.st, srcW, srcO, dstW, dstO, data, n, C, ld, rad,
-                       denom, sws_img, dws, ws_data, nanflag);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// Register-ring form of the fused stage (K4r, k_boxf): any radius boxr_pick_ks() accepts.
-template <int KS, int MODE>
-int launch_boxf_ks(const Run& r, const float* srcW, const float* srcO, float* dstW, float* dstO, const float* data,
-                   int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag,
-                   float* dstP, size_t pws, bool* wroteP) {
-    const BoxDenom denom = box_reciprocal(box_denominator(rad));
-    const int d = 2 * rad - KS;
-    // (the panel output only where the kernel has the registers for it: see boxf_panel_ok())
-    if (!(MODE == 2 && boxf_panel_ok(KS, d > 0))) dstP = nullptr;
-    if (dstP && wroteP) *wroteP = true;
-    const size_t lds = ((size_t)4 * d * 64 + (size_t)2 * boxr_pf_f(KS) * boxf_nsub(KS) * boxf_ts(boxr_pf_f(KS) * boxf_nsub(KS))) * sizeof(float);
-    // one descriptor per window spans both images: the data image must follow the weight image closely
-    if (srcO <= srcW || ((uint64_t)(srcO - srcW) + (uint64_t)C * ld) * 4u >= (1ull << 31))
-        return set_err(TRI_EUNSUPPORTED, "fused frequency stage: the data image must follow the weight image within 2^31 bytes");
-    const unsigned gap = (unsigned)(srcO - srcW);
-    HIPCHK(lds_optin_all(160 * 1024, &k_boxf<KS, true, MODE>));
-    dim3 grid((unsigned)cdiv(C, 32), (unsigned)W);
-    // 32 register slots: two waves per SIMD only pay while the LDS part leaves room for them (measured: r = 30,
-    // 28 LDS slots: 10.0 ms per 252 windows at two waves per SIMD, 7.0 ms with the one-wave register budget)
-    auto k = d > 0 ? &k_boxf<KS, true, MODE> : &k_boxf<KS, false, MODE>;
-    if constexpr (KS == 32) {
-        if (d > 14) { k = &k_boxf<KS, true, MODE, 1>; HIPCHK(lds_optin_all(160 * 1024, k)); }
-    }
-    hipLaunchKernelGGL(k, grid, dim3(64), lds, r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad, denom, sws_img, dws, ws_data, nanflag, dstP, pws);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-// K4qf: the fused frequency stage as an eight-wave stage pipeline (kernels_boxpipe.hpp)
-#ifndef BOXQF_MIN_2R
-#define BOXQF_MIN_2R 34
-#endif
-#ifndef BOXQF_FEW_WAVES
-#define BOXQF_FEW_WAVES 2048             // waves a K4r launch needs to fill the machine at two per SIMD
-#endif
-#ifndef BOXQF_B8_DEFAULT
-#define BOXQF_B8_DEFAULT 1
-#endif
-#ifndef BOXQF_B8_MAX2R
-#define BOXQF_B8_MAX2R 88                // blocks of 8 positions below this delay (56: up to 48 registers; 72: up to 64; 88: up to 80)
-#endif
-template <int KS, int MODE, int B = 16>
-int launch_boxqf_ks(const Run& r, const float* srcW, unsigned gap, float* dstW, float* dstO, const float* data,
-                    int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag) {
-    HIPCHK(lds_optin_all(160 * 1024, &k_boxqf<KS, MODE, B>));
-    const BoxDenom denom = box_reciprocal(box_denominator(rad));
-    dim3 grid((unsigned)cdiv(C, 64), (unsigned)W);
-    hipLaunchKernelGGL((k_boxqf<KS, MODE, B>), grid, dim3(512), boxqf_lds_bytes(B, boxqf_dbl(KS, B)), r.st, srcW, gap, dstW, dstO, data, n, C, ld, rad,
-                       denom, sws_img, dws, ws_data, nanflag);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
-template <int MODE>
-int launch_boxf(const Run& r, int ks, const float* srcW, const float* srcO, float* dstW, float* dstO, const float* data,
-                int n, int C, int ld, int rad, size_t sws_img, size_t dws, size_t ws_data, int64_t W, uint8_t* nanflag,
-                float* dstP = nullptr, size_t pws = 0, bool* wroteP = nullptr) {
-    // MODE 2, dstP: the register-ring kernel (K4r) also writes the residual as column panels [n / 64][C][64] where it has
-    // the registers for it, and says so in *wroteP; the stage pipeline (K4qf) has no such output and leaves *wroteP alone
-    if (MODE != 2 || n % 64 != 0) dstP = nullptr;
-    {
-        static const bool off = is1(getenv("TRI_FILTER_NO_PIPE_F"));
-        const int kq = boxq_pick_ks(rad);
-        // Few, long lines (an SKA slab: 64 windows of 512 lines x 65536 channels): the one-wave-per-32-lines kernels (K4r) fill
-        // half the machine at best; the stage pipeline (a workgroup of eight waves per 64 lines) then takes the small radii too.
-        const bool few = (int64_t)W * cdiv(C, 32) < BOXQF_FEW_WAVES;
-        const bool want = g_boxq_override == 1 || (g_boxq_override < 0 && !off && (2 * rad >= BOXQF_MIN_2R || (few && 2 * rad >= 16)));
-        if (want && kq > 0 && srcO > srcW && n % 4 == 0 && ld % 4 == 0 && sws_img % 4 == 0 && (uint64_t)(srcO - srcW) % 4 == 0 &&
-            ((uintptr_t)srcW % 16 == 0) && ((uint64_t)(srcO - srcW) + (uint64_t)C * ld) * 4u < (1ull << 31) &&
-            (uint64_t)n * (uint64_t)C * 4u < (1ull << 31)) {
-            const unsigned gap = (unsigned)(srcO - srcW);
-            // blocks of 8 positions (two workgroups per CU) while the delay line leaves the registers for it
-            static const int b8 = [] { const char* e = getenv("TRI_FILTER_PIPE_F_B8"); return e ? atoi(e) : BOXQF_B8_DEFAULT; }();
-            if (b8 && g_boxq_b8_override != 0 && 2 * rad >= 16 && 2 * rad < BOXQF_B8_MAX2R) {
-                switch (2 * rad / 8 * 8) {
-                    case 16: return launch_boxqf_ks<16, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                    case 24: return launch_boxqf_ks<24, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                    case 32: return launch_boxqf_ks<32, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                    case 40: return launch_boxqf_ks<40, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                    case 48: return launch_boxqf_ks<48, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-#if BOXQF_B8_MAX2R > 56
-                    case 56: return launch_boxqf_ks<56, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                    case 64: return launch_boxqf_ks<64, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-#endif
-#if BOXQF_B8_MAX2R > 72
-                    case 72: return launch_boxqf_ks<72, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                    case 80:                                // (MODE 2 would spill 11 registers at 128: blocks of 16 for it)
-                        if (MODE == 1) return launch_boxqf_ks<80, 1, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                        break;
-#endif
-#if BOXQF_B8_MAX2R > 88
-                    case 96: return launch_boxqf_ks<96, MODE, 8>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-#endif
-                }
-            }
-            switch (kq) {
-                case 16: return launch_boxqf_ks<16, MODE>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                case 32: return launch_boxqf_ks<32, MODE>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                case 48: return launch_boxqf_ks<48, MODE>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                case 64: return launch_boxqf_ks<64, MODE>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                case 80: return launch_boxqf_ks<80, MODE>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-                case 96: return launch_boxqf_ks<96, MODE>(r, srcW, gap, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag);
-            }
-        }
-    }
-    switch (ks) {
-        case 8: return launch_boxf_ks<8, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
-        case 16: return launch_boxf_ks<16, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
-        case 32: return launch_boxf_ks<32, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
-        case 64: return launch_boxf_ks<64, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
-        case 80: return launch_boxf_ks<80, MODE>(r, srcW, srcO, dstW, dstO, data, n, C, ld, rad, sws_img, dws, ws_data, W, nanflag, dstP, pws, wroteP);
-    }
-    return set_err(TRI_EINVAL, "no register-ring kernel for %d slots", ks);
-}
-
-// K4x: the frequency-axis stage + masked division for any radius, one line pair resident in LDS, lanes =
-// positions, exactness checked per pass with a sequential redo (kernels_boxexact.hpp).  Rows in, rows out.
-// The flagger takes it where no stage pipeline exists (r >= 56: final_st_very_broad's 277 / 221 / 166 / 110);
-// TRI_FILTER_NO_EXACT=1 restores the lane-per-stage / in-place multi-pass routes (A/B runs, tests).
-thread_local int g_boxx_override = -1;   // tests / benches: 0 = off, 1 = on wherever the shape allows
-thread_local unsigned long long g_boxx_last_stats[2] = {0, 0};
-#ifndef BOXX_MIN_R
-#define BOXX_MIN_R 56
-#endif
-// chunk length (low 8 bits) and threads per image (128 or 256, << 8) for a line of n positions, or 0.
-// Long chunks on 128 threads per image where the line fits them (fewer instructions per line: see the kernel);
-// TRI_BOXX_NTI=256 forces the short chunks (A/B runs).
-int boxx_pick_l(int rad, int n) {
-    static const bool env_off = is1(getenv("TRI_FILTER_NO_EXACT"));
-    static const int force_nti = [] { const char* e = getenv("TRI_BOXX_NTI"); return e ? atoi(e) : 0; }();
-    if (g_boxx_override == 0 || (g_boxx_override < 0 && (env_off || rad < BOXX_MIN_R))) return 0;
-    if (rad < 1 || n % 4 != 0) return 0;
-    const int64_t P = (int64_t)n + 4 * (int64_t)rad;
-    struct Cand { int nti, l; };
-    static const Cand cands[] = {{128, 37}, {128, 41}, {256, 17}, {256, 19}, {256, 21}, {256, 25}};
-    for (const Cand& c : cands) {
-        if (force_nti && c.nti != force_nti) continue;
-        if (c.nti == 128 && (P <= 128 * 17 || rad < 64)) continue;        // (short lines / small radii: the short chunks do)
-        if ((int64_t)c.nti * c.l < P || c.l > 2 * rad + 1 || (2 * rad + 1) / c.l > BOXX_AMAX) continue;
-        if (boxx_lds_bytes(c.nti, c.l, rad) > 159 * 1024) continue;
-        return c.l | (c.nti << 8);
-    }
-    return 0;
-}
-// the reciprocal division is verified exhaustively for these radii only (test_division_by_box_denominator)
-static bool boxx_recip_ok(int rad) { return rad <= 128 || rad == 166 || rad == 221 || rad == 277 || rad == 397 || rad == 795; }
-
-template <int NTI, int L, int MODE>
-int launch_boxx_l(const Run& r, const float* srcW, unsigned gap, const float* data, const uint8_t* mask, float* outA, float* outB,
-                  int n, int C, int ld, int rad, size_t sws_img, size_t ws_data, size_t ws_mask, size_t ws_outA, size_t ws_outB,
-                  int64_t W, uint8_t* nanflag, unsigned long long* stats) {
-    const BoxDenom denom = box_reciprocal(box_denominator(rad));
-    const size_t lds = boxx_lds_bytes(NTI, L, rad);
-    dim3 grid((unsigned)C, (unsigned)W);
-    // (the kernel also has a few static LDS bytes -- __syncthreads_or -- so 160 KB of dynamic LDS is refused: ask for 159)
-    const auto k = boxx_recip_ok(rad) ? &k_boxx<NTI, L, MODE, true> : &k_boxx<NTI, L, MODE, false>;
-    HIPCHK(lds_optin_all(159 * 1024, k));
-    hipLaunchKernelGGL(k, grid, dim3(2 * NTI), lds, r.st, srcW, gap, data, mask, outA, outB, n, ld, rad, denom, sws_img,
-                       ws_data, ws_mask, ws_outA, ws_outB, nanflag, stats);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-// rows of (srcW, srcO) [C][ld] + data rows [C][n] (+ byte mask rows) -> outA (MODE 1: |data - bg|; MODE 2: bg), outB (MODE 2: data - bg),
-// rows [C][ld]; outputs may alias the inputs (a workgroup has its whole line in LDS before it writes)
-template <int MODE>
-int launch_boxx(const Run& r, int L, const float* srcW, const float* srcO, const float* data, const uint8_t* mask, float* outA, float* outB,
-                int n, int C, int ld, int rad, size_t sws_img, size_t ws_data, size_t ws_mask, size_t ws_outA, size_t ws_outB,
-                int64_t W, uint8_t* nanflag, unsigned long long* stats = nullptr) {
-    if (srcO <= srcW || ld % 4 != 0 || sws_img % 4 != 0 || (uint64_t)(srcO - srcW) % 4 != 0 || ((uintptr_t)srcW % 16 != 0) ||
-        ((uintptr_t)data % 16 != 0) || ws_data % 4 != 0 || ((uintptr_t)outA % 16 != 0) || ws_outA % 4 != 0 ||
-        (mask && (((uintptr_t)mask % 4 != 0) || ws_mask % 4 != 0)) || (uint64_t)(srcO - srcW) > 0xffffffffull ||
-        (MODE == 2 && (((uintptr_t)outB % 16 != 0) || ws_outB % 4 != 0)) || C > 65535 * 1024)
-        return set_err(TRI_EUNSUPPORTED, "exact row filter: unaligned images");
-    const unsigned gap = (unsigned)(srcO - srcW);
-#define BOXX_CASE(NTI, LL) case ((NTI) << 8 | (LL)): return launch_boxx_l<NTI, LL, MODE>(r, srcW, gap, data, mask, outA, outB, n, C, ld, rad, sws_img, ws_data, ws_mask, ws_outA, ws_outB, W, nanflag, stats);
-    switch (L) {
-        BOXX_CASE(128, 37) BOXX_CASE(128, 41)
-        BOXX_CASE(256, 17) BOXX_CASE(256, 19) BOXX_CASE(256, 21) BOXX_CASE(256, 25)
-    }
-#undef BOXX_CASE
-    return set_err(TRI_EINVAL, "no exact row filter for code %d", L);
-}
-
-// Lane-per-stage variant of the same (radii 17..LANE4_R_MAX): k_colfilter_lane4<3, *>.
-bool colfilter_t4_usable(int rad) { return !filter_no_tin() && colfilter_use_lane4(rad); }
-
-int launch_colfilter_t4(const Run& r, const float* srcW, const float* srcO, float* dstW, float* dstO,
-                        int n, int C, int ld, int rad, size_t sws_img, size_t dws, int64_t W, float* deferred_denom) {
-    float denom = box_denominator(rad);
-    size_t lds = ((size_t)lane4_ring_capacity(rad) * 64 + 32 * 17) * sizeof(float);
-    HIPCHK(lds_optin_all(160 * 1024, &k_colfilter_lane4<3, false>, &k_colfilter_lane4<3, true>));
-    dim3 grid((unsigned)cdiv(C, 16), (unsigned)W, 2);
-    if (deferred_denom) *deferred_denom = denom;
-    const auto k = deferred_denom ? &k_colfilter_lane4<3, false> : &k_colfilter_lane4<3, true>;
-    hipLaunchKernelGGL(k, grid, dim3(64), lds, r.st, srcW, srcO, (const float*)nullptr, (const uint8_t*)nullptr,
-                       dstW, dstO, n, C, rad, denom, sws_img, (size_t)ld, dws);
-    LAUNCHCHK();
-    return TRI_OK;
-}
-
 // _get_background2d (flagging.py:516-579) for the median spectra of the batch,
 // held in spectrum layout [Fa][Wb] (line axis = channel, column = window).
 // Result: rows [0,Fa) of ws.so hold the background.
@@ -1391,8 +806,9 @@ int spectrum_background(const Run& r) {
         // Radii beyond the stage pipeline (K4p): the spectra as ROWS through the exact row filter (K4x) -- the in-place
         // multi-pass kernel walks 4 x (Fa + 4 r) positions with one wave per 64 windows: 5.8 ms per launch whatever
         // the batch.  The 2-D time-stage scratch (ws.Aw ...) is idle here and holds the four row images.
-        const int xl = (rad > 0 && 2 * (size_t)pl.PT >= 4) ? boxx_pick_l(rad, Fa) : 0;
-        if (xl > 0) {
+        FreqPick rows;
+        rows.xl = (rad > 0 && 2 * (size_t)pl.PT >= 4) ? boxx_pick_l(r.box, rad, Fa) : 0;
+        if (rows.xl > 0) {
             float* rowW = ws.Aw;                       // [Wn][Fa] weight rows, then the signed residual (unused)
             float* rowO = ws.Aw + nS;                  // weight * data rows
             float* rowD = ws.Aw + 2 * nS;              // the spectra themselves
@@ -1404,10 +820,11 @@ int spectrum_background(const Run& r) {
             if (!rc && !rowD_valid) rc = launch_transpose<float>(r, ws.sdata, rowD, Fa, Wn, 0, 0, 1);
             if (rc) return rc;
             rowD_valid = true;
-            if (final_pass)
-                rc = launch_boxx<2>(r, xl, rowW, rowO, rowD, nullptr, rowR, rowW, Fa, Wn, Fa, rad, 0, 0, 0, 0, 0, 1, reinterpret_cast<uint8_t*>(ws.rowcnt));
-            else
-                rc = launch_boxx<1>(r, xl, rowW, rowO, rowD, nullptr, rowR, nullptr, Fa, Wn, Fa, rad, 0, 0, 0, 0, 0, 1, nullptr);
+            FreqJob j;
+            j.srcW = rowW; j.srcO = rowO; j.data = rowD; j.outA = rowR;
+            j.n = Fa; j.C = Wn; j.ld = Fa; j.rad = rad;
+            if (final_pass) { j.outB = rowW; j.nanflag = reinterpret_cast<uint8_t*>(ws.rowcnt); }
+            rc = final_pass ? launch_boxx<2>(r, rows, j) : launch_boxx<1>(r, rows, j);
             if (!rc) rc = launch_transpose<float>(r, rowR, ws.so, Wn, Fa, 0, 0, 1);
             if (rc) return rc;
             if (!final_pass) {
@@ -1419,7 +836,11 @@ int spectrum_background(const Run& r) {
             continue;
         }
         if (rad > 0) {
-            int rc = launch_colfilter(r, ColSrc::ByteFlags, ws.sw, ws.so, ws.sdata, ws.sbgf, ws.sw, ws.so, Fa, Wn, rad, 0, 0, 0, 1, COL_WEIGHTS_01);
+            ColJob j;
+            j.srcData = ws.sdata; j.srcFlags = ws.sbgf;
+            j.bufW = j.dstW = ws.sw; j.bufO = j.dstO = ws.so;
+            j.n = Fa; j.C = Wn; j.rad = rad;
+            int rc = launch_colfilter(r, pick_col_filter(r.box, ColSrc::ByteFlags, COL_WEIGHTS_01, false, rad, Fa, Wn, 1, spectrum_aligned(j)), j);
             if (rc) return rc;
         } else {
             hipLaunchKernelGGL(k_build_wo, grid1(nS, 1), dim3(256), 0, r.st, ws.sdata, ws.sbgf, ws.sw, ws.so, nS, (size_t)0, (size_t)0);
@@ -1458,14 +879,7 @@ enum class TimeStage {
     PrebuiltDirectFT, // ... which writes the FT layout itself (TRI_FILTER_DIRECT_FT=1; measured no faster than two transposes)
     ByteFlags         // built on the fly from byte flags (multi-pass kernel of the large radii: 11.4 vs 16.8 ms per call with a build)
 };
-enum class FreqStage {
-    ExactRows,        // K4x: rows of the time stage's TF images in, rows out, then to FT
-    FusedRing,        // K4r / K4qf + masked division in one kernel (launch_boxf)
-    FusedLds,         // four LDS rings + masked division in one kernel (launch_colfilter_tf)
-    LdsDiv,           // four LDS rings from the TF images, then the division (launch_colfilter_t)
-    Lane4Div,         // lane per stage from the TF images, then the division (launch_colfilter_t4)
-    Transposed        // two transposes, launch_colfilter on the FT images (none at r = 0), then the division
-};
+// (FreqStage / FreqPick, the frequency stage of one radius: boxfilter_host.hpp)
 enum class Reject {
     None,             // final pass
     InRows,           // K4x iterations: block medians and rejection where the rows lie (TF4 flag words)
@@ -1475,31 +889,6 @@ enum class Reject {
     MedianReject4,    // block medians, then the vector rejection and a transpose of the flags
     MedianReject      // block medians, then the scalar rejection and a transpose of the flags
 };
-
-// The frequency stage of one radius: lines of n positions, C of them per window, the data image `gap` floats behind the
-// weight image.  Shared by the flagger and tri_bench_boxfilter.
-struct FreqPick {
-    FreqStage route;
-    int ks;           // FusedRing: register slots of K4r
-    int xl;           // ExactRows: chunk code of K4x
-    size_t off;       // Transposed: first element of the FT images (rows [4r, 4r + n) of the padded buffers for the in-place
-                      // multi-pass filter, rows [0, n) for the single-sweep one)
-};
-static FreqPick pick_freq_unfused(int rad, int C) {
-    return {FreqStage::Transposed, 0, 0, colfilter_lds_block(rad, C) > 0 ? 0 : (size_t)4 * rad * C};
-}
-static FreqPick pick_freq_stage(int rad, int n, int C, size_t gap, bool exact_rows) {
-    // register-ring fused stage: signed 32-bit buffer offsets, one descriptor over both images of a window
-    const int ks = ((uint64_t)gap + (uint64_t)n * C) * 4u < (1ull << 31) ? boxr_pick_ks_f(rad) : 0;
-    // exact row filter where the stage pipelines end
-    const int xl = (rad > 0 && (!ks || rad >= BOXX_MIN_R) && exact_rows) ? boxx_pick_l(rad, n) : 0;
-    if (xl > 0) return {FreqStage::ExactRows, 0, xl, 0};
-    if (ks > 0) return {FreqStage::FusedRing, ks, 0, 0};
-    if (colfilter_tf_usable(rad)) return {FreqStage::FusedLds, 0, 0, 0};
-    if (colfilter_t_usable(rad)) return {FreqStage::LdsDiv, 0, 0, 0};
-    if (colfilter_t4_usable(rad)) return {FreqStage::Lane4Div, 0, 0, 0};
-    return pick_freq_unfused(rad, C);
-}
 
 // K3t (tile-parallel median + rejection): scratch sizes and whether the rejection iterations take it
 struct TileRoute { bool use; size_t ccap, ucap; int ytiles; };
@@ -1535,6 +924,7 @@ struct BgStep {
     TimeStage time;
     bool time_needs_bytes;   // the time stage reads a TF byte image of the flags, rebuilt into ws.comb while they are packed
     bool time_defers;        // it leaves its division by float32(d)**4 to the transposes (else it divides itself)
+    ColPick tcol;            // r0 > 0: the filter of the time stage
     FreqPick freq;
     bool freq_transposes;    // Transposed: the FT images still have to be made (not after PrebuiltDirectFT)
     Reject reject;
@@ -1553,7 +943,7 @@ static BgStep pick_bg_step(const Run& r, bool packed, bool tile_route, int ext) 
     s.r1 = (int)box_radius(e * r.p->spike_width_freq);
 
     static const bool prebuild = [] { const char* e = getenv("TRI_TIME_PREBUILD"); return !(e && e[0] == '0'); }();
-    const bool sweep = s.r0 > 0 && colfilter_lds_block(s.r0, Fa) > 0;
+    const bool sweep = s.r0 > 0 && colfilter_lds_block(r.box, s.r0, Fa) > 0;
     if (s.r0 == 0) s.time = TimeStage::BuildOnly;
     else if (sweep && packed) s.time = TimeStage::PackedSweep;
     else if (sweep && prebuild) {
@@ -1563,10 +953,18 @@ static BgStep pick_bg_step(const Run& r, bool packed, bool tile_route, int ext) 
     s.time_needs_bytes = packed && (s.time == TimeStage::BuildOnly || s.time == TimeStage::ByteFlags);
 
     // (K4x masks the unmasked cached amplitudes with the iteration's input flags: it needs them)
-    s.freq = s.time == TimeStage::PrebuiltDirectFT ? pick_freq_unfused(s.r1, T)
-                                                   : pick_freq_stage(s.r1, Fa, T, (size_t)(r.ws.Ao - r.ws.Aw), !r.ampl_cached || r.data_mask);
+    s.freq = s.time == TimeStage::PrebuiltDirectFT
+                 ? pick_freq_unfused(r.box, s.r1, Fa, T, r.Wb)
+                 : pick_freq_stage(r.box, s.final_pass ? 2 : 1, s.r1, Fa, T, r.Wb, r.ws.Aw, r.ws.Ao, wsA, !r.ampl_cached || r.data_mask);
     s.freq_transposes = s.time != TimeStage::PrebuiltDirectFT;
     s.time_defers = s.freq.route == FreqStage::Transposed;
+    switch (s.time) {
+        case TimeStage::BuildOnly: break;
+        case TimeStage::PackedSweep: s.tcol = pick_col_filter(r.box, ColSrc::PackedFlags, COL_WEIGHTS_01, s.time_defers, s.r0, T, Fa, r.Wb, false); break;
+        case TimeStage::Prebuilt: s.tcol = pick_col_filter(r.box, ColSrc::Images, COL_WEIGHTS_01, s.time_defers, s.r0, T, Fa, r.Wb, false); break;
+        case TimeStage::PrebuiltDirectFT: s.tcol = pick_col_filter(r.box, ColSrc::Images, COL_TRANSPOSED_OUT, false, s.r0, T, Fa, r.Wb, false); break;
+        case TimeStage::ByteFlags: s.tcol = pick_col_filter(r.box, ColSrc::ByteFlags, 0, false, s.r0, T, Fa, r.Wb, false); break;
+    }
 
     // K4x iterations stay in the row layout altogether (TRI_FILTER_NO_TF_REJECT=1: transposes + FT kernels)
     static const bool no_tfr = is1(getenv("TRI_FILTER_NO_TF_REJECT"));
@@ -1615,8 +1013,11 @@ static int bg_time_stage(const Run& r, const BgStep& s, const BgImages& im, cons
     const size_t N = (size_t)T * Fa;
     const int64_t W = im.W;
     int rc = TRI_OK;
-    *den_t = 0.0f;
-    float* const defer = s.time_defers ? den_t : nullptr;
+    *den_t = (s.r0 > 0 && s.tcol.defers) ? box_denominator(s.r0) : 0.0f;
+    ColJob j;     // (the sweep's source: the float images in place, or data + flags)
+    j.bufW = j.dstW = im.Aw; j.bufO = j.dstO = im.Ao;
+    j.n = T; j.C = Fa; j.rad = s.r0;
+    j.bws = j.dws = im.wsA; j.W = W;
     const uint8_t* fl = im.flagsTF;
     if (s.time_needs_bytes) {
         rc = launch_transpose<uint8_t>(r, st.cur_ft, im.comb, Fa, T, N, N, W);
@@ -1629,7 +1030,9 @@ static int bg_time_stage(const Run& r, const BgStep& s, const BgImages& im, cons
             LAUNCHCHK();
             return TRI_OK;
         case TimeStage::PackedSweep:
-            return launch_colfilter(r, ColSrc::PackedFlags, im.Aw, im.Ao, im.dataTF, fl, im.Aw, im.Ao, T, Fa, s.r0, im.wsA, N, im.wsA, W, COL_WEIGHTS_01, defer);
+        case TimeStage::ByteFlags:
+            j.srcData = im.dataTF; j.srcFlags = fl; j.sws = N;
+            return launch_colfilter(r, s.tcol, j);
         case TimeStage::Prebuilt:
         case TimeStage::PrebuiltDirectFT:
             if (N % 4 == 0 && im.wsA % 4 == 0)
@@ -1637,11 +1040,8 @@ static int bg_time_stage(const Run& r, const BgStep& s, const BgImages& im, cons
             else
                 hipLaunchKernelGGL(k_build_wo, grid1(N, W), dim3(256), 0, r.st, im.dataTF, fl, im.Aw, im.Ao, N, N, im.wsA);
             LAUNCHCHK();
-            if (s.time == TimeStage::Prebuilt)
-                return launch_colfilter(r, ColSrc::Images, im.Aw, im.Ao, nullptr, nullptr, im.Aw, im.Ao, T, Fa, s.r0, im.wsA, 0, im.wsA, W, COL_WEIGHTS_01, defer);
-            return launch_colfilter(r, ColSrc::Images, im.Aw, im.Ao, nullptr, nullptr, im.Bw + s.freq.off, im.Bo + s.freq.off, T, Fa, s.r0, im.wsA, 0, im.wsB, W, COL_TRANSPOSED_OUT);
-        case TimeStage::ByteFlags:
-            return launch_colfilter(r, ColSrc::ByteFlags, im.Aw, im.Ao, im.dataTF, fl, im.Aw, im.Ao, T, Fa, s.r0, im.wsA, N, im.wsA, W);
+            if (s.time == TimeStage::PrebuiltDirectFT) { j.dstW = im.Bw + s.freq.off; j.dstO = im.Bo + s.freq.off; j.dws = im.wsB; }
+            return launch_colfilter(r, s.tcol, j);
     }
     return set_err(TRI_EINVAL, "internal: no such time stage");
 }
@@ -1655,35 +1055,46 @@ static int bg_freq_stage_mode(const Run& r, const BgStep& s, const BgImages& im,
     const size_t N = (size_t)T * Fa, wsA = im.wsA, wsB = im.wsB;
     const int64_t W = im.W;
     uint8_t* const nan = MODE == 2 ? im.nanflag : nullptr;
-    float den_f = 0.0f;   // division deferred to masked_div
+    const float den_f = s.freq.defers ? box_denominator(r1) : 0.0f;   // division deferred to masked_div
     int rc = TRI_OK;
+    FreqJob j;
+    j.srcW = im.Aw; j.srcO = im.Ao; j.dstW = im.Bw; j.dstO = im.Bo; j.data = im.dataFT;
+    j.n = Fa; j.C = T; j.ld = Fa; j.rad = r1;
+    j.sws_img = wsA; j.dws = wsB; j.ws_data = N; j.W = W; j.nanflag = nan;
     // im.nanflag (W * T ints, idle until the end of the iteration) holds the per-line NaN markers
     if (MODE == 2) HIPCHK(hipMemsetAsync(im.nanflag, 0, (size_t)W * T, r.st));
     switch (s.freq.route) {
         case FreqStage::ExactRows:
             // (the flagger: im.rows == im.Ao, the rows are filtered in place; MODE 2: im.Aw <- data - background)
-            rc = launch_boxx<MODE>(r, s.freq.xl, im.Aw, im.Ao, im.dataTF, im.mask, im.rows, MODE == 2 ? im.Aw : nullptr, Fa, T, Fa, r1, wsA, N,
-                                   im.ws_mask, im.ws_rows, MODE == 2 ? wsA : 0, W, nan, im.xstats);
+            j.data = im.dataTF; j.mask = im.mask; j.ws_mask = im.ws_mask; j.stats = im.xstats;
+            j.outA = im.rows; j.ws_outA = im.ws_rows;
+            if (MODE == 2) { j.outB = im.Aw; j.ws_outB = wsA; }
+            rc = launch_boxx<MODE>(r, s.freq, j);
             if (!rc && MODE == 2) rc = launch_transpose<float>(r, im.Aw, im.Bw, T, Fa, wsA, wsB, W);
             if (rc || s.reject == Reject::InRows) return rc;
             return launch_transpose<float>(r, im.rows, im.Bo, T, Fa, im.ws_rows, wsB, W);
         case FreqStage::FusedRing:
-            return launch_boxf<MODE>(r, s.freq.ks, im.Aw, im.Ao, im.Bw, im.Bo, im.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, nan,
-                                     MODE == 2 ? im.residP : nullptr, MODE == 2 ? N : 0, &st.wrote_panel);
+            if (MODE == 2) { j.dstP = im.residP; j.pws = N; }
+            j.wroteP = &st.wrote_panel;
+            return launch_boxf<MODE>(r, s.freq, j);
         case FreqStage::FusedLds:
-            return launch_colfilter_tf<MODE>(r, im.Aw, im.Ao, im.Bw, im.Bo, im.dataFT, Fa, T, Fa, r1, wsA, wsB, N, W, nan);
+            return launch_colfilter_tf<MODE>(r, j);
         case FreqStage::LdsDiv:
-            rc = launch_colfilter_t(r, im.Aw, im.Ao, im.Bw, im.Bo, Fa, T, Fa, r1, wsA, wsB, W, &den_f);
-            break;
         case FreqStage::Lane4Div:
-            rc = launch_colfilter_t4(r, im.Aw, im.Ao, im.Bw, im.Bo, Fa, T, Fa, r1, wsA, wsB, W, &den_f);
+            rc = launch_colfilter_t(r, s.freq, j);
             break;
         case FreqStage::Transposed:
             if (s.freq_transposes) {
                 rc = launch_transpose<float>(r, im.Aw, im.Bw + s.freq.off, T, Fa, wsA, wsB, W, den_t);
                 if (!rc) rc = launch_transpose<float>(r, im.Ao, im.Bo + s.freq.off, T, Fa, wsA, wsB, W, den_t);
             }
-            if (!rc && r1 > 0) rc = launch_colfilter(r, ColSrc::Images, im.Bw, im.Bo, nullptr, nullptr, im.Bw, im.Bo, Fa, T, r1, wsB, 0, wsB, W, 0, &den_f);
+            if (!rc && r1 > 0) {
+                ColJob c;
+                c.bufW = c.dstW = im.Bw; c.bufO = c.dstO = im.Bo;
+                c.n = Fa; c.C = T; c.rad = r1;
+                c.bws = c.dws = wsB; c.W = W;
+                rc = launch_colfilter(r, s.freq.col, c);
+            }
             break;
     }
     if (rc) return rc;
@@ -2834,16 +2245,8 @@ extern "C" int tri_test_sumthreshold(const float* data, const double* mad, uint8
                    stream, chunk_ends, n_chunk_ends, true);
 }
 
-// The thread-local route overrides of the box filters, saved on entry and restored on exit: a hook that switches routes
-// leaves the flagger's routes as it found them on every return.
-struct RouteOverrides {
-    const int r = g_boxr_override, w = g_boxw_override, p = g_boxp_override, q = g_boxq_override,
-              q8 = g_boxq_b8_override, x = g_boxx_override;
-    ~RouteOverrides() {
-        g_boxr_override = r; g_boxw_override = w; g_boxp_override = p;
-        g_boxq_override = q; g_boxq_b8_override = q8; g_boxx_override = x;
-    }
-};
+// what tri_boxx_last_stats() reports: the K4x pass counters of this thread's last tri_bench_boxfilter(stage 1, variant 4)
+static thread_local unsigned long long g_boxx_last_stats[2] = {0, 0};
 
 // Measurement / test hook: one axis stage of the masked box filter in the launch geometry of
 // the step (see include/tricolour_amd.h).
@@ -2866,18 +2269,21 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     HIPCHK(hipEventCreate(e0.out()));
     HIPCHK(hipEventCreate(e1.out()));
     const size_t N = (size_t)n_line * n_col;
-    const RouteOverrides saved;
-    ScopedSet<bool> unpadded(g_colfilter_unpadded, true);
-    g_boxr_override = variant == 0 ? -1 : (variant == 1 ? 0 : 1);
-    g_boxw_override = variant == 0 ? -1 : 0;            // the named variants run BOTH images through their own kernels
-    // stage 2: 0 = the flagger's route, 1 = register rings, 2 / 3 = stage pipeline with blocks of 16 / 8
-    if (stage == 2) { g_boxr_override = -1; g_boxp_override = variant == 0 ? -1 : (variant == 1 ? 0 : (variant == 2 ? 16 : 8)); }
-    // stage 0: 0 = the flagger's route, 1 = LDS delay lines, 2 = register delay lines (K4r), 3 = stage pipeline (K4q)
-    // (5 = the stage pipeline with blocks of 16 positions wherever 3 takes blocks of 8)
-    if (stage == 0 || stage == 1) {
-        g_boxq_override = variant == 0 ? -1 : (variant == 3 || variant == 5 ? 1 : 0);
-        if (variant == 3 || variant == 5) g_boxr_override = -1;
-        g_boxq_b8_override = variant == 5 ? 0 : -1;
+    // The routes of this call: the flagger's (variant 0), or the variant's own.  They live in this call's Run alone.
+    BoxRoutes& b = r.box;
+    b.unpadded = true;
+    const bool pipe = variant == 3 || variant == 5;
+    if (variant != 0) b.boxw = false;                   // the named variants run BOTH images through their own kernels
+    if (stage == 2) {
+        // stage 2: 0 = the flagger's route, 1 = register rings, 2 / 3 = stage pipeline with blocks of 16 / 8
+        if (variant != 0) b.spec_pipe = variant == 1 ? SpecPipe::Off : (variant == 2 ? SpecPipe::B16 : SpecPipe::B8);
+    } else {
+        // stage 0: 0 = the flagger's route, 1 = LDS delay lines, 2 = register delay lines (K4r), 3 = stage pipeline (K4q)
+        // (5 = the stage pipeline with blocks of 16 positions wherever 3 takes blocks of 8)
+        if (variant != 0) b.pipe_t = b.pipe_f = pipe ? Want::Forced : Want::Off;
+        if (variant != 0 && !pipe) b.reg_rings = variant != 1;
+        if (variant == 5) b.pipe_t_b8 = b.pipe_f_b8 = false;
+        if (variant == 4) b.exact = Want::Forced;       // (at any radius, not only where the flagger takes it)
     }
     int rc = TRI_OK;
     // The stage as one step of the background loop on the hook's images: stage 0 the single sweep from packed flags into
@@ -2892,12 +2298,13 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     if (stage == 0) {
         im.dataTF = data; im.flagsTF = flags4;
         im.Aw = out_w; im.Ao = out_o; im.wsA = N;
+        s.tcol = pick_col_filter(b, ColSrc::PackedFlags, COL_WEIGHTS_01, false, (int)radius, (int)n_line, (int)n_col, n_win, false);
     } else if (stage == 1) {
         im.Aw = const_cast<float*>(reinterpret_cast<const float*>(flags4));   // (read only in a non-final iteration)
         im.Ao = im.Aw + N; im.wsA = 2 * N;
         im.Bw = out_w; im.Bo = out_o; im.wsB = N;
         im.dataFT = data;
-        s.freq = pick_freq_stage((int)radius, (int)n_col, (int)n_line, N, false);
+        s.freq = pick_freq_stage(b, 1, (int)radius, (int)n_col, (int)n_line, n_win, im.Aw, im.Ao, im.wsA, false);
     }
     // stage 1, variant 4: K4x works on rows -- the amplitudes are taken to the TF layout once (untimed), the rows it
     // writes go back to FT inside the timed loop (as in the flagger); out_w doubles as the row buffer.
@@ -2906,16 +2313,15 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     DevBuf<unsigned long long> x_stats;
     int xl = 0;
     if (stage == 1 && variant == 4) {
-        g_boxx_override = 1;
-        xl = boxx_pick_l((int)radius, (int)n_col);      // (forced: at any radius, not only where the flagger takes it)
-        g_boxx_override = -1;
+        xl = boxx_pick_l(b, (int)radius, (int)n_col);
         if (!xl) return set_err(TRI_EUNSUPPORTED, "no exact row filter for radius %d on lines of %d", (int)radius, (int)n_col);
         HIPCHK(x_data_tf.alloc((size_t)n_win * N));
         HIPCHK(x_stats.alloc(2));
         HIPCHK(hipMemsetAsync(x_stats.get(), 0, 2 * sizeof(unsigned long long), r.st));
         rc = launch_transpose<float>(r, data, x_data_tf.get(), (int)n_col, (int)n_line, N, N, n_win);
         if (rc) return rc;
-        s.freq = {FreqStage::ExactRows, 0, xl, 0};
+        s.freq = FreqPick();
+        s.freq.route = FreqStage::ExactRows; s.freq.xl = xl;
         im.dataTF = x_data_tf.get(); im.rows = out_w; im.ws_rows = N; im.xstats = x_stats.get();
     }
     if (stage == 1 && s.freq.route == FreqStage::Transposed)
@@ -2924,8 +2330,12 @@ extern "C" int tri_bench_boxfilter(const float* data, const uint8_t* flags4, flo
     for (int i = 0; i < repeats && rc == TRI_OK; i++) {
         if (stage == 2) {
             // spectrum path: byte flags [n_line][n_col] + data -> filtered weight and data images
-            if (variant >= 2 && boxp_pick_block((int)radius, (int)n_col) == 0) rc = set_err(TRI_EUNSUPPORTED, "no stage pipeline for this shape");
-            else rc = launch_colfilter(r, ColSrc::ByteFlags, out_w, out_o, data, flags4, out_w, out_o, (int)n_line, (int)n_col, (int)radius, 0, 0, 0, 1, COL_WEIGHTS_01);
+            ColJob j;
+            j.srcData = data; j.srcFlags = flags4;
+            j.bufW = j.dstW = out_w; j.bufO = j.dstO = out_o;
+            j.n = (int)n_line; j.C = (int)n_col; j.rad = (int)radius;
+            if (variant >= 2 && boxp_pick_block(b, j.rad, j.C) == 0) rc = set_err(TRI_EUNSUPPORTED, "no stage pipeline for this shape");
+            else rc = launch_colfilter(r, pick_col_filter(b, ColSrc::ByteFlags, COL_WEIGHTS_01, false, j.rad, j.n, j.C, 1, spectrum_aligned(j)), j);
         } else if (stage == 0) {
             float den_t;
             rc = bg_time_stage(r, s, im, bst, &den_t);
