@@ -856,6 +856,74 @@ int tri_median_zscore_threshold(const void *vis, int vis_dtype, const uint8_t *f
                                 int64_t min_samples, double nsigma, int64_t rounds,
                                 float *residual, float *zscore, void *stream);
 
+/*
+ * Antenna integration (beyond the reference; the models are CASA's antint mode
+ * and AOFlagger's antenna selection, the definition is this library's own):
+ * baseline integration with one image per antenna instead of one for all
+ * baselines, and a flags-only variant that extends the flags of an antenna
+ * whose baselines are mostly flagged.  vis (nbl, n) complex64 or float32
+ * amplitudes, flags (nbl, n) uint8 (nonzero = flagged), n = ncorr * ntime *
+ * nchan, i a position in [0, n).  Baseline b has the antennas ant1[b], ant2[b].
+ *   membership: baseline b is a member of antenna a if it is selected, is not an
+ *              auto-correlation where those are excluded, and ant1[b] == a or
+ *              ant2[b] == a; an auto-correlation that takes part is a member of
+ *              its antenna once.  members[a] is their number and list[a] the
+ *              members in ascending b.  The caller builds the lists on the host
+ *              in CSR form: list[a] = baselines[offsets[a] .. offsets[a + 1]),
+ *              offsets[nant + 1] and baselines[] int32 on the device, offsets
+ *              never decreasing and inside baselines[].
+ *   a        = +inf if re or im is infinite, else (float)sqrt((double)re * re
+ *              + (double)im * im)   (fabsf(v) for amplitudes), exactly as in
+ *              baseline integration; a sample counts if its flag is 0 and a is
+ *              not NaN
+ *   tri_antenna_accumulate: for every antenna a, b over list[a] in list order
+ *              and every counting sample sum[a, i] += (double)a, count[a, i]
+ *              += 1; sum float64 and count int32 of shape (nant, n).  One
+ *              thread per (a, i), no atomics, no re-association.  A list entry
+ *              outside [0, nbl) is skipped.  The call ADDS to sum and count
+ *              (the caller zeroes them first), so the baselines fed in several
+ *              calls in ascending order, each call with the lists of its own
+ *              baselines, give the bits of one call.  vis == NULL is the
+ *              flags-only form: a sample counts if its flag is 0, vis_dtype is
+ *              not read, sum is not touched and may be NULL.
+ *   tri_antenna_mean: flag[a, i] = count[a, i] < min_count[a];  amp[a, i] =
+ *              (float)(sum[a, i] / (double)count[a, i]) where flag is 0, else 0.
+ *              min_count[nant] int32 on the device; the caller computes
+ *              min_count[a] = max(1, ceil(min_baseline_frac * members[a])), and
+ *              a value below 1 counts as 1, so an antenna without members is
+ *              flagged throughout.
+ *   (the flagger: tri_sum_threshold_flagger on amp / flag as one float32 block
+ *   of nant * ncorr windows gives det[nant, n])
+ *   tri_antenna_flag_excess: det[a, i] = members[a] > 0 && members[a] -
+ *              count[a, i] > max_flagged[a], with count of the flags-only
+ *              form; members[nant], max_flagged[nant] int32 on the device; the
+ *              caller computes max_flagged[a] = floor(min_flagged_frac *
+ *              members[a]).  Integers only.
+ *   tri_antenna_broadcast_or: out[b, i] = (flags[b, i] != 0) | (det[ant1[b], i]
+ *              != 0) | (det[ant2[b], i] != 0) for EVERY baseline, whether it is
+ *              a member of anything or not; ant1[nbl], ant2[nbl] int32 on the
+ *              device; an antenna number outside [0, nant) contributes
+ *              nothing.  out may be flags itself.
+ * TRI_EINVAL for NULL pointers (other than those named), negative sizes, det
+ * overlapping count, out overlapping det (or overlapping flags without being
+ * flags); TRI_EUNSUPPORTED for dtypes other than complex64 and float32, more
+ * than 65535 antennas and images beyond the index range.  No workspace.  Empty
+ * shapes return TRI_OK without a launch.
+ */
+int tri_antenna_accumulate(const void *vis /* may be NULL */, int vis_dtype,
+                           const uint8_t *flags, const int32_t *offsets,
+                           const int32_t *baselines, int64_t nbl, int64_t nant,
+                           int64_t n, double *sum /* may be NULL without vis */,
+                           int32_t *count, void *stream);
+int tri_antenna_mean(const double *sum, const int32_t *count, const int32_t *min_count,
+                     int64_t nant, int64_t n, float *amp, uint8_t *flag, void *stream);
+int tri_antenna_flag_excess(const int32_t *count, const int32_t *members,
+                            const int32_t *max_flagged, int64_t nant, int64_t n,
+                            uint8_t *det, void *stream);
+int tri_antenna_broadcast_or(const uint8_t *flags, const uint8_t *det,
+                             const int32_t *ant1, const int32_t *ant2, uint8_t *out,
+                             int64_t nbl, int64_t nant, int64_t n, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

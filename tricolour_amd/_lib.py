@@ -239,6 +239,14 @@ _SIGNATURES = {
     "tri_median_zscore_threshold": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                               C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    "tri_antenna_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tri_antenna_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "tri_antenna_flag_excess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_void_p]),
+    "tri_antenna_broadcast_or": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_int64, C.c_int64, C.c_void_p]),
     "tri_last_error": (C.c_char_p, []),
     "tri_version": (C.c_int, []),
     "tri_bench_sumthreshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

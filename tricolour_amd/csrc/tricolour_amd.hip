@@ -35,6 +35,7 @@
 #include "steps/quality/kernels_quality.hpp"
 #include "steps/hist/kernels_hist.hpp"
 #include "steps/medz/kernels_medz.hpp"
+#include "steps/antint/kernels_antint.hpp"
 
 // ===========================================================================
 // host side
@@ -2784,3 +2785,4 @@ extern "C" int tri_uvcontsub_flagger_debug(const void* vis_c64, const uint8_t* f
 #include "steps/quality/quality_host.hpp"
 #include "steps/hist/hist_host.hpp"
 #include "steps/medz/medz_host.hpp"
+#include "steps/antint/antint_host.hpp"

@@ -1454,6 +1454,283 @@ def baseline_integrated_flagger(vis, flags, select=None, min_baseline_frac=0.25,
     return _like_flags(torch, out, flags, from_numpy)
 
 
+# ---------------------------------------------------------------------------
+# Antenna integration: baseline integration with one image per antenna, and the
+# flag excess of an antenna's baselines.  Python and C calls, not strategy tasks.
+# ---------------------------------------------------------------------------
+ANT_MAX_ANTENNAS = 65535
+
+
+def _ant_ubl(ubl, nbl=None):
+    ubl = np.asarray(ubl)
+    if ubl.ndim != 2 or ubl.shape[1] != 3:
+        raise ValueError("ubl must have shape (nbl, 3): (index, ant1, ant2) per baseline, got %s" % (ubl.shape,))
+    if ubl.dtype.kind not in "iu":
+        raise TypeError("ubl must hold integers, got %s" % ubl.dtype)
+    if nbl is not None and ubl.shape[0] != nbl:
+        raise ValueError("ubl must have one row per baseline (%d), got %d" % (nbl, ubl.shape[0]))
+    return ubl
+
+
+def antenna_baselines(ubl, nant=None, select=None, exclude_autos=True):
+    """The per-antenna member lists of the antenna-integration calls, from
+    ``ubl (nbl, 3)`` = (index, ant1, ant2) per baseline.  Baseline ``b`` is a
+    member of antenna ``a`` if it is selected (``select``, one entry per
+    baseline, nonzero = takes part; None: all), is not an auto-correlation
+    where ``exclude_autos`` is set, and ``ant1[b] == a`` or ``ant2[b] == a``;
+    an auto-correlation that takes part is a member of its antenna once.
+    ``nant`` defaults to ``max(ant1, ant2) + 1``; a larger value is allowed and
+    gives antennas without members.  Returns numpy int32 arrays ``(offsets
+    (nant + 1), baselines, members (nant), ant1 (nbl), ant2 (nbl))``: the
+    members of ``a`` are ``baselines[offsets[a]:offsets[a + 1]]`` in ascending
+    order.  Pure host code; needs no device."""
+    ubl = _ant_ubl(ubl)
+    nbl = ubl.shape[0]
+    a1, a2 = ubl[:, 1].astype(np.int64), ubl[:, 2].astype(np.int64)
+    if nbl and (a1.min() < 0 or a2.min() < 0):
+        raise ValueError("ubl holds a negative antenna number")
+    need = int(max(a1.max(), a2.max())) + 1 if nbl else 0
+    if nant is None:
+        nant = need
+    elif isinstance(nant, bool) or not isinstance(nant, (int, np.integer)):
+        raise TypeError("nant must be an integer, got %r" % (nant,))
+    elif nant < need:
+        raise ValueError("nant = %d is below the largest antenna number + 1 = %d" % (nant, need))
+    nant = int(nant)
+    if nant > ANT_MAX_ANTENNAS:
+        raise ValueError("nant = %d is above the %d antennas one call holds" % (nant, ANT_MAX_ANTENNAS))
+    take = np.ones(nbl, bool)
+    if select is not None:
+        select = np.asarray(select.cpu() if hasattr(select, "cpu") else select)
+        if select.shape != (nbl,):
+            raise ValueError("select must have one entry per baseline (%d), got shape %s" % (nbl, select.shape))
+        take = select != 0
+    if exclude_autos:
+        take = take & (a1 != a2)
+    b = np.nonzero(take)[0]
+    second = a2[b] != a1[b]                                    # an auto-correlation is a member once
+    ants = np.concatenate([a1[b], a2[b][second]])
+    bls = np.concatenate([b, b[second]])
+    order = np.lexsort((bls, ants))                            # by antenna, ascending baseline within
+    members = np.bincount(ants, minlength=nant).astype(np.int32)
+    offsets = np.concatenate([[0], np.cumsum(members)]).astype(np.int32)
+    return offsets, bls[order].astype(np.int32), members, a1.astype(np.int32), a2.astype(np.int32)
+
+
+def _ant_fraction(name, frac):
+    value = float(frac)
+    if not 0.0 <= value <= 1.0:               # also rejects NaN
+        raise ValueError("%s must lie in [0, 1], got %r" % (name, frac))
+    return value
+
+
+def _ant_flags_inputs(flags, ubl, nant, select, exclude_autos):
+    """Checks of the flags-only calls (all before any device work), then (torch, flags uint8 on the device, from_numpy,
+    device, the host lists of antenna_baselines)."""
+    shape = tuple(flags.shape)
+    if len(shape) != 4:
+        raise ValueError("flags must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    lists = antenna_baselines(_ant_ubl(ubl, shape[0]), nant, select, exclude_autos)
+    torch = _require_gpu()
+    device = flags.device if (torch.is_tensor(flags) and flags.is_cuda) else \
+        torch.device("cuda", torch.cuda.current_device())
+    return torch, _flags_u8(torch, flags, device), isinstance(flags, np.ndarray), device, lists
+
+
+def _ant_inputs(name, vis, flags, ubl, nant, select, exclude_autos):
+    """Checks of the antenna-integration calls that read visibilities (all before any device work), then (torch, vis,
+    flags uint8, dtype code, from_numpy, device, the host lists of antenna_baselines)."""
+    shape = tuple(vis.shape)
+    if len(shape) != 4:
+        raise ValueError("vis must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    if tuple(flags.shape) != shape:
+        raise ValueError("vis and flags must have the same shape, got %s and %s" % (shape, tuple(flags.shape)))
+    if str(vis.dtype).replace("torch.", "") not in ("complex64", "float32"):
+        raise TypeError("tricolour_amd.%s: visibilities must be complex64 or float32 (got %s)" % (name, vis.dtype))
+    lists = antenna_baselines(_ant_ubl(ubl, shape[0]), nant, select, exclude_autos)
+    torch = _require_gpu()
+    return (torch,) + _as_device_inputs(torch, vis, flags) + (lists,)
+
+
+def _ant_dev(torch, device, a):
+    """A host int32 list on the device; never empty, so that its address is one."""
+    a = np.ascontiguousarray(a, np.int32)
+    return torch.from_numpy(a if a.size else np.zeros(1, np.int32)).to(device)
+
+
+def _ant_accumulate(torch, lib, device, v, f8, code, lists, acc):
+    """(sum float64 or None, count int32) of shape (ant, corr, time, chan) on the device: new tensors, continued from
+    `acc`.  v None: the flags-only count (acc: an earlier count)."""
+    offsets, baselines, members = lists[:3]
+    nbl, nant = int(f8.shape[0]), len(members)
+    img = (nant,) + tuple(int(s) for s in f8.shape[1:])
+    if v is None:
+        total, count = None, torch.zeros(img, dtype=torch.int32, device=device)
+    else:
+        total, count = _acc_pair(torch, device, img, acc)
+    if count.numel() > 0 and nbl > 0:
+        off, bls = _ant_dev(torch, device, offsets), _ant_dev(torch, device, baselines)
+        _lib.check(lib.tri_antenna_accumulate(
+            None if v is None else v.data_ptr(), code, f8.data_ptr(), off.data_ptr(), bls.data_ptr(), nbl, nant,
+            count.numel() // nant, None if total is None else total.data_ptr(), count.data_ptr(),
+            torch.cuda.current_stream(device).cuda_stream))
+    return total, count
+
+
+def _ant_mean(torch, lib, device, total, count, members, frac):
+    amp = torch.empty(total.shape, dtype=torch.float32, device=device)
+    flag = torch.empty(total.shape, dtype=torch.uint8, device=device)
+    if total.numel() > 0:
+        min_count = np.maximum(1, np.ceil(frac * members.astype(np.float64))).astype(np.int32)
+        mc = _ant_dev(torch, device, min_count)
+        _lib.check(lib.tri_antenna_mean(total.data_ptr(), count.data_ptr(), mc.data_ptr(), len(members),
+                                        total.numel() // len(members), amp.data_ptr(), flag.data_ptr(),
+                                        torch.cuda.current_stream(device).cuda_stream))
+    return amp, flag
+
+
+def _ant_broadcast(torch, lib, device, f8, det8, ant1, ant2):
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    if out.numel() > 0:
+        nbl, nant = int(f8.shape[0]), int(det8.shape[0])
+        a1, a2 = _ant_dev(torch, device, ant1), _ant_dev(torch, device, ant2)
+        _lib.check(lib.tri_antenna_broadcast_or(f8.data_ptr(), det8.data_ptr() if det8.numel() else None, a1.data_ptr(),
+                                                a2.data_ptr(), out.data_ptr(), nbl, nant, out.numel() // nbl,
+                                                torch.cuda.current_stream(device).cuda_stream))
+    return out
+
+
+def antenna_integral(vis, flags, ubl, nant=None, select=None, exclude_autos=True, acc=None):
+    """Sum and count per antenna of the amplitudes of (bl, corr, time, chan)
+    visibilities: :func:`baseline_integral` over the members of each antenna
+    (:func:`antenna_baselines`) in ascending baseline order.  Returns ``(sum
+    float64, count int32)`` of shape (ant, corr, time, chan) -- numpy arrays
+    for numpy input, tensors on the device otherwise.  ``acc``: an earlier
+    result to continue from (not modified; the result is a new pair): baseline
+    chunks fed in ascending order, each call with its chunk's own ``ubl`` and
+    the scan's ``nant``, give the bits of one call.  One thread owns a position
+    of an antenna and sums in list order, so the result is reproducible bit
+    for bit.  Every sample is read once per antenna it belongs to.  Inputs are
+    not modified."""
+    torch, v, f8, code, from_numpy, device, lists = _ant_inputs("antenna_integral", vis, flags, ubl, nant, select,
+                                                                exclude_autos)
+    with torch.cuda.device(device):
+        total, count = _ant_accumulate(torch, _lib.lib(), device, v, f8, code, lists, acc)
+    return _like_input(from_numpy, total, count)
+
+
+def antenna_mean_amplitude(vis, flags, ubl, nant=None, select=None, exclude_autos=True, min_baseline_frac=0.0):
+    """Mean amplitude per antenna: :func:`antenna_integral`'s ``float32(sum /
+    count)`` per (ant, corr, time, chan) position.  A position that fewer than
+    ``max(1, ceil(min_baseline_frac * members[ant]))`` baselines count at is
+    flagged, with amplitude 0; an antenna without members is flagged
+    throughout.  Returns ``(amp float32, flag bool)`` -- numpy arrays for numpy
+    input, tensors on the device otherwise.  Inputs are not modified."""
+    frac = _ant_fraction("min_baseline_frac", min_baseline_frac)
+    torch, v, f8, code, from_numpy, device, lists = _ant_inputs("antenna_mean_amplitude", vis, flags, ubl, nant, select,
+                                                                exclude_autos)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        total, count = _ant_accumulate(torch, lib, device, v, f8, code, lists, None)
+        amp, flag = _ant_mean(torch, lib, device, total, count, lists[2], frac)
+    return _like_input(from_numpy, amp, flag.view(torch.bool))
+
+
+def antenna_integrated_flagger(vis, flags, ubl, nant=None, select=None, exclude_autos=True, min_baseline_frac=0.25,
+                               **sum_threshold_kwargs):
+    """SumThreshold on the antenna-integrated images: :func:`antenna_mean_amplitude`
+    gives one (corr, time, chan) float32 image per antenna, whose noise falls
+    as 1 / sqrt(members); :func:`sum_threshold_flagger` (``sum_threshold_kwargs``)
+    flags them as an (ant, corr, time, chan) block; the detections of its two
+    antennas are ORed into the flags of EVERY baseline, member of anything or
+    not: ``out[b] = (flags[b] != 0) | det[ant1[b]] | det[ant2[b]]``.  Finds a
+    fault that sits on the baselines of one antenna, too faint for each
+    baseline alone and diluted over all baselines together.  Returns a new
+    array in the container / dtype of ``flags``; the inputs are not modified.
+    A Python call, not a strategy task."""
+    frac = _ant_fraction("min_baseline_frac", min_baseline_frac)
+    torch, v, f8, code, from_numpy, device, lists = _ant_inputs("antenna_integrated_flagger", vis, flags, ubl, nant,
+                                                                select, exclude_autos)
+    lib = _lib.lib()
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            total, count = _ant_accumulate(torch, lib, device, v, f8, code, lists, None)
+            amp, flag = _ant_mean(torch, lib, device, total, count, lists[2], frac)
+            del total, count
+            det = sum_threshold_flagger(amp, flag, **sum_threshold_kwargs)
+            out = _ant_broadcast(torch, lib, device, f8, _flags_u8(torch, det, device), lists[3], lists[4])
+    return _like_flags(torch, out, flags, from_numpy)
+
+
+def antenna_flagged_counts(flags, ubl, nant=None, select=None, exclude_autos=True):
+    """How many of each antenna's member baselines (:func:`antenna_baselines`)
+    are flagged at every (corr, time, chan) position.  No visibilities are
+    read.  Returns ``(flagged int32 (ant, corr, time, chan), members int32
+    (ant))`` -- numpy arrays for numpy input, tensors on the device otherwise."""
+    torch, f8, from_numpy, device, lists = _ant_flags_inputs(flags, ubl, nant, select, exclude_autos)
+    with torch.cuda.device(device):
+        _, count = _ant_accumulate(torch, _lib.lib(), device, None, f8, 0, lists, None)
+        members = torch.from_numpy(lists[2]).to(device)
+        flagged = members.view(-1, 1, 1, 1) - count
+    return _like_input(from_numpy, flagged, members)
+
+
+def extend_flags_by_antenna(flags, ubl, nant=None, select=None, exclude_autos=True, min_flagged_frac=0.6):
+    """Extends the flags of an antenna whose baselines are mostly flagged (after
+    CASA's ``antint`` mode): where more than ``floor(min_flagged_frac *
+    members[ant])`` of an antenna's member baselines are flagged at a (corr,
+    time, chan) position, the position is flagged on EVERY baseline of that
+    antenna: ``out[b] = (flags[b] != 0) | det[ant1[b]] | det[ant2[b]]``.
+    ``min_flagged_frac`` lies in [0, 1]; 1.0 never adds a flag.  Flags only: no
+    visibilities are read.  Returns a new array in the container / dtype of
+    ``flags``; the input is not modified.  A Python call, not a strategy task."""
+    frac = _ant_fraction("min_flagged_frac", min_flagged_frac)
+    torch, f8, from_numpy, device, lists = _ant_flags_inputs(flags, ubl, nant, select, exclude_autos)
+    lib = _lib.lib()
+    members = lists[2]
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            _, count = _ant_accumulate(torch, lib, device, None, f8, 0, lists, None)
+            max_flagged = np.floor(frac * members.astype(np.float64)).astype(np.int32)
+            det = torch.empty(count.shape, dtype=torch.uint8, device=device)
+            mem, mf = _ant_dev(torch, device, members), _ant_dev(torch, device, max_flagged)
+            _lib.check(lib.tri_antenna_flag_excess(count.data_ptr(), mem.data_ptr(), mf.data_ptr(), len(members),
+                                                   count.numel() // len(members), det.data_ptr(),
+                                                   torch.cuda.current_stream(device).cuda_stream))
+            out = _ant_broadcast(torch, lib, device, f8, det, lists[3], lists[4])
+    return _like_flags(torch, out, flags, from_numpy)
+
+
+def antenna_broadcast_or(flags, det, ubl, nant=None):
+    """``out[b] = (flags[b] != 0) | (det[ant1[b]] != 0) | (det[ant2[b]] != 0)``
+    for (bl, corr, time, chan) flags and per-antenna detections ``det`` of
+    shape (ant, corr, time, chan); ``nant``, if given, is ``det.shape[0]``.  An
+    antenna number of ``ubl`` outside ``[0, nant)`` contributes nothing.
+    Returns a new array in the container / dtype of ``flags``; the inputs are
+    not modified."""
+    shape, dshape = tuple(flags.shape), tuple(det.shape)
+    if len(shape) != 4:
+        raise ValueError("flags must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    if len(dshape) != 4 or dshape[1:] != shape[1:]:
+        raise ValueError("det must have shape (ant,) + %s, got %s" % (shape[1:], dshape))
+    if nant is not None and int(nant) != dshape[0]:
+        raise ValueError("nant = %r is not the number of det images (%d)" % (nant, dshape[0]))
+    if dshape[0] > ANT_MAX_ANTENNAS:
+        raise ValueError("nant = %d is above the %d antennas one call holds" % (dshape[0], ANT_MAX_ANTENNAS))
+    ubl = _ant_ubl(ubl, shape[0])
+    # (clipped into int32: a number beyond it stays outside every antenna range)
+    a1, a2 = (np.clip(ubl[:, k].astype(np.int64), -1, np.iinfo(np.int32).max).astype(np.int32) for k in (1, 2))
+    torch = _require_gpu()
+    device = flags.device if (torch.is_tensor(flags) and flags.is_cuda) else \
+        torch.device("cuda", torch.cuda.current_device())
+    f8, det8 = _flags_u8(torch, flags, device), _flags_u8(torch, det, device)
+    with torch.cuda.device(device):
+        out = _ant_broadcast(torch, _lib.lib(), device, f8, det8, a1, a2)
+    return _like_flags(torch, out, flags, isinstance(flags, np.ndarray))
+
+
 INS_MAX_SHAPES = 32
 
 
