@@ -924,6 +924,82 @@ int tri_antenna_broadcast_or(const uint8_t *flags, const uint8_t *det,
                              const int32_t *ant1, const int32_t *ant2, uint8_t *out,
                              int64_t nbl, int64_t nant, int64_t n, void *stream);
 
+/*
+ * Spectral kurtosis along time (beyond the reference; the estimator is Nita &
+ * Gary 2010, the definition with its operation order is this library's own).
+ * It asks whether the statistics of a channel over a stretch of time are those
+ * of noise, and flags whole (block of rows, channel) cells where they are not:
+ * pulsed interference pushes the estimator well above 1, a steady carrier
+ * towards 0.  It needs no background, no noise estimate and no bandpass.
+ * vis (n_win, ntime, nchan) complex64 or float32, flags of the same shape,
+ * any non-zero byte is flagged; windows are independent.
+ *   power:   arithmetic is float64, the operation order below is the
+ *            definition, nothing is fused.  complex64: p = (double)re *
+ *            (double)re + (double)im * (double)im (both products exact, one
+ *            rounding).  float32: p = (double)x * (double)x.  A sample is valid
+ *            when its flag is 0 and p is finite; a NaN or infinite part makes
+ *            it invalid.
+ *   blocks:  block_time = M is an integer in [2, 65536].  Block b holds the rows
+ *            [b*M, min(T, (b+1)*M)), so there are nb = ceil(T / M) blocks.
+ *   sums:    for every window, block and channel, walk the block's rows in
+ *            ascending time order, starting from n = 0, S1 = +0.0, S2 = +0.0.
+ *            For each valid sample: n += 1; S1 = S1 + p; S2 = S2 + (p * p), the
+ *            product rounded before the add.  The order is sequential.  A tree
+ *            or pairwise sum is a different result and is wrong.
+ *   estimator: with d = shape (a finite double greater than 0; it is 1 for raw
+ *            correlator dumps and N for data that is already an average of N):
+ *              q  = ((double)n * S2) / (S1 * S1)
+ *              k  = (((double)n * d + 1.0) / ((double)n - 1.0)) * (q - 1.0)
+ *              sk = (float)k
+ *            sk is the NaN 0x7FC00000 in two cases: n < min_samples
+ *            (min_samples is an integer in [2, M]; a last block with fewer
+ *            than min_samples rows never reaches it and is never hit), and
+ *            S1 * S1 not greater than 0 (all-zero data, underflow).  Any other
+ *            NaN is also written as 0x7FC00000.  Under a gamma law of shape d,
+ *            which exponential power is with d = 1, the expectation of k is 1.
+ *   outputs of the statistics pass: sk float32 (n_win, nb, nchan); count int32
+ *            of the same shape, holding n.  Every element of both is written.
+ *   decision: two tables of M + 1 doubles, lower[n] and upper[n], indexed by
+ *            the valid count.  hit = (double)sk < lower[n] || (double)sk >
+ *            upper[n].  A NaN sk never hits.  A NaN table entry never hits:
+ *            that is how a side is switched off.  A count outside [0, M]
+ *            (tri_sk_apply takes any) never hits.
+ *            out[w, t, f] = (flags[w, t, f] != 0) | hit[w, t / M, f], 0 or 1.
+ *            The inputs are never written.  A second round cannot change
+ *            anything, because a hit block has no valid sample left: there is
+ *            no rounds argument.
+ * tri_sk_statistics writes sk and, unless NULL, count.  tri_sk_apply takes the
+ * statistics back in.  tri_sk_threshold runs both; sk and count are required
+ * and are OUTPUTS.  lower and upper are device pointers to block_time + 1
+ * doubles each; they belong to the caller and are read only.  There is no
+ * workspace: all buffers are the caller's.  The sums run in the order above
+ * whatever the alignment and however the windows are split over calls: the
+ * same bits on every run.
+ * TRI_EINVAL for NULL pointers (other than count of tri_sk_statistics),
+ * negative shapes, block_time, shape or min_samples out of range or NaN, and
+ * any output overlapping an input or another output; TRI_EUNSUPPORTED for vis
+ * dtypes other than complex64 and float32 and for more cells than one launch
+ * holds (pass fewer windows per call).  Empty shapes return TRI_OK without a
+ * launch.
+ */
+int tri_sk_statistics(const void *vis, int vis_dtype, const uint8_t *flags,
+                      int64_t n_win, int64_t ntime, int64_t nchan,
+                      int64_t block_time, double shape, int64_t min_samples,
+                      float *sk, int32_t *count /* may be NULL */,
+                      void *stream);
+int tri_sk_apply(const float *sk, const int32_t *count, const uint8_t *flags,
+                 uint8_t *out_flags,
+                 int64_t n_win, int64_t ntime, int64_t nchan, int64_t block_time,
+                 const double *lower, const double *upper,
+                 void *stream);
+int tri_sk_threshold(const void *vis, int vis_dtype, const uint8_t *flags,
+                     uint8_t *out_flags,
+                     int64_t n_win, int64_t ntime, int64_t nchan,
+                     int64_t block_time, double shape, int64_t min_samples,
+                     const double *lower, const double *upper,
+                     float *sk, int32_t *count,
+                     void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

@@ -36,6 +36,7 @@
 #include "steps/hist/kernels_hist.hpp"
 #include "steps/medz/kernels_medz.hpp"
 #include "steps/antint/kernels_antint.hpp"
+#include "steps/sk/kernels_sk.hpp"
 
 // ===========================================================================
 // host side
@@ -2786,3 +2787,4 @@ extern "C" int tri_uvcontsub_flagger_debug(const void* vis_c64, const uint8_t* f
 #include "steps/hist/hist_host.hpp"
 #include "steps/medz/medz_host.hpp"
 #include "steps/antint/antint_host.hpp"
+#include "steps/sk/sk_host.hpp"

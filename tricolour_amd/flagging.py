@@ -1312,6 +1312,218 @@ def threshold_median_zscore(vis, flags, nsigma=6.0, radius_time=8, radius_freq=8
     return _like_flags(torch, out, flags, from_numpy)
 
 
+SK_MAX_BLOCK = 65536        # largest block_time of the spectral-kurtosis step
+
+
+def _sk_block(block_time):
+    m = _medz_int("block_time", block_time)
+    if m is None or not 2 <= m <= SK_MAX_BLOCK:
+        raise ValueError("block_time must be an integer in [2, %d], got %r" % (SK_MAX_BLOCK, block_time))
+    return m
+
+
+def _sk_nsigma(name, v):
+    """``None`` (the side is off) or a float > 0."""
+    if v is None:
+        return None
+    try:
+        ok = not isinstance(v, bool) and 0.0 < float(v) < float("inf")       # also rejects NaN
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be None or a finite number > 0, got %r" % (name, v))
+    return float(v)
+
+
+def _sk_params(block_time, shape, min_samples):
+    m = _sk_block(block_time)
+    try:
+        ok = not isinstance(shape, bool) and 0.0 < float(shape) < float("inf")    # also rejects NaN
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("shape must be a finite number > 0, got %r" % (shape,))
+    if min_samples is None:
+        ms = max(2, m // 2)
+    else:
+        ms = _medz_int("min_samples", min_samples)
+        if ms is None or not 2 <= ms <= m:
+            raise ValueError("min_samples must be an integer in [2, %d], got %r" % (m, min_samples))
+    return m, float(shape), ms
+
+
+def check_spectral_kurtosis_kwargs(block_time=64, shape=1.0, min_samples=None, nsigma_low=4.0, nsigma_high=4.0):
+    """The argument checks of :func:`threshold_spectral_kurtosis` (no device work): ``block_time`` that is no integer in
+    [2, 65536], ``shape`` that is not a finite number > 0, ``min_samples`` that is no integer in [2, block_time] and an
+    ``nsigma_low`` / ``nsigma_high`` that is neither ``None`` nor a finite number > 0 raise ``ValueError`` naming the
+    argument; booleans are no numbers here.  Returns the values, ``min_samples`` resolved (``None``: half a block, at
+    least 2)."""
+    m, d, ms = _sk_params(block_time, shape, min_samples)
+    return m, d, ms, _sk_nsigma("nsigma_low", nsigma_low), _sk_nsigma("nsigma_high", nsigma_high)
+
+
+def spectral_kurtosis_bounds(block_time, shape=1.0, nsigma_low=4.0, nsigma_high=4.0):
+    """The default decision tables of the spectral-kurtosis step, ``(lower, upper)``: ``block_time + 1`` float64
+    each, indexed by a cell's valid count ``n``.  With ``d = shape``, for ``n >= 2``:
+    ``sigma(n) = sqrt(2 d (d + 1) n^2 / ((n - 1)(n d + 2)(n d + 3)))`` (the estimator's standard deviation under a
+    gamma law of shape ``d``), ``lower[n] = exp(-nsigma_low * sigma(n))`` and ``upper[n] = exp(+nsigma_high *
+    sigma(n))``: symmetric in ``ln sk``, as the estimator's skewed distribution nearly is, not in ``sk``.  The entries
+    for ``n < 2`` are NaN, and a side given as ``None`` is NaN throughout: a NaN entry never hits.  Host arithmetic in
+    NumPy float64."""
+    m, d, _, lo, hi = check_spectral_kurtosis_kwargs(block_time, shape, None, nsigma_low, nsigma_high)
+    n = np.arange(m + 1, dtype=np.float64)
+    lower = np.full(m + 1, np.nan)
+    upper = np.full(m + 1, np.nan)
+    k = n[2:]
+    sigma = np.sqrt(2.0 * d * (d + 1.0) * k * k / ((k - 1.0) * (k * d + 2.0) * (k * d + 3.0)))
+    if lo is not None:
+        lower[2:] = np.exp(-lo * sigma)
+    if hi is not None:
+        upper[2:] = np.exp(hi * sigma)
+    return lower, upper
+
+
+def _sk_tables(bounds, m):
+    """``bounds = (lower, upper)`` as two float64 arrays of ``m + 1`` entries (any values: NaN switches an entry off)."""
+    try:
+        lower, upper = bounds
+        lower, upper = np.array(lower, np.float64), np.array(upper, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("bounds must be a pair (lower, upper) of arrays of numbers") from None
+    for name, t in (("lower", lower), ("upper", upper)):
+        if t.shape != (m + 1,):
+            raise ValueError("bounds: %s must hold block_time + 1 = %d entries, got shape %s" % (name, m + 1, t.shape))
+    return lower, upper
+
+
+def _sk_cap(ntime, nchan, m):
+    """Windows one launch of the spectral-kurtosis family holds (every launch is one-dimensional and holds fewer than
+    2^31 blocks; the apply pass has the most: one per block of rows, 16 rows of it and 256 channels)."""
+    return ((1 << 31) - 1) // (-(-ntime // m) * -(-m // 16) * -(-nchan // 256))
+
+
+def _sk_launches(torch, device, n_win, ntime, nchan, m, max_windows):
+    """The batches of a spectral-kurtosis call (there is no workspace to size them against) as a list of ``(at, b)``,
+    and the stream."""
+    launches, (_, _, stream) = _window_launches(torch, device, n_win, lambda b: 0, _sk_cap(ntime, nchan, m),
+                                                max_windows, workspace=False)
+    return list(launches), stream
+
+
+def spectral_kurtosis(vis, flags, block_time=64, shape=1.0, min_samples=None, _max_windows=None):
+    """Spectral kurtosis (Nita & Gary 2010) of (bl, corr, time, chan) windows
+    over tiled blocks of ``block_time`` rows: per block and channel, with ``n``
+    the number of unflagged, finite samples and ``S1``, ``S2`` the sums of their
+    powers and squared powers (float64, rows in ascending order),
+    ``sk = ((n d + 1) / (n - 1)) (n S2 / S1^2 - 1)`` with ``d = shape``: 1 for
+    raw correlator dumps, N for data that is already an average of N.  Its
+    expectation on noise is 1 whatever the level; pulsed interference pushes it
+    up, a steady carrier towards 0.  NaN where ``n < min_samples`` (``None``:
+    half a block) or the powers sum to 0.  Definition:
+    ``include/tricolour_amd.h``.  Returns ``(sk float32, count int32)`` of shape
+    (bl, corr, ceil(time / block_time), chan) -- numpy arrays for numpy input,
+    tensors on the device otherwise.  Inputs are not modified."""
+    m, d, ms = _sk_params(block_time, shape, min_samples)
+    torch, v, f8, code, from_numpy, device = _medz_inputs("spectral_kurtosis", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    nb = -(-ntime // m)
+    sk = torch.empty((nbl, ncorr, nb, nchan), dtype=torch.float32, device=device)
+    cnt = torch.empty((nbl, ncorr, nb, nchan), dtype=torch.int32, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            launches, stream = _sk_launches(torch, device, n_win, ntime, nchan, m, _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_sk_statistics(at(v), code, at(f8), b, ntime, nchan, m, d, ms, at(sk), at(cnt), stream))
+    return _like_input(from_numpy, sk, cnt)
+
+
+def apply_spectral_kurtosis(sk, count, flags, block_time, bounds, _max_windows=None):
+    """Flags whole (block, channel) cells on statistics of
+    :func:`spectral_kurtosis`: with ``bounds = (lower, upper)``, two tables of
+    ``block_time + 1`` numbers indexed by a cell's count ``n`` (the defaults:
+    :func:`spectral_kurtosis_bounds`; Pearson-type or Monte-Carlo bounds go in
+    the same way), a cell is hit when ``sk < lower[n]`` or ``sk > upper[n]``.
+    A NaN ``sk`` and a NaN table entry never hit.  ``out[.., t, f] = flags[..,
+    t, f] | hit[.., t // block_time, f]``.  ``sk`` float32 and ``count`` int32
+    of shape (bl, corr, ceil(time / block_time), chan), ``flags`` (bl, corr,
+    time, chan).  Returns a new array in the container / dtype of ``flags``;
+    the inputs are not modified."""
+    m = _sk_block(block_time)
+    lower, upper = _sk_tables(bounds, m)
+    shape = tuple(flags.shape)
+    if len(shape) != 4:
+        raise ValueError("flags must be 4-D (bl, corr, time, chan), got shape %s" % (shape,))
+    cells = (shape[0], shape[1], -(-shape[2] // m), shape[3])
+    for name, a, dt in (("sk", sk, "float32"), ("count", count, "int32")):
+        if tuple(a.shape) != cells:
+            raise ValueError("%s must have the shape %s, got %s" % (name, cells, tuple(a.shape)))
+        if str(a.dtype).replace("torch.", "") != dt:
+            raise ValueError("%s must be %s, got %s" % (name, dt, a.dtype))
+    torch = _require_gpu()
+    from_numpy = any(isinstance(a, np.ndarray) for a in (sk, count, flags))
+    device = next((a.device for a in (flags, sk, count) if torch.is_tensor(a) and a.is_cuda),
+                  torch.device("cuda", torch.cuda.current_device()))
+    f8 = _flags_u8(torch, flags, device)
+    s, c = (_sk_dev(torch, device, a) for a in (sk, count))
+    nbl, ncorr, ntime, nchan = (int(x) for x in shape)
+    n_win = nbl * ncorr
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            lo, hi = _sk_dev(torch, device, lower), _sk_dev(torch, device, upper)
+            launches, stream = _sk_launches(torch, device, n_win, ntime, nchan, m, _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_sk_apply(at(s), at(c), at(f8), at(out), b, ntime, nchan, m, lo.data_ptr(),
+                                            hi.data_ptr(), stream))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
+def _sk_dev(torch, device, a):
+    """A contiguous device tensor of a numpy array or tensor."""
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    return a.to(device).contiguous()
+
+
+def threshold_spectral_kurtosis(vis, flags, block_time=64, shape=1.0, min_samples=None, nsigma_low=4.0, nsigma_high=4.0,
+                                bounds=None, _max_windows=None):
+    """Flags whole (block of ``block_time`` rows, channel) cells of (bl, corr,
+    time, chan) windows whose spectral kurtosis (:func:`spectral_kurtosis`) is
+    not that of noise: above ``upper[n]`` -- pulsed or intermittent
+    interference, too sparse for the SumThreshold windows and too weak for a
+    line RMS -- or below ``lower[n]`` -- a steady carrier, which a background
+    fit absorbs as level.  No background, noise estimate or bandpass enters.
+    The tables are :func:`spectral_kurtosis_bounds` of ``nsigma_low`` /
+    ``nsigma_high`` (``None`` switches a side off), or ``bounds = (lower,
+    upper)`` in their place.  ``out = flags | hits``; a second round could not
+    change anything.  Where a bright source's fringe dominates the noise within
+    a block the estimator reads low without any interference: apply the step to
+    noise-dominated data (residuals), or with ``nsigma_low=None``.  Definition:
+    ``include/tricolour_amd.h``.  Returns a new array in the container / dtype
+    of ``flags``; the inputs are not modified."""
+    m, d, ms, lo, hi = check_spectral_kurtosis_kwargs(block_time, shape, min_samples, nsigma_low, nsigma_high)
+    lower, upper = spectral_kurtosis_bounds(m, d, lo, hi) if bounds is None else _sk_tables(bounds, m)
+    torch, v, f8, code, from_numpy, device = _medz_inputs("threshold_spectral_kurtosis", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            lo_t, hi_t = _sk_dev(torch, device, lower), _sk_dev(torch, device, upper)
+            launches, stream = _sk_launches(torch, device, n_win, ntime, nchan, m, _max_windows)
+            # the library's two statistics images of one batch at a time
+            sk = torch.empty((launches[0][1], -(-ntime // m), nchan), dtype=torch.float32, device=device)
+            cnt = torch.empty(sk.shape, dtype=torch.int32, device=device)
+            for at, b in launches:
+                _lib.check(lib.tri_sk_threshold(at(v), code, at(f8), at(out), b, ntime, nchan, m, d, ms, lo_t.data_ptr(),
+                                                hi_t.data_ptr(), sk.data_ptr(), cnt.data_ptr(), stream))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
 def _bli_inputs(name, vis, flags, select):
     """Checks of the baseline-integration calls (all before any device work), then the device inputs:
     (torch, vis, flags uint8, dtype code, from_numpy, device, select uint8 on the device or None)."""
