@@ -1000,6 +1000,109 @@ int tri_sk_threshold(const void *vis, int vis_dtype, const uint8_t *flags,
                      float *sk, int32_t *count,
                      void *stream);
 
+/*
+ * Piecewise-polynomial fit along the lines of a window and flagging of what
+ * stands off it (beyond the reference; after CASA's tfcrop, the definition
+ * with its operation order is this library's own).  Every line is normalised
+ * by itself: the fit absorbs a bandpass shape, a fringe or a gain drift, and
+ * the threshold is the scatter about the fit on the same line.
+ * vis (n_win, ntime, nchan) complex64 or float32, flags of the same shape,
+ * any non-zero byte is flagged; windows are independent.
+ *   a      = the float32 amplitude: complex64 (float)sqrt((double)re *
+ *            (double)re + (double)im * (double)im), +inf when a part is
+ *            infinite; float32 fabsf(x).
+ *   valid  = flag == 0 and a is finite.
+ * All arithmetic below is float64, one correctly rounded operation at a time
+ * in the order written; nothing is fused; division and sqrt are IEEE.
+ *   fit of one line a[0..n) under a mask m, P pieces, degree D in 0..3:
+ *            piece p covers [e_p, e_{p+1}) with e_p = (p * n) / P (integer
+ *            division); a piece may be empty.  In a piece of length L the
+ *            sample j = i - e_p has x = (double)(2 * j + 1 - L) / (double)L.
+ *     moments: two-level sums with cells of 32 consecutive samples counted
+ *            from the piece start.  Within a cell, from +0.0, in ascending j
+ *            over the masked samples, with pw_0 = 1.0 and pw_k = pw_{k-1} * x:
+ *            s_k = s_k + pw_k (k = 0..2D), b_k = b_k + pw_k * (double)a
+ *            (k = 0..D).  S_k and B_k are the cell sums added from +0.0 in
+ *            ascending cell order; n_p is the masked count of the piece.  The
+ *            two-level order is part of the definition; a sequential, tree or
+ *            pairwise sum over the piece is a different result and is wrong.
+ *     solve: n_p == 0: the fit is NaN over the piece.  Otherwise d = min(D,
+ *            n_p - 1) and A[i][j] = S_{i+j} (i, j <= d) is factored by
+ *            Cholesky, column j = 0..d:  v = A[j][j], then v = v - l[j][k] *
+ *            l[j][k] for k = 0..j-1 one term at a time.  If !(v > 0x1p-20 *
+ *            S_0): d = j - 1, the leading factor is kept and the factoring
+ *            ends (samples clustered in a corner of a piece get a lower
+ *            degree, down to the mean).  Else l[j][j] = sqrt(v) and for i > j:
+ *            t = A[i][j], t = t - l[i][k] * l[j][k] for k = 0..j-1 one term at
+ *            a time, l[i][j] = t / l[j][j].  Forward: for i = 0..d, t = B_i,
+ *            t = t - l[i][k] * y_k for k = 0..i-1, y_i = t / l[i][i].  Back:
+ *            for i = d..0, t = y_i, t = t - l[k][i] * c_k for k = i+1..d in
+ *            ascending k, c_i = t / l[i][i].
+ *     value: Horner from c_d down: f = c_d, then f = f * x + c_k for
+ *            k = d-1..0.  Residual r = (double)a - f.
+ *   rounds on one line with the starting mask m0, max_pieces, degree, cutoff,
+ *            rounds, min_samples: hit = 0; for r = 0..rounds-1: m = m0 & ~hit;
+ *            P = min(2r + 1, max_pieces); the degree is min(1, degree) in round
+ *            0 and degree after it; n_m = the masked count of the line; if n_m
+ *            < min_samples the rounds end.  Fit.  Q: the cell sums of r * r
+ *            (the cells of the fit, chains in ascending j over the masked
+ *            samples, from +0.0) added from +0.0 in ascending cell order
+ *            within a piece, pieces ascending -- one chain over all cells of
+ *            the line.  sigma = sqrt(Q / (double)n_m).  A masked sample is hit
+ *            when fabs(r) > cutoff * sigma and fabs(r) > fabs(f) * 0x1p-20;
+ *            the second condition keeps noise-free data from being flagged on
+ *            rounding residue.
+ *   step:    order 0 = freqtime (along frequency: every time row is a line;
+ *            then along time: every channel is a line), 1 = timefreq, 2 = freq
+ *            only, 3 = time only.  The first pass has m0 = valid, the second
+ *            m0 = valid & ~hits_first.  out = (flags != 0) | hits_time |
+ *            hits_freq, 0 or 1.  The inputs are never written.
+ *   ranges:  cutoffs finite and > 0, degrees in 0..3, pieces in 1..32, rounds
+ *            in 1..16, min_samples >= 2.  tfcrop's defaults: time cutoff 4.0,
+ *            degree 1, 1 piece; frequency cutoff 3.0, degree 3, 7 pieces;
+ *            5 rounds, min_samples 8.
+ * tri_polyfit_background does one fit per line of `axis` (0 = time, 1 =
+ * frequency) with m = valid, `pieces` pieces and `degree`, no rounds:
+ * background (n_win, ntime, nchan) float32 is (float)f at EVERY sample, flagged
+ * ones included, and the NaN 0x7FC00000 where a piece has no valid sample (and
+ * for any other NaN).  Called with the flags of tri_polyfit_threshold it is the
+ * robust bandpass or time trend.
+ * A fitted line holds at most 16384 samples: a longer ntime (when the time axis
+ * is fitted) or nchan (when the frequency axis is) is TRI_EUNSUPPORTED before
+ * any launch; the axis that is not fitted has no such limit.
+ * scratch: a device buffer of tri_polyfit_workspace_bytes(n_win, ntime, nchan,
+ * time_pieces) bytes, with time_pieces the pieces of the fit along time (0
+ * when no fit runs along time; 0..32, anything else gives 0).  It holds the
+ * amplitudes, one state byte per sample and the fits of the time pass; its
+ * prior contents do not matter (tests/test_polyfit.py fills it with 0xFF and
+ * with zeros before every call of the C entry points).  The
+ * sums run in the order above whatever the alignment and however the windows
+ * are split over calls: the same bits on every run.
+ * TRI_EINVAL for NULL pointers, negative shapes, an order, axis, cutoff,
+ * degree, pieces, rounds or min_samples out of range or NaN, and an output or
+ * the scratch buffer overlapping an input or each other; TRI_EUNSUPPORTED for vis
+ * dtypes other than complex64 and float32, for a fitted line of more than 16384
+ * samples and for more lines than one launch holds (pass fewer windows per
+ * call); TRI_EWORKSPACE for a NULL or short scratch buffer.  Empty shapes return
+ * TRI_OK without a launch.
+ */
+size_t tri_polyfit_workspace_bytes(int64_t n_win, int64_t ntime, int64_t nchan,
+                                   int64_t time_pieces);
+int tri_polyfit_background(const void *vis, int vis_dtype, const uint8_t *flags,
+                           int64_t n_win, int64_t ntime, int64_t nchan,
+                           int axis, int64_t pieces, int64_t degree,
+                           float *background,
+                           void *scratch, size_t scratch_bytes, void *stream);
+int tri_polyfit_threshold(const void *vis, int vis_dtype, const uint8_t *flags,
+                          uint8_t *out_flags,
+                          int64_t n_win, int64_t ntime, int64_t nchan, int order,
+                          double time_cutoff, int64_t time_degree,
+                          int64_t time_pieces,
+                          double freq_cutoff, int64_t freq_degree,
+                          int64_t freq_pieces,
+                          int64_t rounds, int64_t min_samples,
+                          void *scratch, size_t scratch_bytes, void *stream);
+
 /* Thread-local description of the last failure in the calling thread. */
 const char *tri_last_error(void);
 

@@ -131,7 +131,7 @@ static inline void tri_klog(const void* fn) {
     } while (0)
 
 extern "C" const char* tri_last_error(void) { return g_err; }
-extern "C" int tri_version(void) { return 111; }
+extern "C" int tri_version(void) { return 112; }
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

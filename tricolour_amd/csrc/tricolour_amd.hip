@@ -37,6 +37,7 @@
 #include "steps/medz/kernels_medz.hpp"
 #include "steps/antint/kernels_antint.hpp"
 #include "steps/sk/kernels_sk.hpp"
+#include "steps/polyfit/kernels_polyfit.hpp"
 
 // ===========================================================================
 // host side
@@ -2788,3 +2789,4 @@ extern "C" int tri_uvcontsub_flagger_debug(const void* vis_c64, const uint8_t* f
 #include "steps/medz/medz_host.hpp"
 #include "steps/antint/antint_host.hpp"
 #include "steps/sk/sk_host.hpp"
+#include "steps/polyfit/polyfit_host.hpp"

@@ -1524,6 +1524,134 @@ def threshold_spectral_kurtosis(vis, flags, block_time=64, shape=1.0, min_sample
     return _like_flags(torch, out, flags, from_numpy)
 
 
+PF_ORDERS = ("freqtime", "timefreq", "freq", "time")    # the `order` vocabulary of the polynomial-fit step, by ABI code
+PF_AXES = ("time", "freq")                              # the `axis` vocabulary of its background call, by ABI code
+PF_MAX_PIECES = 32
+PF_MAX_ROUNDS = 16
+PF_MAX_LINE = 16384         # longest fitted line, either axis
+
+
+def _pf_int(name, v, lo, hi):
+    k = _medz_int(name, v)
+    if k is None or not lo <= k <= hi:
+        raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    return k
+
+
+def _pf_cutoff(name, v):
+    try:
+        ok = not isinstance(v, bool) and 0.0 < float(v) < float("inf")       # also rejects NaN
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be a finite number > 0, got %r" % (name, v))
+    return float(v)
+
+
+def check_polyfit_kwargs(order="freqtime", time_cutoff=4.0, time_degree=1, time_pieces=1, freq_cutoff=3.0, freq_degree=3,
+                         freq_pieces=7, rounds=5, min_samples=8):
+    """The argument checks of :func:`threshold_polyfit` (no device work): an ``order`` outside ``freqtime``,
+    ``timefreq``, ``freq``, ``time``, a cutoff that is not a finite number > 0, a degree that is no integer in [0, 3],
+    pieces outside [1, 32], ``rounds`` outside [1, 16] and ``min_samples`` that is no integer >= 2 raise ``ValueError``
+    naming the argument; booleans are no numbers here.  Returns the values in the order of the arguments."""
+    if not isinstance(order, str) or order not in PF_ORDERS:
+        raise ValueError("order must be one of %s, got %r" % (", ".join(PF_ORDERS), order))
+    return (order, _pf_cutoff("time_cutoff", time_cutoff), _pf_int("time_degree", time_degree, 0, 3),
+            _pf_int("time_pieces", time_pieces, 1, PF_MAX_PIECES), _pf_cutoff("freq_cutoff", freq_cutoff),
+            _pf_int("freq_degree", freq_degree, 0, 3), _pf_int("freq_pieces", freq_pieces, 1, PF_MAX_PIECES),
+            _pf_int("rounds", rounds, 1, PF_MAX_ROUNDS), _pf_int("min_samples", min_samples, 2, (1 << 31) - 1))
+
+
+def _pf_cap(ntime, nchan):
+    """Windows one launch of the polynomial-fit family holds (every launch is one-dimensional and holds fewer than
+    2^31 blocks: one per time row in the frequency pass, one per 256 samples in the prepare and finish passes)."""
+    return ((1 << 31) - 1) // (ntime * -(-nchan // 256))
+
+
+def _pf_line_limit(shape, time, freq):
+    """The library's limit on a fitted line, from the input's shape alone: raised before any device work (a shape that is
+    not 4-D is left to the input checks)."""
+    if len(shape) != 4:
+        return
+    ntime, nchan = int(shape[2]), int(shape[3])
+    if (time and ntime > PF_MAX_LINE) or (freq and nchan > PF_MAX_LINE):
+        raise NotImplementedError("a fitted line holds at most %d samples, got %d times and %d channels"
+                                  % (PF_MAX_LINE, ntime, nchan))
+
+
+def polyfit_background(vis, flags, axis="freq", pieces=1, degree=3, _max_windows=None):
+    """Piecewise-polynomial fit along every line of one axis of (bl, corr, time,
+    chan) windows: ``axis="freq"`` fits each time row over its channels (a
+    bandpass), ``axis="time"`` each channel over its rows (a time trend).  The
+    line is cut into ``pieces`` equal pieces, each fitted by least squares with
+    a polynomial of ``degree`` (0..3) to the amplitudes of its unflagged,
+    finite samples; a piece whose samples cannot carry the degree gets a lower
+    one, down to the mean.  Returns the fit as float32 of the shape of ``vis``,
+    evaluated at EVERY sample, flagged ones included, NaN where a piece holds
+    no usable sample -- a numpy array for numpy input, a tensor on the device
+    otherwise.  One fit, no rejection: call it with the flags of
+    :func:`threshold_polyfit` for the robust curve.  Definition:
+    ``include/tricolour_amd.h``.  Lines of more than 16384 samples raise
+    ``NotImplementedError``.  Inputs are not modified."""
+    if not isinstance(axis, str) or axis not in PF_AXES:
+        raise ValueError("axis must be one of %s, got %r" % (", ".join(PF_AXES), axis))
+    pieces = _pf_int("pieces", pieces, 1, PF_MAX_PIECES)
+    degree = _pf_int("degree", degree, 0, 3)
+    time = axis == "time"
+    _pf_line_limit(tuple(vis.shape), time, not time)
+    torch, v, f8, code, from_numpy, device = _medz_inputs("polyfit_background", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    bg = torch.empty(v.shape, dtype=torch.float32, device=device)
+    lib = _lib.lib()
+    tp = pieces if time else 0
+    with torch.cuda.device(device):
+        if v.numel() > 0:
+            launches, tail = _window_launches(
+                torch, device, n_win, lambda b: lib.tri_polyfit_workspace_bytes(b, ntime, nchan, tp), _pf_cap(ntime, nchan),
+                _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_polyfit_background(at(v), code, at(f8), b, ntime, nchan, PF_AXES.index(axis), pieces,
+                                                      degree, at(bg), *tail))
+    return _like_input(from_numpy, bg)[0]
+
+
+def threshold_polyfit(vis, flags, order="freqtime", time_cutoff=4.0, time_degree=1, time_pieces=1, freq_cutoff=3.0,
+                      freq_degree=3, freq_pieces=7, rounds=5, min_samples=8, _max_windows=None):
+    """Flags single samples of (bl, corr, time, chan) windows that stand off a
+    robust piecewise-polynomial fit along their line (after CASA's ``tfcrop``;
+    the definition is this library's own).  Every line is normalised by itself:
+    the fit absorbs a bandpass shape, a fringe or a gain drift, and the
+    threshold is the scatter about the fit on the same line, so it works on
+    uncalibrated data.  Per line, ``rounds`` rounds: fit the samples not yet
+    hit -- a straight line over the whole line first, then ``min(2 r + 1,
+    pieces)`` pieces of ``degree`` -- and hit those whose residual exceeds
+    ``cutoff`` times the RMS residual of the round.  Lines with fewer than
+    ``min_samples`` usable samples are left alone.  ``order``: ``"freqtime"``
+    (along frequency, then along time on what is left), ``"timefreq"``,
+    ``"freq"`` or ``"time"``.  ``out = flags | hits``.  Definition:
+    ``include/tricolour_amd.h``.  Lines of more than 16384 samples along a
+    fitted axis raise ``NotImplementedError``.  Returns a new array in the
+    container / dtype of ``flags``; the inputs are not modified."""
+    order, ct, dt, pt, cf, df, pf, rounds, ms = check_polyfit_kwargs(
+        order, time_cutoff, time_degree, time_pieces, freq_cutoff, freq_degree, freq_pieces, rounds, min_samples)
+    _pf_line_limit(tuple(vis.shape), order != "freq", order != "time")
+    torch, v, f8, code, from_numpy, device = _medz_inputs("threshold_polyfit", vis, flags)
+    nbl, ncorr, ntime, nchan = (int(s) for s in v.shape)
+    n_win = nbl * ncorr
+    out = torch.empty(f8.shape, dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    with torch.cuda.device(device):
+        if out.numel() > 0:
+            launches, tail = _window_launches(
+                torch, device, n_win, lambda b: lib.tri_polyfit_workspace_bytes(b, ntime, nchan, pt),
+                _pf_cap(ntime, nchan), _max_windows)
+            for at, b in launches:
+                _lib.check(lib.tri_polyfit_threshold(at(v), code, at(f8), at(out), b, ntime, nchan, PF_ORDERS.index(order),
+                                                     ct, dt, pt, cf, df, pf, rounds, ms, *tail))
+    return _like_flags(torch, out, flags, from_numpy)
+
+
 def _bli_inputs(name, vis, flags, select):
     """Checks of the baseline-integration calls (all before any device work), then the device inputs:
     (torch, vis, flags uint8, dtype code, from_numpy, device, select uint8 on the device or None)."""
